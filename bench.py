@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of the fused RIS-VEC step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5|big]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5|big] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over the whole resident env batch: every env advances by one
 `Environ.step()` with its RIS cascaded channel gains recomputed from h_r and theta in the same launch
@@ -15,9 +15,15 @@ it starts N rank processes (`python -m torch.distributed.run`, one per GPU, rend
 with their code.  It never runs fewer ranks than asked: too few devices, a world size that differs from
 `--gpus`, or a gather that cannot be constructed end the run with a non-zero exit code.
 
-Rank 0 prints ONE JSON line with the driver's contract fields plus `roofline`, `cpu_baseline` and `legs` (the
-other BASELINE configs measured in the same process: configs[1], a configs[3] shard, configs[4], and the
-headline kernel on a working set far beyond the 256 MiB Infinity Cache).
+Rank 0 prints ONE JSON line with the driver's contract fields plus `roofline`, `cpu_baseline` and `legs`.  A plain
+run sets up, warms up, times the K steps and prints the line: `cpu_baseline` is null, `legs` is empty and
+`roofline.yardstick` is null.  `--full` adds the measurements that take runs of their own: the CPU baseline, the
+streaming yardstick and the `legs` (the other BASELINE configs measured in the same process: configs[1], a
+configs[3] shard, configs[4], and the headline kernel on a working set far beyond the 256 MiB Infinity Cache).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step as
+DIR/<name>.npy (float32 / float64; rank 0's envs; a fixed seeded sample of the envs if the whole would exceed
+64 MB).  The inputs depend only on the arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -400,7 +406,43 @@ class Case:
             meter_add = meter.bind(env)
         self.grouper, self.marshal, self.group, self.launch, self.store = grouper, marshal, group, launch, store
         self.meter, self.meter_add = meter, meter_add
+        self.replay = replay if opts.replay else None
         self.keep = (action, partner, n_groups, p_off01)
+
+    def outputs(self) -> dict:
+        """What the timed path handed its caller in its last step (tensors with the env axis first): the step's
+        outputs and the observation / metrics it wrote, plus the grouping, the transitions stored, the policy's
+        actions and the episode sums where those stages ran."""
+        t = self.env.tensors                            # (materialises theta if the sweeps kept it by index)
+        if self.mode == "sarl":
+            out = {k: t[k] for k in ("data_buf", "data_t", "data_p", "over_power", "over_data", "gain")}
+            out["global_reward"] = t["metrics"][:, 0]
+        else:
+            out = {k: t[k] for k in ("reward", "data_buf", "data_t", "data_p", "over_power", "over_data", "mec_q")}
+            if self.fused:
+                out["gain"] = t["gain"]
+            if self.full:
+                out["metrics"] = t["metrics"]
+            if self.opts.meter:
+                out["power_w"] = t["power_w"]
+        if self.full:
+            out["obs"] = t["obs"]
+        if self.bcd:
+            out["theta"] = t["theta"]
+        if self.grouper is not None:
+            g = self.grouper._t
+            out.update(partner=g["partner"], n_groups=g["n_groups"], noma_mask=self.grouper.mask)
+        if self.opts.policy:
+            out["action"] = self.keep[0]
+        if self.replay is not None:
+            rb = self.replay
+            rows = (rb.mem_cntr - self.E + torch.arange(self.E, device=self.device)) % rb.mem_size
+            for k in ("state_memory", "action_memory", "reward_global_memory", "reward_local_memory", "new_state_memory",
+                      "terminal_memory", "mask_memory"):
+                out["replay_" + k] = getattr(rb, k)[rows]
+        if self.meter is not None:
+            out["episode_acc"] = self.meter.acc.t()
+        return out
 
     def one_step(self, i: int) -> None:
         L = self.episode_len
@@ -608,11 +650,49 @@ class StubCase:
     def kernel_name(self):
         return "stub (no GPU work)"
 
+    def outputs(self):
+        return {"obs": self.obs}
+
     def close(self):
         self.gather = None
 
 
 GATHER_SLOTS = 4        # (stage, output) slots of the joint-observation gather: up to 4 gathers in flight
+
+DUMP_LIMIT_BYTES = 64 * 10**6     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path: str, outs: dict, E: int) -> dict:
+    """Write each output as <path>/<name>.npy: float64 stays float64, integers and booleans become float64 (exact),
+    everything else float32 (complex as [..., 2]).  Arrays whose first axis is the E envs are cut to a fixed seeded
+    sample of the envs (sorted; written as env_index.npy) when the whole would exceed DUMP_LIMIT_BYTES."""
+    arrs = {}
+    for name, t in outs.items():
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        arrs[name] = t.to(dt)
+    per_env = sum(a[0].numel() * a.element_size() for a in arrs.values() if a.dim() and a.shape[0] == E)
+    fixed = sum(a.numel() * a.element_size() for a in arrs.values() if not (a.dim() and a.shape[0] == E))
+    head = 128 * (len(arrs) + 1)                      # .npy headers
+    idx = None
+    if per_env * E + fixed + head > DUMP_LIMIT_BYTES:
+        k = max(1, (DUMP_LIMIT_BYTES - fixed - head) // (per_env + 8))
+        idx = np.sort(np.random.default_rng(0).choice(E, size=min(k, E), replace=False))
+    os.makedirs(path, exist_ok=True)
+    written = 0
+    for name, a in arrs.items():
+        if idx is not None and a.dim() and a.shape[0] == E:
+            a = a[torch.from_numpy(idx).to(a.device)]
+        a = a.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        written += a.nbytes
+    if idx is not None:
+        np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
+        written += idx.size * 8
+    return dict(dir=path, arrays=len(arrs) + (idx is not None), bytes=written,
+                envs=E if idx is None else int(idx.size))
 
 
 def main() -> None:
@@ -630,8 +710,14 @@ def main() -> None:
                     help="N>1: all-gather the joint observation every k steps on a side stream (0 = never).  Default 32 at "
                          "32 768 envs/GPU (one gather moves 5.2 MB per rank over point-to-point xGMI links, several env "
                          "steps' worth of time, so it is amortised), 1 with --config c4 (1.3 MB per rank, BASELINE configs[3])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary workloads (`legs` in the JSON line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the streaming yardstick "
+                         "(roofline.yardstick) and, at the default shape, the secondary workloads (`legs`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, rank 0's envs, a seeded sample of them beyond 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the secondary workloads (`legs` in the JSON line)")
     ap.add_argument("--lean", action="store_true", help="experiment: skip metrics and obs writes")
     ap.add_argument("--steer", action="store_true",
                     help="fused / bcd modes: the steering form of the gain+step kernel (RISVEC_STEP_STEER): h_r is not "
@@ -691,7 +777,7 @@ def main() -> None:
 
     # ---- CPU baseline first: its process-per-core replicas are forked, which must precede the first GPU call
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub:
         cpu = cpu_baseline(args.veh, args.ris)
 
     from ris_vec_marl_amd import dist as rdist
@@ -711,6 +797,9 @@ def main() -> None:
     start, _ = rdist.shard_range(E * world, rank, world)
     case = (StubCase if STUB else Case)(E, V, M, args.mode, device, rank, world, start, args, args.gather_every)
     dt, kernel_ms = case.run(args.steps, args.warmup, world)
+    if args.dump_outputs and rank == 0:
+        d = dump_outputs(args.dump_outputs, case.outputs(), E)
+        sys.stderr.write("bench.py: wrote %d arrays, %.1f MB (%d envs) to %s\n" % (d["arrays"], d["bytes"] / 1e6, d["envs"], d["dir"]))
     gather_ok = getattr(case, "gather_ok", True)
     case_ring_fused = getattr(case, "ring_fused", False)
     case_placement = getattr(getattr(case, "env", None), "placement", None)    # h_r placed by measurement (streams beyond the cache)
@@ -723,7 +812,7 @@ def main() -> None:
     # ---- secondary workloads, same process, same protocol (every rank takes part: they contain barriers)
     legs = {}
     default_shape = (E, V, M, args.mode) == CONFIGS["c3"][:4] and not (args.noma or args.lean or args.steer or args.meter)
-    if default_shape and not args.no_legs:
+    if args.full and default_shape and not args.no_legs:
         if world == 1:
             legs["hbm_only"] = run_leg("hbm_only", 262144, 8, 64, "fused", device, rank, world, 200, 30)
             legs["c2"] = run_leg("c2", *CONFIGS["c2"][:4], device, rank, world, 2000, 200)
@@ -746,7 +835,7 @@ def main() -> None:
     if (E, V, M, args.mode) == (32768, 8, 64, "fused") and full and not args.steer and not STUB:
         traffic, traffic_src = measured_traffic("k_step_fused")
     yard = None
-    if world == 1 and fused and not args.steer and not STUB:
+    if args.full and world == 1 and fused and not args.steer and not STUB:
         yard = yardstick_read(int(per_env * E), device)
     work = {"fused": "RIS cascaded gains + step()", "cached": "step() on cached gains",
             "bcd": "BCD sweep + gains + step()", "sarl": "SARL get_next_phase + gains + step()"}[args.mode]
@@ -791,7 +880,7 @@ def main() -> None:
                      "yardstick": yard,
                      "frac_of_yardstick": (achieved / yard["GBps"]) if yard else None,
                      "note": ("working set %.0f MB < 256 MiB Infinity Cache: h_r / theta re-reads are partly served on-die; "
-                              "legs.hbm_only is the same kernel on 1.36 GB" % (bytes_per_launch / 1e6))
+                              "legs.hbm_only (--full) is the same kernel on 1.36 GB" % (bytes_per_launch / 1e6))
                              if bytes_per_launch < (256 << 20) else "working set beyond the Infinity Cache"},
         "legs": legs,
     }

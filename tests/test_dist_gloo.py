@@ -123,12 +123,12 @@ def test_bench_launcher_spawns_the_ranks_it_was_asked_for():
 
 
 def test_bench_scale_command_with_eight_ranks():
-    """The command the driver's SCALE step issues -- `python bench.py --gpus 8` with the default workload -- end to end on
-    CPU (gloo, the HIP step stubbed out): 8 rank processes, 32 768 envs per rank, the three BASELINE configs[3] legs
+    """The command the driver's SCALE step issues -- `python bench.py --gpus 8 --full` with the default workload -- end to end
+    on CPU (gloo, the HIP step stubbed out): 8 rank processes, 32 768 envs per rank, the three BASELINE configs[3] legs
     (8 192 envs per rank with the all-gather every step / every 32 steps / off), every gather's contents checked on
     rank 0, and the JSON schema of the real line (`n_gpus`, `legs`, the backend named)."""
     import json
-    r = _bench("--gpus", "8", "--stub", "--steps", "6", "--warmup", "2", timeout=600)
+    r = _bench("--gpus", "8", "--stub", "--steps", "6", "--warmup", "2", "--full", timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -143,6 +143,23 @@ def test_bench_scale_command_with_eight_ranks():
     assert d["gather_ok"] is True and abs(d["max_over_ranks_s"] - 0.008) < 1e-12      # MAX over 8 ranks
     for key in ("metric", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "vs_baseline", "dtype", "data", "roofline"):
         assert key in d, key
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline only (no legs, no CPU baseline, no yardstick); --dump-outputs writes
+    what the timed path left after its last step (here the stub's observation: rank 0 holds 2 + 5 steps' increments)."""
+    import json
+    out = tmp_path / "out"
+    r = _bench("--gpus", "2", "--stub", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["legs"] == {} and d["cpu_baseline"] is None and d["roofline"]["yardstick"] is None
+    assert d["steps"] == 5 and "ms_per_step" in d
+    assert sorted(os.listdir(out)) == ["obs.npy"]
+    obs = np.load(out / "obs.npy")
+    assert obs.dtype == np.float32 and obs.shape == (32768, 8, 5) and (obs == 7.0).all()
 
 
 def test_bench_never_silently_runs_fewer_ranks():

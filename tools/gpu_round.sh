@@ -15,7 +15,7 @@ grep "parity margin" $OUT/pytest_$TAG.log | sed "s/^[.]*//" | sort -u > $OUT/mar
 echo "== smoke" | tee -a $OUT/round_$TAG.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee -a $OUT/round_$TAG.log
 echo "== bench" | tee -a $OUT/round_$TAG.log
-timeout -k 10 600 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 600 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 echo "bench rc=$?" | tee -a $OUT/round_$TAG.log
 cat $OUT/bench_$TAG.json | tee -a $OUT/round_$TAG.log
 tail -3 $OUT/bench_$TAG.err
