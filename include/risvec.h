@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RISVEC_ABI_VERSION 15
+#define RISVEC_ABI_VERSION 16
 #define RISVEC_POISSON_TABLE 64   /* entries of the arrival CDF table            */
 #define RISVEC_MAX_LANES 8        /* lane coordinates per direction (ref. has 4) */
 #define RISVEC_MAX_VEH 64         /* V <= 64: one env's vehicles fit a wavefront */
@@ -222,6 +222,39 @@ uint32_t risvec_abi_version(void);
  * member of the fused-step family a shape / batch size takes is a dispatch decision; tests assert it. */
 const char *risvec_last_kernel(void);
 const char *risvec_last_error(void);
+
+/* Forms of a step call, for risvec_step_kernel(): risvec_step, risvec_step_fused, risvec_step_ring (cached / fused),
+ * the T-step launch of risvec_step_fused_multi. */
+enum {
+    RISVEC_FORM_CACHED = 0,
+    RISVEC_FORM_FUSED = 1,
+    RISVEC_FORM_CACHED_RING = 2,
+    RISVEC_FORM_FUSED_RING = 3,
+    RISVEC_FORM_FUSED_MULTI = 4
+};
+/* Name of the kernel a step call of this `form` with these `flags` would launch for this state's shape and batch size,
+ * without launching: the same selector the launchers use, so risvec_last_kernel() after the call returns the same
+ * string.  NULL when the form does not exist for the shape (risvec_last_error() says why).  Host-only; reads no
+ * device memory. */
+const char *risvec_step_kernel(const RisVecState *s, uint32_t flags, int32_t form);
+
+/* FOR TESTS AND SAME-BOX A/Bs ONLY: force a kernel form the dispatch rules would not pick at this size.  Every field
+ * is RISVEC_BY_RULE (0) by default: the rules decide.  The forms compute the same bits; only speed differs.  Applies
+ * process-wide to later launches; set it from one thread, between launches.  risvec_force_forms(NULL) restores the
+ * rules. */
+enum { RISVEC_BY_RULE = 0, RISVEC_FORCE_OFF = 1, RISVEC_FORCE_ON = 2 };
+typedef struct RisVecForce {
+    uint32_t abi_version;       /* = RISVEC_ABI_VERSION                                       */
+    uint32_t struct_bytes;      /* = sizeof(RisVecForce)                                      */
+    int32_t lat;                /* latency-shaped single step where the shape has a software pipeline: OFF never
+                                   (the pipeline), ON at every batch size                     */
+    int32_t lat_epw;            /* its envs per wavefront: 0 by rule, or 1 / 2 / 4 (clamped to the shape's members) */
+    int32_t lat_nt;             /* its non-temporal form                                      */
+    int32_t lat_alt;            /* its alternating walk (taken where the non-temporal form is not) */
+    int32_t pipe_nt;            /* non-temporal loads in the software pipeline (MARL, SARL and gain)   */
+    int32_t colsum_nt;          /* non-temporal loads in the BCD column sums                  */
+} RisVecForce;
+int risvec_force_forms(const RisVecForce *f);
 
 /* Fill `p` with the class defaults of ENV:57-190 and the reference driver's lanes
  * (marl_train_bcd.py:446-449).  Host-only helper. */

@@ -5,10 +5,11 @@ raises at import of the symbol table, and every compute call goes through HIP.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 POISSON_TABLE = 64
 MAX_LANES = 8
 MAX_VEH = 64
@@ -26,6 +27,8 @@ STEP_STEER = 64
 STEP_REUSE_IDX = 128
 STEP_THETA_BY_INDEX = 256
 BCD_REUSE_COLSUM, BCD_REUSE_SSUM, BCD_REUSE_IDX, BCD_NO_THETA = 1, 2, 4, 8
+FORM_CACHED, FORM_FUSED, FORM_CACHED_RING, FORM_FUSED_RING, FORM_FUSED_MULTI = range(5)
+BY_RULE, FORCE_OFF, FORCE_ON = range(3)
 
 METRIC_NAMES = (
     "global_reward", "last_off_kbit_sum", "last_local_kbit_sum", "last_mec_queue_cycles",
@@ -126,6 +129,11 @@ class RisVecStepRing(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class RisVecForce(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("struct_bytes", C.c_uint32), ("lat", C.c_int32), ("lat_epw", C.c_int32),
+                ("lat_nt", C.c_int32), ("lat_alt", C.c_int32), ("pipe_nt", C.c_int32), ("colsum_nt", C.c_int32)]
+
+
 NOMA_MAX_VEH = 16
 NOMA_HAS_LAST, NOMA_UNSTICK_USED, NOMA_HAS_GROUPS = 1, 2, 4
 
@@ -136,6 +144,8 @@ _PROTOS = {
     "risvec_abi_version": (C.c_uint32, []),
     "risvec_last_error": (C.c_char_p, []),
     "risvec_last_kernel": (C.c_char_p, []),
+    "risvec_step_kernel": (C.c_char_p, [C.POINTER(RisVecState), C.c_uint32, C.c_int32]),
+    "risvec_force_forms": (C.c_int, [C.POINTER(RisVecForce)]),
     "risvec_default_params": (None, [C.POINTER(RisVecParams)]),
     "risvec_reset": (C.c_int, [C.POINTER(RisVecState), C.POINTER(RisVecParams), _FP, _FP,
                                C.c_uint64, C.c_uint32, _FP]),
@@ -248,6 +258,31 @@ def last_kernel() -> str:
     """Name of the kernel the calling thread's last step / BCD call dispatched (risvec_last_kernel)."""
     k = load().risvec_last_kernel()
     return k.decode() if k else ""
+
+
+def step_kernel(state, flags: int = 0, form: int = FORM_FUSED):
+    """Name of the kernel a step call of this form would launch for `state` (risvec_step_kernel), without launching;
+    None when the shape has no such form."""
+    k = load().risvec_step_kernel(C.byref(state), flags, form)
+    return k.decode() if k else None
+
+
+@contextlib.contextmanager
+def forced(**fields):
+    """FOR TESTS AND SAME-BOX A/Bs ONLY: force kernel forms inside the block (risvec_force_forms), the dispatch rules
+    again after it.  lat / lat_nt / lat_alt / pipe_nt / colsum_nt: True forces the form on, False off; lat_epw: 1, 2 or 4."""
+    f = RisVecForce(abi_version=ABI_VERSION, struct_bytes=C.sizeof(RisVecForce))
+    names = {n for n, _ in RisVecForce._fields_} - {"abi_version", "struct_bytes"}
+    for k, v in fields.items():
+        if k not in names:
+            raise TypeError("forced(): no field %r" % k)
+        setattr(f, k, v if k == "lat_epw" else (FORCE_ON if v else FORCE_OFF))
+    lib = load()
+    check(lib.risvec_force_forms(C.byref(f)))
+    try:
+        yield
+    finally:
+        lib.risvec_force_forms(None)
 
 
 class RisVecError(RuntimeError):

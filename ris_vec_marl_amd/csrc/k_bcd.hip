@@ -806,11 +806,9 @@ k_bcd_sweep8_pair(Dims d, const double* __restrict__ c_col, float* __restrict__ 
 // launchers
 // ---------------------------------------------------------------------------
 hipError_t launch_colsum(const RisVecState& s, hipStream_t st) {
-    static const bool no_slab = std::getenv("RISVEC_NO_COLSUM_SLAB") != nullptr;       // A/B switches for experiments
-    static const bool no_rows = std::getenv("RISVEC_NO_COLSUM_ROWS") != nullptr;
-    if (s.n_ris == kRowsM && s.n_veh <= 16 && !no_rows && !no_slab) {
-        static const char* nt_env = std::getenv("RISVEC_COLSUM_NT");              // "0" / "1" force it off / on (tests, A/B)
-        const bool nt = nt_env ? nt_env[0] == '1' : (long long)s.n_envs * s.n_veh * s.n_ris * 8 > tuning().colsum_nt_from;
+    // h_r streams larger than the Infinity Cache are read with the non-temporal hint (see launch_pipe)
+    const bool nt = forced_or(forced_forms().colsum_nt, (long long)s.n_envs * s.n_veh * s.n_ris * 8 > tuning().colsum_nt_from);
+    if (s.n_ris == kRowsM && s.n_veh <= 16) {
         const dim3 g((unsigned)(((long long)s.n_envs + kRowsEnvs - 1) / kRowsEnvs)), b(kRowsThreads);
         if (s.n_veh <= 8) {
             if (nt) hipLaunchKernelGGL((k_colsum_rows256<8, true>), g, b, 0, st, dims_of(s), s.h_r, s.b, s.c_col);
@@ -821,12 +819,9 @@ hipError_t launch_colsum(const RisVecState& s, hipStream_t st) {
         }
         return hipGetLastError();
     }
-    if (s.n_ris % kSlabM == 0 && s.n_veh <= 16 && !no_slab) {
+    if (s.n_ris % kSlabM == 0 && s.n_veh <= 16) {
         const long long blocks = ((long long)s.n_envs + kWave - 1) / kWave;
         if (blocks < (1LL << 31)) {
-            // h_r streams larger than the Infinity Cache are read with the non-temporal hint (see launch_pipe)
-            static const char* nt_env = std::getenv("RISVEC_COLSUM_NT");          // "0" / "1" force it off / on (tests, A/B)
-            const bool nt = nt_env ? nt_env[0] == '1' : (long long)s.n_envs * s.n_veh * s.n_ris * 8 > tuning().colsum_nt_from;
             const dim3 g((unsigned)blocks), b(kSlabThreads);
             if (s.n_veh <= 8) {
                 if (nt) hipLaunchKernelGGL((k_colsum_slab<8, true>), g, b, 0, st, dims_of(s), s.h_r, s.b, s.c_col);
@@ -901,8 +896,7 @@ hipError_t launch_bcd(const RisVecState& s, const RisVecParams&, int32_t* idx_ou
         const hipError_t err = launch_colsum(s, st);
         if (err != hipSuccess) return err;
     }
-    static const bool no_idx = std::getenv("RISVEC_NO_IDX_SWEEP") != nullptr;     // A/B switch: always the generic sweep
-    if (s.control_bit == 3 && reuse_idx && s.theta_idx && (!no_idx || !write_theta)) {
+    if (s.control_bit == 3 && reuse_idx && s.theta_idx) {
         const unsigned gp = (unsigned)((s.n_envs + kWave / 2 - 1) / (kWave / 2));
         const int rs = (reuse_s && s.s_sum) ? 1 : 0;
         const bool pad = s.n_ris % kSweepBlk != 0;

@@ -86,16 +86,7 @@ hipError_t launch_sarl_step(const RisVecState& s, const RisVecSarlParams& p, con
         const hipError_t err = launch_sarl_pipe(s, p, a, st);
         if (err != hipErrorNotSupported) return err;
     }
-    switch (pow2_ceil(s.n_veh)) {
-        case 1: return launch_sarl_vp<1>(s, p, a, st);
-        case 2: return launch_sarl_vp<2>(s, p, a, st);
-        case 4: return launch_sarl_vp<4>(s, p, a, st);
-        case 8: return launch_sarl_vp<8>(s, p, a, st);
-        case 16: return launch_sarl_vp<16>(s, p, a, st);
-        case 32: return launch_sarl_vp<32>(s, p, a, st);
-        case 64: return launch_sarl_vp<64>(s, p, a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return with_vp(s.n_veh, [&](auto vp) { return launch_sarl_vp<vp>(s, p, a, st); });
 }
 
 }  // namespace risvec

@@ -19,7 +19,7 @@
 //     round-trip through HBM before use.
 #include <type_traits>
 
-#include "risvec_step.hpp"
+#include "risvec_pipe.hpp"
 
 namespace risvec {
 
@@ -210,34 +210,26 @@ k_step_steer(Dims d, RisVecParams P, StepArgs A, const double* __restrict__ z_r)
     step_core<VP>(d, P, A, e_mine, v_mine, active, g, in);
 }
 
+// LDS of the steering kernel per wavefront: its EPW envs' rows of M + 1 w values, float64 ("wide") when 4 wavefronts' worth
+// still leave room for several blocks per CU, float32 for long rows
+static size_t steer_lds_per_wave(int vp, int n_ris, bool* wide) {
+    const size_t row = (size_t)(kWave / vp) * (n_ris + 1);
+    *wide = row * sizeof(double2) * (kBlock / kWave) <= 40 * 1024;     // >= 4 blocks per CU either way
+    return row * (*wide ? sizeof(double2) : sizeof(float2));
+}
+
 template <int VP>
 static hipError_t launch_steer_vp(const RisVecState& s, const RisVecParams& p, const StepArgs& a, hipStream_t st) {
     constexpr int EPW = kWave / VP;
-    const size_t row = (size_t)EPW * (s.n_ris + 1);
-    const bool wide = row * sizeof(double2) * (kBlock / kWave) <= 40 * 1024;     // >= 4 blocks per CU either way
-    const size_t per_wave = row * (wide ? sizeof(double2) : sizeof(float2));
-    int waves = (int)((64 * 1024) / per_wave);             // as many wavefronts per block as 64 KB of LDS hold
-    if (waves < 1) return hipErrorNotSupported;            // theta rows do not fit: use the streaming kernel
+    bool wide;
+    const size_t per_wave = steer_lds_per_wave(VP, s.n_ris, &wide);
+    int waves = (int)((64 * 1024) / per_wave);             // as many wavefronts per block as 64 KB of LDS hold (>= 1: plan_step)
     if (waves > kBlock / kWave) waves = kBlock / kWave;
     const long long n_waves = ((long long)s.n_envs + EPW - 1) / EPW;
     const dim3 grid((unsigned)((n_waves + waves - 1) / waves)), block(waves * kWave);
     if (wide) hipLaunchKernelGGL((k_step_steer<VP, true>), grid, block, per_wave * waves, st, dims_of(s), p, a, s.z_r);
     else hipLaunchKernelGGL((k_step_steer<VP, false>), grid, block, per_wave * waves, st, dims_of(s), p, a, s.z_r);
-    note_kernel("k_step_steer<%d,%s>", VP, wide ? "wide" : "narrow");
     return hipGetLastError();
-}
-
-hipError_t launch_step_steer(const RisVecState& s, const RisVecParams& p, const StepArgs& a, hipStream_t st) {
-    switch (pow2_ceil(s.n_veh)) {
-        case 1: return launch_steer_vp<1>(s, p, a, st);
-        case 2: return launch_steer_vp<2>(s, p, a, st);
-        case 4: return launch_steer_vp<4>(s, p, a, st);
-        case 8: return launch_steer_vp<8>(s, p, a, st);
-        case 16: return launch_steer_vp<16>(s, p, a, st);
-        case 32: return launch_steer_vp<32>(s, p, a, st);
-        case 64: return launch_steer_vp<64>(s, p, a, st);
-        default: return hipErrorInvalidValue;
-    }
 }
 
 template <int G>
@@ -267,34 +259,28 @@ hipError_t launch_gain(const RisVecState& s, const RisVecParams&, hipStream_t st
     }
 }
 
+// the generic members: cached k_step<VP> (RING: with the transition store), fused k_step_fused<VP,G,VEC>, k_step_steer<VP>
 template <int VP>
-static hipError_t launch_step_vp(const RisVecState& s, const RisVecParams& p, const StepArgs& a,
-                                 bool fused, hipStream_t st) {
+static hipError_t launch_step_vp(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
+                                 hipStream_t st) {
     const long long threads = (long long)s.n_envs * VP;
     const unsigned grid = (unsigned)((threads + kBlock - 1) / kBlock);
     const Dims d = dims_of(s);
-    if (!fused) {
-        if (a.ring.state_memory) {
-            if constexpr (VP == 4 || VP == 8 || VP == 16) {
+    if (pl.family == StepPlan::STEER) return launch_steer_vp<VP>(s, p, a, st);
+    if (pl.family == StepPlan::CACHED) {
+        if constexpr (VP == 4 || VP == 8 || VP == 16) {
+            if (pl.ring) {
                 hipLaunchKernelGGL((k_step<VP, true>), dim3(grid), dim3(kBlock), 0, st, d, p, a);
-                note_kernel("k_step<%d,RING>", VP);
                 return hipGetLastError();
-            } else {
-                return hipErrorNotSupported;
             }
         }
         hipLaunchKernelGGL((k_step<VP>), dim3(grid), dim3(kBlock), 0, st, d, p, a);
-        note_kernel("k_step<%d>", VP);
         return hipGetLastError();
     }
-    if (a.ring.state_memory) return hipErrorNotSupported;      // fused + ring: the software pipeline's ring form only
-    const bool even = (s.n_ris & 1) == 0;
-    const int g = pick_group(s.n_ris, even ? 2 : 1, VP);
 #define RISVEC_FUSED(GG)                                                                          \
-    if (g == GG) {                                                                                \
-        if (even) hipLaunchKernelGGL((k_step_fused<VP, GG, 2>), dim3(grid), dim3(kBlock), 0, st, d, p, a); \
-        else hipLaunchKernelGGL((k_step_fused<VP, GG, 1>), dim3(grid), dim3(kBlock), 0, st, d, p, a);      \
-        note_kernel("k_step_fused<%d,%d,%d>", VP, GG, even ? 2 : 1);                                \
+    if (pl.g == GG) {                                                                             \
+        if (pl.vec == 2) hipLaunchKernelGGL((k_step_fused<VP, GG, 2>), dim3(grid), dim3(kBlock), 0, st, d, p, a); \
+        else hipLaunchKernelGGL((k_step_fused<VP, GG, 1>), dim3(grid), dim3(kBlock), 0, st, d, p, a);             \
         return hipGetLastError();                                                                 \
     }
     if constexpr (kWave / VP <= 8) { RISVEC_FUSED(8) }
@@ -305,45 +291,231 @@ static hipError_t launch_step_vp(const RisVecState& s, const RisVecParams& p, co
     return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------------------
+// The selector: which member of the step family a call launches.  Every dispatch rule of the family lives here, in the
+// order it applies (DESIGN.md 3.1 points here).  stream = h_r + theta bytes of one step = E (8VM + 8M); IC = the
+// Infinity Cache; the thresholds are tuning()'s (risvec_pipe.hpp: 256 CUs and 256 MiB on MI355X).
+//
+//   cached (risvec_step)    k_step<VP>, VP = pow2_ceil(V)
+//   cached + ring           k_step<VP,RING>, V in {4, 8, 16}
+//   fused + ring            the compile-time shapes' pipeline k_step_fused_pipe<V,M,D,MarlCore+ring> (NT as in 4.)
+//   fused T-step            the compile-time shapes with V <= 8: k_step_fused_lat<V,M,EPWT,MULTI>
+//   fused, the first that applies:
+//     1. RISVEC_STEP_THETA_BY_INDEX   k_step_fused_lat<..,EMAX,TK> (NT / ALT by stream size as in 3.)
+//     2. RISVEC_STEP_STEER            k_step_steer<VP,wide|narrow> while one wavefront's theta rows fit 64 KB of LDS
+//     3. V in {4, 8, 16}, even M <= 256: the latency-shaped k_step_fused_lat (k_step_lat.hip)
+//          stream > 1.29 IC           EMAX envs per wavefront, NT
+//          IC < stream <= 1.29 IC     EMAX, ALT
+//          otherwise                  EPWT envs per wavefront, while 8x64 and 4x16 have at most 24 wavefronts (of 4
+//                                     envs) per CU and 16x64 at most 8 (16x64: never NT); 8x36, 8x40, 16x256 and the
+//                                     run-time-M members at every size
+//     4. the compile-time shapes      k_step_fused_pipe<V,M,D,MarlCore> (NT beyond 1.055 IC)
+//     5. anything else                k_step_fused<VP,G,VEC>
+//
+// Why (us per step; profiles/):
+//   * beyond 1.29 IC many short wavefronts with every request up front are what the best pure reader looks like: 1-4 %
+//     faster than the pipeline's long-lived wavefronts (r02t_lat_nt_experiment.txt, pipeline / this: 65 536 envs
+//     59.3 / 58.5, 131 072 115.8 / 111.9, 262 144 223.6 / 217.1; with the default cache policy it loses 7-12 % there);
+//   * in (1, 1.29] IC the default policy with the envs walked in alternating directions from step to step is 3-12 %
+//     faster than the hint (r03q_pingpong_band.txt);
+//   * the crossover at 8 x 64 (r02t_lat_vs_pipe.txt, this / pipeline: 8 192 envs 7.3 / 9.4, 12 288 11.5 / 12.5,
+//     20 480 17.9 / 18.7, 24 576 21.2 / 21.1, 32 768 27.5 / 26.9); at 16 x 64 (r02t_lat_v16.txt, pipeline / this:
+//     4 096 envs 8.0 / 7.0, 8 192 14.5 / 14.5, from 16 384 the pipeline wins); M = 36 / 40 at every size
+//     (r02u_lat_vs_pipe_ragged.txt); 16 x 256, one env per wavefront (r02t_lat_v16.txt: 2 048 envs 14.6 -> 13.5,
+//     4 096 25.3 -> 23.4; BASELINE configs[4] with the BCD sweep 251.5 -> 233);
+//   * EPWT = the largest of {4, 2, 1} that keeps >= 8 wavefronts per CU (r02t_lat_epw_sweep.txt), clamped to the
+//     member's [EMIN, EMAX];
+//   * the T-step loop is instruction-issue-bound (~400 dependent-ish vector instructions per step and wavefront whatever
+//     the number of active lanes): EPWT = 64 / V envs per wavefront (at most 8), halved while fewer than 4 wavefronts
+//     per CU.
+// risvec_force_forms() (tests and same-box A/Bs only) overrides the lat / pipeline choice, the envs per wavefront and the
+// cache policies.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct Fixed { int V, M, D, emin, emax; bool tstep; };
+constexpr Fixed kFixed[] = {
+#define RISVEC_X(V_, M_, D_, EMIN, EMAX, T) {V_, M_, D_, EMIN, EMAX, T},
+    RISVEC_FIXED_SHAPES(RISVEC_X)
+#undef RISVEC_X
+};
+struct RuntimeM { int V, G, NIT, emin, emax; };
+constexpr RuntimeM kRuntimeM[] = {
+#define RISVEC_X(V_, G_, NIT_, EMIN, EMAX) {V_, G_, NIT_, EMIN, EMAX},
+    RISVEC_RUNTIME_M_SHAPES(RISVEC_X)
+#undef RISVEC_X
+};
+
+const Fixed* fixed_shape(int V, int M) {
+    for (const Fixed& f : kFixed)
+        if (f.V == V && f.M == M) return &f;
+    return nullptr;
+}
+
+long long stream_bytes(const RisVecState& s) { return (long long)s.n_envs * (8LL * s.n_veh * s.n_ris + 8LL * s.n_ris); }
+
+// M = 0: the run-time-M member (G, NIT) at s.n_ris
+StepPlan lat_plan(const RisVecState& s, int M, int G, int NIT, int epwt, int pol, bool tk, bool multi) {
+    StepPlan pl;
+    pl.family = StepPlan::LAT;
+    pl.V = s.n_veh; pl.M = M; pl.G = G; pl.NIT = NIT;
+    pl.epwt = epwt; pl.pol = pol; pl.tk = tk; pl.multi = multi;
+    const char* ps = pol == 1 ? ",NT" : (pol == 2 ? ",ALT" : "");
+    if (M)
+        snprintf(pl.name, sizeof(pl.name), "k_step_fused_lat<%d,%d,%d%s%s%s>", pl.V, M, epwt, multi ? ",MULTI" : "", ps,
+                 tk ? ",TK" : "");
+    else
+        snprintf(pl.name, sizeof(pl.name), "k_step_fused_lat<%d,M=%d(G=%d,NIT=%d),%d%s%s%s>", pl.V, s.n_ris, G, NIT, epwt,
+                 multi ? ",MULTI" : "", ps, tk ? ",TK" : "");
+    return pl;
+}
+
+// rules 1 and 3
+StepPlan plan_lat(const RisVecState& s, bool tk) {
+    const int V = s.n_veh, M = s.n_ris;
+    if (!step_fused_lat_covers(V, M)) return {};
+    const RisVecForce& F = forced_forms();
+    const Tuning& T = tuning();
+    const long long b = stream_bytes(s);
+    const bool off = F.lat == RISVEC_FORCE_OFF;
+    bool nt = !off && forced_or(F.lat_nt, b > T.lat_nt_from);
+    const bool walk = forced_or(F.lat_alt, b > T.ic_bytes && b <= T.lat_nt_from);
+    const bool band = !off && !nt && walk && b > T.ic_bytes;
+    // wavefronts (of 4 envs) per CU up to which this kernel beats the shape's software pipeline
+    auto below = [&](int waves_per_cu) {
+        return F.lat == RISVEC_FORCE_ON || (!off && s.n_envs <= (long long)waves_per_cu * T.cus * 4);
+    };
+    const Fixed* f = fixed_shape(V, M);
+    if ((V == 8 && M == 64) || (V == 4 && M == 16)) {
+        if (!nt && !band && !tk && !below(24)) return {};
+    } else if (V == 16 && M == 64) {
+        if (!below(8) && !tk) return {};
+        nt = false;
+    } else if (f && off && !tk) {
+        return {};
+    }
+    int emin, emax, G = 0, NIT = 0;
+    if (f) {
+        emin = f->emin; emax = f->emax;
+    } else {
+        const RuntimeM* r = nullptr;
+        for (const RuntimeM& x : kRuntimeM)
+            if (x.V == V && x.G == fused_g(V, M) && x.NIT == fused_nit(V, M)) r = &x;
+        if (!r) return {};
+        emin = r->emin; emax = r->emax; G = r->G; NIT = r->NIT;
+    }
+    const int pol = nt ? 1 : (walk ? 2 : 0);
+    if (tk || pol) return lat_plan(s, f ? M : 0, G, NIT, emax, pol, tk, false);     // these forms: the EMAX member only
+    int epwt = F.lat_epw;
+    if (!epwt) {
+        epwt = 4;
+        while (epwt > 1 && (long long)s.n_envs / epwt < 8LL * T.cus) epwt >>= 1;
+    }
+    epwt = epwt < emin ? emin : (epwt > emax ? emax : epwt);
+    return lat_plan(s, f ? M : 0, G, NIT, epwt, 0, false, false);
+}
+
+StepPlan plan_tstep(const RisVecState& s) {
+    const Fixed* f = fixed_shape(s.n_veh, s.n_ris);
+    if (!f || !f->tstep) return {};
+    int epwt = kWave / pow2_ceil(s.n_veh);
+    if (epwt > 8) epwt = 8;
+    while (epwt > 1 && (long long)s.n_envs / epwt < 4LL * tuning().cus) epwt >>= 1;
+    return lat_plan(s, f->M, 0, 0, epwt, 0, false, true);
+}
+
+StepPlan plan_steer(const RisVecState& s) {
+    StepPlan pl;
+    bool wide;
+    if ((64 * 1024) / steer_lds_per_wave(pow2_ceil(s.n_veh), s.n_ris, &wide) < 1) return pl;   // rows too long for LDS
+    pl.family = StepPlan::STEER;
+    pl.vp = pow2_ceil(s.n_veh);
+    snprintf(pl.name, sizeof(pl.name), "k_step_steer<%d,%s>", pl.vp, wide ? "wide" : "narrow");
+    return pl;
+}
+
+StepPlan plan_generic(const RisVecState& s, bool fused, bool ring) {
+    StepPlan pl;
+    pl.vp = pow2_ceil(s.n_veh);
+    if (fused) {
+        pl.family = StepPlan::FUSED;
+        pl.vec = (s.n_ris & 1) ? 1 : 2;
+        pl.g = pick_group(s.n_ris, pl.vec, pl.vp);
+        snprintf(pl.name, sizeof(pl.name), "k_step_fused<%d,%d,%d>", pl.vp, pl.g, pl.vec);
+    } else if (!ring || pl.vp == 4 || pl.vp == 8 || pl.vp == 16) {
+        pl.family = StepPlan::CACHED;
+        pl.ring = ring;
+        snprintf(pl.name, sizeof(pl.name), ring ? "k_step<%d,RING>" : "k_step<%d>", pl.vp);
+    }
+    return pl;
+}
+
+}  // namespace
+
+StepPlan plan_pipe(const RisVecState& s, const char* core) {
+    StepPlan pl;
+    const Fixed* f = fixed_shape(s.n_veh, s.n_ris);
+    if (!f) return pl;
+    pl.family = StepPlan::PIPE;
+    pl.V = f->V; pl.M = f->M;
+    pl.pol = forced_or(forced_forms().pipe_nt, stream_bytes(s) > tuning().pipe_nt_from) ? 1 : 0;
+    snprintf(pl.name, sizeof(pl.name), "k_step_fused_pipe<%d,%d,%d,%s%s>", f->V, f->M, f->D, core, pl.pol ? ",NT" : "");
+    return pl;
+}
+
+StepPlan plan_step(const RisVecState& s, uint32_t flags, int form) {
+    switch (form) {
+        case RISVEC_FORM_CACHED: return plan_generic(s, false, false);
+        case RISVEC_FORM_CACHED_RING: return plan_generic(s, false, true);
+        case RISVEC_FORM_FUSED_RING: {
+            StepPlan pl = plan_pipe(s, MarlRingCore<8>::name());    // (one name for every V)
+            pl.ring = true;
+            return pl;
+        }
+        case RISVEC_FORM_FUSED_MULTI: return plan_tstep(s);
+        case RISVEC_FORM_FUSED: break;
+        default: return {};
+    }
+    if (flags & RISVEC_STEP_THETA_BY_INDEX) return plan_lat(s, true);
+    if (flags & RISVEC_STEP_STEER) {
+        const StepPlan pl = plan_steer(s);
+        if (pl.family != StepPlan::NONE) return pl;
+    }
+    const StepPlan lat = plan_lat(s, false);
+    if (lat.family != StepPlan::NONE) return lat;
+    const StepPlan pipe = plan_pipe(s, MarlCore::name());
+    if (pipe.family != StepPlan::NONE) return pipe;
+    return plan_generic(s, true, false);
+}
+
 hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float* action,
                        const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals,
                        uint64_t seed, uint32_t counter, uint32_t flags, bool fused, hipStream_t st, const StepRing* ring) {
+    const int form = fused ? (ring ? RISVEC_FORM_FUSED_RING : RISVEC_FORM_FUSED) : (ring ? RISVEC_FORM_CACHED_RING : RISVEC_FORM_CACHED);
+    const StepPlan pl = plan_step(s, flags, form);
+    if (pl.family == StepPlan::NONE) return hipErrorNotSupported;
     StepArgs a = make_step_args(s, action, partner, n_groups, arrivals, seed, counter,
                                 flags & ~(uint32_t)(RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX));
-    if (ring) {
-        // the transition store rides in the step kernel: the software pipeline's ring form (compile-time shapes) or the
-        // cached-gain k_step<VP, RING>; no other member of the family carries it
-        a.ring = *ring;
-        if (fused) return launch_step_fused_pipe_ring(s, p, a, st);
-    }
-    if (fused && (flags & RISVEC_STEP_THETA_BY_INDEX)) {
-        // theta is kept by index: only the latency-shaped family has that form (the API checked the shape)
+    if (ring) a.ring = *ring;                                  // the transition store rides in the step kernel
+    if (pl.tk) {                                               // theta is kept by index (the API checked the shape)
         a.theta_k = s.theta_idx;
         a.theta_k_stride = theta_idx_stride(s.n_ris);
-        return launch_step_fused_lat(s, p, a, st);
     }
-    if (fused && (flags & RISVEC_STEP_STEER)) {
-        const hipError_t err = launch_step_steer(s, p, a, st);
-        if (err != hipErrorNotSupported) return err;       // theta rows too long for LDS: stream h_r as usual
-    }
-    if (fused) {                                                // small batch: latency-shaped single-group kernel
-        const hipError_t err = launch_step_fused_lat(s, p, a, st);
-        if (err != hipErrorNotSupported) return err;
-    }
-    if (fused) {
-        const hipError_t err = launch_step_fused_pipe(s, p, a, st);
-        if (err != hipErrorNotSupported) return err;
-    }
-    switch (pow2_ceil(s.n_veh)) {
-        case 1: return launch_step_vp<1>(s, p, a, fused, st);
-        case 2: return launch_step_vp<2>(s, p, a, fused, st);
-        case 4: return launch_step_vp<4>(s, p, a, fused, st);
-        case 8: return launch_step_vp<8>(s, p, a, fused, st);
-        case 16: return launch_step_vp<16>(s, p, a, fused, st);
-        case 32: return launch_step_vp<32>(s, p, a, fused, st);
-        case 64: return launch_step_vp<64>(s, p, a, fused, st);
-        default: return hipErrorInvalidValue;
-    }
+    hipError_t err;
+    if (pl.family == StepPlan::LAT) err = launch_step_fused_lat(s, p, a, pl, 1, RisVecTraj{}, st);
+    else if (pl.family == StepPlan::PIPE) err = launch_step_fused_pipe(s, p, a, pl, st);
+    else err = with_vp(s.n_veh, [&](auto vp) { return launch_step_vp<vp>(s, p, a, pl, st); });
+    note_kernel("%s", pl.name);
+    return err;
+}
+
+hipError_t launch_step_fused_multi(const RisVecState& s, const RisVecParams& p, const StepArgs& a, int n_steps,
+                                   const RisVecTraj* traj, hipStream_t st) {
+    const StepPlan pl = plan_step(s, 0, RISVEC_FORM_FUSED_MULTI);
+    if (pl.family == StepPlan::NONE) return hipErrorNotSupported;
+    const hipError_t err = launch_step_fused_lat(s, p, a, pl, n_steps, traj ? *traj : RisVecTraj{}, st);
+    note_kernel("%s", pl.name);
+    return err;
 }
 
 template <int VP>
@@ -359,16 +531,7 @@ static hipError_t launch_step_multi_vp(const RisVecState& s, const RisVecParams&
 hipError_t launch_step_multi(const RisVecState& s, const RisVecParams& p, const StepArgs& a, int n_steps,
                              const RisVecTraj* traj, hipStream_t st) {
     const RisVecTraj tj = traj ? *traj : RisVecTraj{nullptr, nullptr, nullptr};
-    switch (pow2_ceil(s.n_veh)) {
-        case 1: return launch_step_multi_vp<1>(s, p, a, n_steps, tj, st);
-        case 2: return launch_step_multi_vp<2>(s, p, a, n_steps, tj, st);
-        case 4: return launch_step_multi_vp<4>(s, p, a, n_steps, tj, st);
-        case 8: return launch_step_multi_vp<8>(s, p, a, n_steps, tj, st);
-        case 16: return launch_step_multi_vp<16>(s, p, a, n_steps, tj, st);
-        case 32: return launch_step_multi_vp<32>(s, p, a, n_steps, tj, st);
-        case 64: return launch_step_multi_vp<64>(s, p, a, n_steps, tj, st);
-        default: return hipErrorInvalidValue;
-    }
+    return with_vp(s.n_veh, [&](auto vp) { return launch_step_multi_vp<vp>(s, p, a, n_steps, tj, st); });
 }
 
 template <int VP>
@@ -385,16 +548,7 @@ static hipError_t launch_rate_vp(const RisVecState& s, const RisVecParams& p, co
 hipError_t launch_data_rate(const RisVecState& s, const RisVecParams& p, const float* p_off,
                             const int32_t* partner, const int32_t* n_groups, float* rate_out,
                             hipStream_t st) {
-    switch (pow2_ceil(s.n_veh)) {
-        case 1: return launch_rate_vp<1>(s, p, p_off, partner, n_groups, rate_out, st);
-        case 2: return launch_rate_vp<2>(s, p, p_off, partner, n_groups, rate_out, st);
-        case 4: return launch_rate_vp<4>(s, p, p_off, partner, n_groups, rate_out, st);
-        case 8: return launch_rate_vp<8>(s, p, p_off, partner, n_groups, rate_out, st);
-        case 16: return launch_rate_vp<16>(s, p, p_off, partner, n_groups, rate_out, st);
-        case 32: return launch_rate_vp<32>(s, p, p_off, partner, n_groups, rate_out, st);
-        case 64: return launch_rate_vp<64>(s, p, p_off, partner, n_groups, rate_out, st);
-        default: return hipErrorInvalidValue;
-    }
+    return with_vp(s.n_veh, [&](auto vp) { return launch_rate_vp<vp>(s, p, p_off, partner, n_groups, rate_out, st); });
 }
 
 }  // namespace risvec

@@ -34,7 +34,7 @@
 
 namespace risvec {
 
-// NT: h_r / theta loads carry the non-temporal hint (streams beyond the Infinity Cache: see launch_step_fused_lat)
+// NT: h_r / theta loads carry the non-temporal hint (streams beyond the Infinity Cache: see plan_step, k_step.hip)
 template <bool NT>
 __device__ __forceinline__ float4 lat_ld(const float4* p) {
     if constexpr (NT) {
@@ -71,7 +71,7 @@ k_step_fused_lat(Dims d, RisVecParams P, StepArgs A, int n_steps, RisVecTraj TJ)
         // in ALTERNATING directions from step to step (A.ping: the launcher's step parity): the lines the previous
         // launch touched last -- the ones still cached -- are the first this launch asks for, where a same-direction
         // walk of an LRU-like cache hits nothing.  Which wavefront serves which env changes nothing in the results.
-        // Measured (tools/gpu_pingpong.sh, profiles/r03q_pingpong_band.txt, r03p_*; h_r + theta per step at E x 8 x 64, us
+        // Measured (profiles/r03q_pingpong_band.txt, r03p_pingpong_default_policy.txt; h_r + theta per step at E x 8 x 64, us
         // per step round-2 dispatch / this): 283 MB 49.9 / 48.6, 302 MB 59.1 / 53.7, 340 MB 70.2 / 62.0, 377 MB 70.1 / 70.6,
         // 528 MB 100.2 / 101.5, 1.2 GB 226 / 236.
         const int n_waves = (d.E + EPWT - 1) / EPWT;
@@ -249,31 +249,6 @@ k_step_fused_lat(Dims d, RisVecParams P, StepArgs A, int n_steps, RisVecTraj TJ)
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-static int env_int(const char* name, int dflt) {
-    const char* s = std::getenv(name);
-    return s ? std::atoi(s) : dflt;
-}
-
-// envs per wavefront: as many (<= 4) as keep >= 8 wavefronts per CU in flight (measured: EXPERIMENTS.md, rounds 1-2 section 6)
-static int lat_epwt(int n_envs) {
-    static const int forced = env_int("RISVEC_LAT_EPW", -1);   // A/B switch; 0 disables the latency-shaped single-step kernel
-    if (forced >= 0) return forced;
-    const long long want = 8LL * num_cus();
-    int e = 4;
-    while (e > 1 && (long long)n_envs / e < want) e >>= 1;
-    return e;
-}
-
-static long long stream_bytes_of(const RisVecState& s) { return (long long)s.n_envs * (8LL * s.n_veh * s.n_ris + 8LL * s.n_ris); }
-
-// RISVEC_LAT_PINGPONG: 0 never / 1 always (tests) / 2 (default) when the stream lies in (1, 1.29] x the Infinity Cache
-static bool alternate_walk(const RisVecState& s) {
-    static const int mode = env_int("RISVEC_LAT_PINGPONG", 2);
-    if (mode != 2) return mode == 1;
-    const long long b = stream_bytes_of(s);
-    return b > tuning().ic_bytes && b <= tuning().lat_nt_from;
-}
-
 // POL: 0 default cache policy, 1 non-temporal loads, 2 default policy + alternating walk (single-step kernels only)
 template <class S, int EPWT, bool MULTI, int POL, bool TK>
 static hipError_t launch_one(const RisVecState& s, const RisVecParams& p, const StepArgs& a0, int n_steps,
@@ -285,63 +260,43 @@ static hipError_t launch_one(const RisVecState& s, const RisVecParams& p, const 
     a.ping = POL == 2 ? (int)(a.counter & 1u) : 0;
     hipLaunchKernelGGL((k_step_fused_lat<S, EPWT, MULTI, false, POL, TK>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a,
                        n_steps, tj);
-    const char* pol = POL == 1 ? ",NT" : (POL == 2 ? ",ALT" : "");
-    if (S::FIXED)
-        note_kernel("k_step_fused_lat<%d,%d,%d%s%s%s>", S::V, S::MC, EPWT, MULTI ? ",MULTI" : "", pol, TK ? ",TK" : "");
-    else
-        note_kernel("k_step_fused_lat<%d,M=%d(G=%d,NIT=%d),%d%s%s%s>", S::V, s.n_ris, S::G, S::NIT, EPWT, MULTI ? ",MULTI" : "",
-                    pol, TK ? ",TK" : "");
     return hipGetLastError();
 }
 
-// One shape class, single step: EPWT in [EMIN, EMAX] by batch size (default cache policy), EMAX with the non-temporal
-// hint beyond the Infinity Cache; HAS_TK: the theta-by-index forms of the EMAX kernel exist.
-template <class S, int EMIN, int EMAX, bool HAS_TK>
-static hipError_t launch_single(const RisVecState& s, const RisVecParams& p, const StepArgs& a, int epwt, bool nt,
-                                hipStream_t st) {
-    const RisVecTraj none{};
-    const bool alt = !nt && alternate_walk(s);                 // (1, 1.29] x the Infinity Cache: the EMAX kernel, walked both ways
-    if (a.theta_k) {
-        if constexpr (HAS_TK) {
-            if (nt) return launch_one<S, EMAX, false, 1, true>(s, p, a, 1, none, st);
-            if (alt) return launch_one<S, EMAX, false, 2, true>(s, p, a, 1, none, st);
-            return launch_one<S, EMAX, false, 0, true>(s, p, a, 1, none, st);
-        } else {
-            return hipErrorNotSupported;
+// One member: EMIN ... EMAX envs per wavefront with the default cache policy; the EMAX kernel also non-temporal, walked
+// both ways and by index (TK); T: the T-step launch with 1 / 2 / 4 (and, where a wavefront holds them, 8) envs per
+// wavefront.
+template <class S, int EMIN, int EMAX, bool T>
+static hipError_t launch_member(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl, int n_steps,
+                                const RisVecTraj& tj, hipStream_t st) {
+    if (pl.multi) {
+        if constexpr (T) {
+            switch (pl.epwt) {
+                case 1: return launch_one<S, 1, true, 0, false>(s, p, a, n_steps, tj, st);
+                case 2: return launch_one<S, 2, true, 0, false>(s, p, a, n_steps, tj, st);
+                case 4: return launch_one<S, 4, true, 0, false>(s, p, a, n_steps, tj, st);
+                case 8:
+                    if constexpr (S::EPW >= 8) return launch_one<S, 8, true, 0, false>(s, p, a, n_steps, tj, st);
+                    break;
+            }
         }
+        return hipErrorNotSupported;
     }
-    if (nt) return launch_one<S, EMAX, false, 1, false>(s, p, a, 1, none, st);
-    if (alt) return launch_one<S, EMAX, false, 2, false>(s, p, a, 1, none, st);
-    if (epwt > EMAX) epwt = EMAX;
-    if (epwt < EMIN) epwt = EMIN;
-    if constexpr (EMIN <= 1 && EMAX >= 1) { if (epwt == 1) return launch_one<S, 1, false, 0, false>(s, p, a, 1, none, st); }
-    if constexpr (EMIN <= 2 && EMAX >= 2) { if (epwt == 2) return launch_one<S, 2, false, 0, false>(s, p, a, 1, none, st); }
-    if constexpr (EMIN <= 4 && EMAX >= 4) { if (epwt >= 3) return launch_one<S, 4, false, 0, false>(s, p, a, 1, none, st); }
+    if (pl.epwt == EMAX) {
+        switch (pl.pol * 2 + (pl.tk ? 1 : 0)) {
+            case 0: return launch_one<S, EMAX, false, 0, false>(s, p, a, 1, tj, st);
+            case 1: return launch_one<S, EMAX, false, 0, true>(s, p, a, 1, tj, st);
+            case 2: return launch_one<S, EMAX, false, 1, false>(s, p, a, 1, tj, st);
+            case 3: return launch_one<S, EMAX, false, 1, true>(s, p, a, 1, tj, st);
+            case 4: return launch_one<S, EMAX, false, 2, false>(s, p, a, 1, tj, st);
+            case 5: return launch_one<S, EMAX, false, 2, true>(s, p, a, 1, tj, st);
+        }
+        return hipErrorNotSupported;
+    }
+    if constexpr (EMIN <= 1 && EMAX > 1) { if (pl.epwt == 1) return launch_one<S, 1, false, 0, false>(s, p, a, 1, tj, st); }
+    if constexpr (EMIN <= 2 && EMAX > 2) { if (pl.epwt == 2) return launch_one<S, 2, false, 0, false>(s, p, a, 1, tj, st); }
     return hipErrorNotSupported;
 }
-
-template <class S>
-static hipError_t launch_multi_shape(const RisVecState& s, const RisVecParams& p, const StepArgs& a, int n_steps,
-                                     const RisVecTraj& tj, int epwt, hipStream_t st) {
-    switch (epwt) {
-        case 1: return launch_one<S, 1, true, 0, false>(s, p, a, n_steps, tj, st);
-        case 2: return launch_one<S, 2, true, 0, false>(s, p, a, n_steps, tj, st);
-        case 4: return launch_one<S, 4, true, 0, false>(s, p, a, n_steps, tj, st);
-        case 8:
-            // all 64 lanes stepping: only worth its registers where the step loop dominates (the T-step launch)
-            if constexpr (S::EPW >= 8) return launch_one<S, 8, true, 0, false>(s, p, a, n_steps, tj, st);
-            return hipErrorNotSupported;
-        default: return hipErrorNotSupported;
-    }
-}
-
-// compile-time shapes (the BASELINE configurations and the reference driver's default M = 40)
-using S8x64 = FusedShape<8, 32, 1, 64>;
-using S8x36 = FusedShape<8, 32, 1, 36>;
-using S8x40 = FusedShape<8, 32, 1, 40>;
-using S4x16 = FusedShape<4, 16, 1, 16>;
-using S16x64 = FusedShape<16, 32, 1, 64>;
-using S16x256 = FusedShape<16, 64, 2, 256>;
 
 // Shapes with a member of this family: V in {4, 8, 16}, even M <= 256.
 bool step_fused_lat_covers(int V, int M) {
@@ -352,99 +307,29 @@ bool step_fused_lat_covers(int V, int M) {
 // shape this family covers (the EMAX-envs-per-wavefront member of each shape has a TK form)
 bool theta_by_index_supported(int V, int M) { return step_fused_lat_covers(V, M); }
 
-// Single step.  Which kernel, in order:
-//   1. h_r + theta of one step beyond lat_nt_from (1.29 x the Infinity Cache): EMAX envs per wavefront, non-temporal
-//      loads -- many short hardware-dispatched wavefronts with every request up front are what the best pure reader
-//      looks like, and they beat the pipeline's 2 048 long-lived wavefronts by 1-4 % there (tools/gpu_latnt.sh,
-//      profiles/r02t_lat_nt_experiment.txt, us per step pipeline / this: 65 536 envs 59.3 / 58.5, 131 072 115.8 / 111.9,
-//      262 144 223.6 / 217.1; with the default cache policy it loses 7-12 % at those sizes).
-//   2. shapes with a software pipeline (8 x 64, 4 x 16: up to 24 wavefronts per CU of 4 envs = 24 576 envs on 256 CUs;
-//      16 x 64: 8 per CU = 8 192 envs): this kernel while the batch is that small (tools/gpu_crossover.sh,
-//      profiles/r02t_lat_vs_pipe.txt, us per step this / pipeline at 8 x 64: 8 192 envs 7.3 / 9.4, 12 288 11.5 / 12.5,
-//      20 480 17.9 / 18.7, 24 576 21.2 / 21.1, 32 768 27.5 / 26.9), the pipeline above.
-//   3. everything else (M = 36 / 40: profiles/r02u_lat_vs_pipe_ragged.txt; 16 x 256; the run-time-M members): here at
-//      every size.
-// RISVEC_LAT_MAX_ENVS (0: never this kernel where a pipeline exists), RISVEC_LAT_EPW, RISVEC_LAT_NT (0 never / 1 always /
-// 2 by size) and RISVEC_LAT_NT_MB override for A/Bs and the bit-identity tests.
-hipError_t launch_step_fused_lat(const RisVecState& s, const RisVecParams& p, const StepArgs& a, hipStream_t st) {
-    const int V = s.n_veh, M = s.n_ris;
-    if (!step_fused_lat_covers(V, M)) return hipErrorNotSupported;
-    static const long long forced_limit = [] { const char* e = std::getenv("RISVEC_LAT_MAX_ENVS"); return e ? std::atoll(e) : -1LL; }();
-    static const int nt_mode = env_int("RISVEC_LAT_NT", 2);
-    const long long stream_bytes = stream_bytes_of(s);
-    const bool off = forced_limit == 0;                        // the family is switched off where a pipeline exists
-    const bool nt = !off && (nt_mode == 1 || (nt_mode == 2 && stream_bytes > tuning().lat_nt_from));
-    // between the cache size and lat_nt_from: this kernel with the default policy and the alternating walk (launch_one)
-    const bool band = !off && !nt && nt_mode != 1 && alternate_walk(s) && stream_bytes > tuning().ic_bytes;
-    const int epwt = lat_epwt(s.n_envs);
-    if (epwt <= 0) return hipErrorNotSupported;
-    // wavefronts per CU (of 4 envs) up to which this kernel beats the shape's software pipeline
-    auto below = [&](int waves_per_cu) {
-        const long long limit = forced_limit >= 0 ? forced_limit : (long long)waves_per_cu * num_cus() * 4;
-        return (long long)s.n_envs <= limit;
-    };
+// The member plan_step() chose (k_step.hip holds the rules).
+hipError_t launch_step_fused_lat(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
+                                 int n_steps, const RisVecTraj& tj, hipStream_t st) {
 #ifdef RISVEC_DIAG
     // diagnostic library only (make diag -> librisvec_diag.so, tools/lat_stamps.py): the s_memrealtime build of the kernel
     if (const char* dbg = std::getenv("RISVEC_LAT_STAMPS_PTR")) {
-        if (V == 8 && M == 36 && epwt == 2) {
-            const RisVecTraj tj{reinterpret_cast<float*>(std::strtoull(dbg, nullptr, 0)), nullptr, nullptr};
+        if (pl.V == 8 && pl.M == 36 && pl.epwt == 2 && !pl.multi && !pl.tk && pl.pol == 0) {
+            const RisVecTraj dtj{reinterpret_cast<float*>(std::strtoull(dbg, nullptr, 0)), nullptr, nullptr};
             const long long waves = ((long long)s.n_envs + 1) / 2;
-            hipLaunchKernelGGL((k_step_fused_lat<S8x36, 2, false, true>), dim3((unsigned)((waves + 3) / 4)), dim3(kBlock), 0, st,
-                               dims_of(s), p, a, 1, tj);
+            hipLaunchKernelGGL((k_step_fused_lat<FusedShape<8, 32, 1, 36>, 2, false, true>), dim3((unsigned)((waves + 3) / 4)),
+                               dim3(kBlock), 0, st, dims_of(s), p, a, 1, dtj);
             return hipGetLastError();
         }
     }
 #endif
-    if (V == 8 && M == 64) {
-        if (!nt && !band && !a.theta_k && !below(24)) return hipErrorNotSupported;
-        return launch_single<S8x64, 1, 4, true>(s, p, a, epwt, nt, st);
-    }
-    if (V == 4 && M == 16) {
-        if (!nt && !band && !a.theta_k && !below(24)) return hipErrorNotSupported;
-        return launch_single<S4x16, 1, 4, true>(s, p, a, epwt, nt, st);
-    }
-    if (V == 16 && M == 64) {
-        // (tools/gpu_v16.sh, us per step pipeline / this: 4 096 envs 8.0 / 7.0, 8 192 14.5 / 14.5, from 16 384 the pipeline wins)
-        if (!below(8) && !a.theta_k) return hipErrorNotSupported;
-        return launch_single<S16x64, 1, 4, true>(s, p, a, epwt, false, st);
-    }
-    if (off && ((V == 8 && (M == 36 || M == 40)) || (V == 16 && M == 256)))
-        return hipErrorNotSupported;                           // bit-identity tests: force the pipeline where one exists
-    if (V == 8 && M == 36) return launch_single<S8x36, 1, 4, true>(s, p, a, epwt, nt, st);
-    if (V == 8 && M == 40) return launch_single<S8x40, 1, 4, true>(s, p, a, epwt, nt, st);
-    // 16 x 256 (one env = 34 loads per lane): one env per wavefront at every size (tools/gpu_v16.sh: 2 048 envs
-    // 14.6 -> 13.5 us, 4 096 25.3 -> 23.4; BASELINE configs[4] with the BCD sweep 251.5 -> 233 us per step)
-    if (V == 16 && M == 256) return launch_single<S16x256, 1, 1, true>(s, p, a, 1, nt, st);
-    // run-time M: the member with this (V, G, NIT)
-    const int g = fused_g(V, M), nit = fused_nit(V, M);
-#define RISVEC_RT(VV, GG, NN, EMIN, EMAX) \
-    if (V == VV && g == GG && nit == NN) return launch_single<FusedShape<VV, GG, NN, 0>, EMIN, EMAX, true>(s, p, a, epwt, nt, st);
-    RISVEC_RT(8, 8, 1, 2, 4) RISVEC_RT(8, 16, 1, 2, 4) RISVEC_RT(8, 32, 1, 2, 4) RISVEC_RT(8, 64, 1, 2, 4) RISVEC_RT(8, 64, 2, 2, 4)
-    RISVEC_RT(4, 16, 1, 2, 4) RISVEC_RT(4, 32, 1, 2, 4) RISVEC_RT(4, 64, 1, 2, 4) RISVEC_RT(4, 64, 2, 2, 4)
-    RISVEC_RT(16, 8, 1, 2, 4) RISVEC_RT(16, 16, 1, 2, 4) RISVEC_RT(16, 32, 1, 2, 4) RISVEC_RT(16, 64, 1, 1, 2) RISVEC_RT(16, 64, 2, 1, 1)
-#undef RISVEC_RT
-    return hipErrorNotSupported;
-}
-
-// n_steps consecutive fused steps in one launch; hipErrorNotSupported when the shape has no
-// compile-time kernel (the caller then issues one fused launch + one launch of k_step_multi).
-hipError_t launch_step_fused_multi(const RisVecState& s, const RisVecParams& p, const StepArgs& a, int n_steps,
-                                   const RisVecTraj* traj, hipStream_t st) {
-    // The step loop is instruction-issue-bound (one step() is ~400 dependent-ish vector instructions per
-    // wavefront whatever the number of active lanes), so a wavefront should carry as many envs as it has
-    // lanes for -- as long as every SIMD still gets a wavefront (4 per CU).
-    int epw = kWave / pow2_ceil(s.n_veh);
-    if (epw > 8) epw = 8;
-    static const int forced = env_int("RISVEC_MULTI_EPW", 0);
-    int epwt = epw;
-    while (epwt > 1 && (long long)s.n_envs / epwt < 4LL * num_cus()) epwt >>= 1;
-    if (forced > 0) epwt = forced;
-    const RisVecTraj tj = traj ? *traj : RisVecTraj{nullptr, nullptr, nullptr};
-    const int V = s.n_veh, M = s.n_ris;
-    if (V == 8 && M == 64) return launch_multi_shape<S8x64>(s, p, a, n_steps, tj, epwt, st);
-    if (V == 8 && M == 36) return launch_multi_shape<S8x36>(s, p, a, n_steps, tj, epwt, st);
-    if (V == 8 && M == 40) return launch_multi_shape<S8x40>(s, p, a, n_steps, tj, epwt, st);
-    if (V == 4 && M == 16) return launch_multi_shape<S4x16>(s, p, a, n_steps, tj, epwt, st);
+#define RISVEC_X(VV, MM, DD, EMIN, EMAX, T) \
+    if (pl.V == VV && pl.M == MM) return launch_member<FusedShape<VV, fused_g(VV, MM), fused_nit(VV, MM), MM>, EMIN, EMAX, T>(s, p, a, pl, n_steps, tj, st);
+    RISVEC_FIXED_SHAPES(RISVEC_X)
+#undef RISVEC_X
+#define RISVEC_X(VV, GG, NN, EMIN, EMAX) \
+    if (pl.M == 0 && pl.V == VV && pl.G == GG && pl.NIT == NN) return launch_member<FusedShape<VV, GG, NN, 0>, EMIN, EMAX, false>(s, p, a, pl, n_steps, tj, st);
+    RISVEC_RUNTIME_M_SHAPES(RISVEC_X)
+#undef RISVEC_X
     return hipErrorNotSupported;
 }
 

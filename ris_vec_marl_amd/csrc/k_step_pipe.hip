@@ -14,8 +14,6 @@
 //
 // Reference: Simulation-MARL-BCD/Environment.py update_channel_gains ENV:263-273 + step
 // ENV:547-731 (see risvec_step.hpp).
-#include <cstdlib>
-
 #include "risvec_pipe.hpp"
 #include "risvec_sarl.hpp"
 
@@ -257,99 +255,73 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
 //   D=4: 28.0 (4)  27.7 (8)   28.0 (12)      D=8: 29.7 (4)  29.7 (8)   29.6 (12)
 // i.e. a shallow ring with more resident waves wins: deeper rings cost registers (fewer
 // waves) and buy nothing once ~8 waves/CU already keep >= 16 KiB in flight each.
-static int pipe_waves_per_cu() {
-    static int v = [] {
-        const char* s = std::getenv("RISVEC_PIPE_WAVES_PER_CU");
-        const int x = s ? std::atoi(s) : 0;
-        return (x >= 1 && x <= 32) ? x : 8;
-    }();
-    return v;
-}
+constexpr int kPipeWavesPerCu = 8;
 
-static int env_int(const char* name, int dflt) {
-    const char* s = std::getenv(name);
-    return s ? std::atoi(s) : dflt;
-}
-
+// NT: non-temporal h_r / theta loads, once the per-step stream no longer fits the 256 MiB Infinity Cache (plan_pipe).
+// Measured (same box, E x 8 x 64, us per step default / nt): 40 960 envs (188 MiB) 32.9 / 39.0, 57 344 (263 MiB)
+// 46.0 / 53.8, 65 536 (288 MiB) 59.4 / 57.8, 262 144 (1.15 GiB) 245-250 / 221-223; 32 768 x 16 x 256 (1.1 GiB) with the
+// BCD sweep 276-284 / 240-252 -- below the cache size the re-read of last step's lines is worth more than the hint,
+// above it the hint is worth 10 %.
 template <int V, int M, int D, class Core>
-static hipError_t launch_pipe(const RisVecState& s, const typename Core::Params& p, const typename Core::Args& a,
+static hipError_t launch_pipe(const RisVecState& s, const typename Core::Params& p, const typename Core::Args& a, bool nt,
                               hipStream_t st) {
     using S = PipeShape<V, M>;
     const int n_groups = (s.n_envs + S::EPW - 1) / S::EPW;
     const int wpb = kBlock / kWave;
-    long long want_waves = (long long)num_cus() * pipe_waves_per_cu();
+    long long want_waves = (long long)num_cus() * kPipeWavesPerCu;
     if (want_waves > n_groups) want_waves = n_groups;
     // balance: every wave gets the same number of groups (the last one possibly fewer)
     const long long per_wave = (n_groups + want_waves - 1) / want_waves;
     want_waves = (n_groups + per_wave - 1) / per_wave;
     const unsigned grid = (unsigned)((want_waves + wpb - 1) / wpb);
-    // Non-temporal h_r / theta loads once the per-step stream no longer fits the 256 MiB Infinity Cache.  Measured
-    // (same box, E x 8 x 64, us per step default / nt): 40 960 envs (188 MiB) 32.9 / 39.0, 57 344 (263 MiB) 46.0 / 53.8,
-    // 65 536 (288 MiB) 59.4 / 57.8, 262 144 (1.15 GiB) 245-250 / 221-223; 32 768 x 16 x 256 (1.1 GiB) with the BCD sweep
-    // 276-284 / 240-252 -- below the cache size the re-read of last step's lines is worth more than the hint, above it
-    // the hint is worth 10 %.  RISVEC_PIPE_NT = 0 / 1 force it off / on; RISVEC_PIPE_CHUNKED (1: contiguous group range
-    // per wavefront, 2: per workgroup) is an experiment that lost at every size but one (214 vs 222 us at 262 144 envs).
-    static const int chunked = env_int("RISVEC_PIPE_CHUNKED", 0);
-    static const int nt_mode = env_int("RISVEC_PIPE_NT", 2);              // 0 never, 1 always, 2 by stream size
-    const long long stream_bytes = (long long)s.n_envs * (8LL * V * M + 8LL * M);
-    const bool nt = nt_mode == 1 || (nt_mode == 2 && stream_bytes > tuning().pipe_nt_from);    // 1.055 x the Infinity Cache
-    const int pw = chunked == 1 ? (int)per_wave : (chunked == 2 ? -(int)per_wave : 0);
-    if (nt) hipLaunchKernelGGL((k_step_fused_pipe<V, M, D, Core, true>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, pw);
-    else hipLaunchKernelGGL((k_step_fused_pipe<V, M, D, Core, false>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, pw);
-    note_kernel("k_step_fused_pipe<%d,%d,%d,%s%s>", V, M, D, Core::name(), nt ? ",NT" : "");
+    if (nt) hipLaunchKernelGGL((k_step_fused_pipe<V, M, D, Core, true>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, 0);
+    else hipLaunchKernelGGL((k_step_fused_pipe<V, M, D, Core, false>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, 0);
     return hipGetLastError();
 }
 
-static bool pipe_disabled() {
-    static const bool off = std::getenv("RISVEC_NO_PIPE") != nullptr;    // A/B switch for experiments
-    return off;
-}
-
-// compile-time shapes shared by the three cores
+// Cores::at<V>: the core of that shape
 template <class Core>
-static hipError_t dispatch_pipe(const RisVecState& s, const typename Core::Params& p, const typename Core::Args& a,
-                                hipStream_t st) {
-    if (pipe_disabled()) return hipErrorNotSupported;
-    const int V = s.n_veh, M = s.n_ris;
-    if (V == 8 && M == 64) return launch_pipe<8, 64, 2, Core>(s, p, a, st);
-    if (V == 8 && M == 36) return launch_pipe<8, 36, 2, Core>(s, p, a, st);
-    if (V == 8 && M == 40) return launch_pipe<8, 40, 2, Core>(s, p, a, st);
-    if (V == 4 && M == 16) return launch_pipe<4, 16, 4, Core>(s, p, a, st);
-    if (V == 16 && M == 64) return launch_pipe<16, 64, 2, Core>(s, p, a, st);
-    if (V == 16 && M == 256) return launch_pipe<16, 256, 2, Core>(s, p, a, st);
+struct AnyV {
+    template <int>
+    using at = Core;
+};
+struct RingCores {
+    template <int V>
+    using at = MarlRingCore<V>;
+};
+
+// the compile-time shape of the plan (RISVEC_FIXED_SHAPES: one table for every core)
+template <class Cores, class P, class A>
+static hipError_t launch_pipe_shape(const RisVecState& s, const P& p, const A& a, const StepPlan& pl, hipStream_t st) {
+#define RISVEC_X(VV, MM, DD, EMIN, EMAX, T) \
+    if (pl.V == VV && pl.M == MM) return launch_pipe<VV, MM, DD, typename Cores::template at<VV>>(s, p, a, pl.pol == 1, st);
+    RISVEC_FIXED_SHAPES(RISVEC_X)
+#undef RISVEC_X
     return hipErrorNotSupported;
 }
 
-hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, const StepArgs& a,
+hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
                                   hipStream_t st) {
-    if (!pipe_disabled() && s.n_veh == 8 && s.n_ris == 64) {             // ring-depth experiment knob
-        static const int depth = [] { const char* e = std::getenv("RISVEC_PIPE_DEPTH"); return e ? std::atoi(e) : 2; }();
-        if (depth == 1) return launch_pipe<8, 64, 1, MarlCore>(s, p, a, st);
-        if (depth == 4) return launch_pipe<8, 64, 4, MarlCore>(s, p, a, st);
-        if (depth == 8) return launch_pipe<8, 64, 8, MarlCore>(s, p, a, st);
-    }
-    return dispatch_pipe<MarlCore>(s, p, a, st);
+    if (pl.ring) return launch_pipe_shape<RingCores>(s, p, a, pl, st);
+    return launch_pipe_shape<AnyV<MarlCore>>(s, p, a, pl, st);
 }
 
-hipError_t launch_step_fused_pipe_ring(const RisVecState& s, const RisVecParams& p, const StepArgs& a, hipStream_t st) {
-    if (pipe_disabled()) return hipErrorNotSupported;
-    const int V = s.n_veh, M = s.n_ris;
-    if (V == 8 && M == 64) return launch_pipe<8, 64, 2, MarlRingCore<8>>(s, p, a, st);
-    if (V == 8 && M == 36) return launch_pipe<8, 36, 2, MarlRingCore<8>>(s, p, a, st);
-    if (V == 8 && M == 40) return launch_pipe<8, 40, 2, MarlRingCore<8>>(s, p, a, st);
-    if (V == 4 && M == 16) return launch_pipe<4, 16, 4, MarlRingCore<4>>(s, p, a, st);
-    if (V == 16 && M == 64) return launch_pipe<16, 64, 2, MarlRingCore<16>>(s, p, a, st);
-    if (V == 16 && M == 256) return launch_pipe<16, 256, 2, MarlRingCore<16>>(s, p, a, st);
-    return hipErrorNotSupported;
+template <class Core, class P, class A>
+static hipError_t launch_core(const RisVecState& s, const P& p, const A& a, hipStream_t st) {
+    const StepPlan pl = plan_pipe(s, Core::name());
+    if (pl.family == StepPlan::NONE) return hipErrorNotSupported;
+    const hipError_t err = launch_pipe_shape<AnyV<Core>>(s, p, a, pl, st);
+    note_kernel("%s", pl.name);
+    return err;
 }
 
 hipError_t launch_sarl_pipe(const RisVecState& s, const RisVecSarlParams& p, const SarlArgs& a, hipStream_t st) {
-    return dispatch_pipe<SarlCore>(s, p, a, st);
+    return launch_core<SarlCore>(s, p, a, st);
 }
 
 hipError_t launch_gain_pipe(const RisVecState& s, hipStream_t st) {
     const GainArgs a{s.pl, s.h_r, s.theta, s.b, s.h_d, s.gain};
-    return dispatch_pipe<GainCore>(s, 0, a, st);
+    return launch_core<GainCore>(s, 0, a, st);
 }
 
 }  // namespace risvec

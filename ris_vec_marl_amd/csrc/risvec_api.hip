@@ -13,6 +13,7 @@ namespace {
 
 thread_local char g_err[512] = "";
 thread_local char g_kernel[160] = "";
+RisVecForce g_force{};                  // risvec_force_forms(): all RISVEC_BY_RULE
 
 int fail(int code, const char* fmt, ...) {
     va_list ap;
@@ -98,6 +99,8 @@ void note_kernel(const char* fmt, ...) {
     vsnprintf(g_kernel, sizeof(g_kernel), fmt, ap);
     va_end(ap);
 }
+
+const RisVecForce& forced_forms() { return g_force; }
 }  // namespace risvec
 
 extern "C" {
@@ -107,6 +110,42 @@ uint32_t risvec_abi_version(void) { return RISVEC_ABI_VERSION; }
 const char* risvec_last_kernel(void) { return g_kernel; }
 
 const char* risvec_last_error(void) { return g_err; }
+
+const char* risvec_step_kernel(const RisVecState* s, uint32_t flags, int32_t form) {
+    const char* fn = "risvec_step_kernel";
+    thread_local char name[sizeof(risvec::StepPlan::name)];
+    if (check_common(fn, s, nullptr)) return nullptr;
+    if (form < RISVEC_FORM_CACHED || form > RISVEC_FORM_FUSED_MULTI) {
+        fail(RISVEC_ERR_ARG, "%s: form=%d is not a RISVEC_FORM_*", fn, form);
+        return nullptr;
+    }
+    const risvec::StepPlan pl = risvec::plan_step(*s, flags, form);
+    if (pl.family == risvec::StepPlan::NONE) {
+        fail(RISVEC_ERR_UNSUPPORTED, "%s: form %d has no kernel at n_veh=%d, n_ris=%d (flags 0x%x)", fn, form, s->n_veh, s->n_ris,
+             flags);
+        return nullptr;
+    }
+    std::memcpy(name, pl.name, sizeof(name));
+    return name;
+}
+
+int risvec_force_forms(const RisVecForce* f) {
+    const char* fn = "risvec_force_forms";
+    if (!f) {
+        g_force = RisVecForce{};
+        return RISVEC_OK;
+    }
+    if (f->abi_version != RISVEC_ABI_VERSION || f->struct_bytes != sizeof(RisVecForce))
+        return fail(RISVEC_ERR_ARG, "%s: RisVecForce ABI mismatch (version %u/%u, bytes %u/%zu)", fn, f->abi_version,
+                    (unsigned)RISVEC_ABI_VERSION, f->struct_bytes, sizeof(RisVecForce));
+    for (int32_t v : {f->lat, f->lat_nt, f->lat_alt, f->pipe_nt, f->colsum_nt})
+        if (v != RISVEC_BY_RULE && v != RISVEC_FORCE_OFF && v != RISVEC_FORCE_ON)
+            return fail(RISVEC_ERR_ARG, "%s: %d is not RISVEC_BY_RULE / RISVEC_FORCE_OFF / RISVEC_FORCE_ON", fn, v);
+    if (f->lat_epw != 0 && f->lat_epw != 1 && f->lat_epw != 2 && f->lat_epw != 4)
+        return fail(RISVEC_ERR_ARG, "%s: lat_epw=%d is not 0 (by rule), 1, 2 or 4", fn, f->lat_epw);
+    g_force = *f;
+    return RISVEC_OK;
+}
 
 void risvec_default_params(RisVecParams* p) {
     if (!p) return;

@@ -95,6 +95,12 @@ hipError_t launch_theta_from_index(const RisVecState& s, hipStream_t st);
 // risvec_last_kernel(): the launchers of the step path and the BCD sweep name the kernel they dispatched (per thread)
 void note_kernel(const char* fmt, ...);
 
+// risvec_force_forms(): the test / A/B override of the dispatch rules.  Read by the step selector (plan_step) and
+// launch_colsum only.
+const RisVecForce& forced_forms();
+// `rule` unless the override field forces the form on or off
+inline bool forced_or(int32_t field, bool rule) { return field == RISVEC_BY_RULE ? rule : field == RISVEC_FORCE_ON; }
+
 inline Dims dims_of(const RisVecState& s) {
     return Dims{s.n_envs, s.n_veh, s.n_ris, s.control_bit, (long long)s.env_offset};
 }

@@ -3,7 +3,6 @@
 // image of a load unit, the transposing butterfly and the MARL core.
 #pragma once
 
-#include <cstdlib>
 #include <cstring>
 
 #include "risvec_step.hpp"
@@ -98,7 +97,7 @@ struct MarlCore {
 //                  crossover 294 ... 368 MiB); between ic_bytes and this it reads with the default policy and walks the
 //                  envs in alternating directions from step to step (round 3: 3-12 % faster than the hint in that band,
 //                  equal at 1.4 x, 4 % slower at 5 x)
-// The RISVEC_* environment switches remain as overrides for same-box A/Bs and the bit-identity tests.
+// How they are used: plan_step() in k_step.hip.
 // ---------------------------------------------------------------------------
 struct Tuning {
     int cus;
@@ -118,12 +117,8 @@ inline const Tuning& tuning() {
                 else if (std::strncmp(a, "gfx94", 5) == 0 || std::strncmp(a, "gfx95", 5) == 0) r.ic_bytes = 256LL << 20;
             }
         }
-        auto mb = [](const char* name, long long dflt) {
-            const char* e = std::getenv(name);
-            return e ? (std::atoll(e) << 20) : dflt;
-        };
-        r.pipe_nt_from = mb("RISVEC_PIPE_NT_MB", r.ic_bytes + r.ic_bytes * 55 / 1000);
-        r.lat_nt_from = mb("RISVEC_LAT_NT_MB", r.ic_bytes + r.ic_bytes * 29 / 100);
+        r.pipe_nt_from = r.ic_bytes + r.ic_bytes * 55 / 1000;
+        r.lat_nt_from = r.ic_bytes + r.ic_bytes * 29 / 100;
         r.colsum_nt_from = r.ic_bytes + r.ic_bytes * 55 / 1000;
         return r;
     }();

@@ -274,6 +274,21 @@ __device__ __forceinline__ float2 cascade_row(const float* __restrict__ hrow,
 
 // lanes per (env, vehicle) row: enough to cover M/VEC elements in one pass when
 // possible, but never more vehicles per pass than an env has (keeps lanes busy).
+// f(std::integral_constant<int, VP>{}) with VP = pow2_ceil(V): the per-VP instantiations of a launcher
+template <class F>
+hipError_t with_vp(int V, F&& f) {
+    switch (pow2_ceil(V)) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+
 inline int pick_group(int M, int vec, int VP) {
     int g = pow2_ceil((M + vec - 1) / vec);
     if (g > kWave) g = kWave;
@@ -729,16 +744,49 @@ inline StepArgs make_step_args(const RisVecState& s, const float* action, const 
     return a;
 }
 
-// specialised software-pipelined fused kernels (k_step_pipe.hip); returns
-// hipErrorNotSupported when the shape has no specialisation.
-hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, const StepArgs& a,
-                                  hipStream_t st);
-hipError_t launch_gain_pipe(const RisVecState& s, hipStream_t st);
-hipError_t launch_step_fused_pipe_ring(const RisVecState& s, const RisVecParams& p, const StepArgs& a, hipStream_t st);
-// latency-shaped single-group kernels for small batches and the multi-step launch (k_step_lat.hip)
-hipError_t launch_step_fused_lat(const RisVecState& s, const RisVecParams& p, const StepArgs& a, hipStream_t st);
+// The compile-time shapes (the BASELINE configurations and the reference driver's default M = 40).  Each has a software
+// pipeline (k_step_pipe.hip, ring depth D) for all four cores -- MarlCore, MarlRingCore<V>, SarlCore, GainCore -- and a
+// latency-shaped member (k_step_lat.hip) with EMIN ... EMAX envs per wavefront; T: it has a T-step member as well.
+//   X(V, M, D, EMIN, EMAX, T)
+#define RISVEC_FIXED_SHAPES(X) \
+    X(8, 64, 2, 1, 4, true) X(8, 36, 2, 1, 4, true) X(8, 40, 2, 1, 4, true) X(4, 16, 4, 1, 4, true) \
+    X(16, 64, 2, 1, 4, false) X(16, 256, 2, 1, 1, false)
+// The run-time-M members of the latency-shaped family: any even M with fused_g(V, M) == G and fused_nit(V, M) == NIT.
+//   X(V, G, NIT, EMIN, EMAX)
+#define RISVEC_RUNTIME_M_SHAPES(X) \
+    X(8, 8, 1, 2, 4) X(8, 16, 1, 2, 4) X(8, 32, 1, 2, 4) X(8, 64, 1, 2, 4) X(8, 64, 2, 2, 4) \
+    X(4, 16, 1, 2, 4) X(4, 32, 1, 2, 4) X(4, 64, 1, 2, 4) X(4, 64, 2, 2, 4) \
+    X(16, 8, 1, 2, 4) X(16, 16, 1, 2, 4) X(16, 32, 1, 2, 4) X(16, 64, 1, 1, 2) X(16, 64, 2, 1, 1)
+
+// What one step call launches: the decision of the selector plan_step() (k_step.hip), which holds every dispatch rule
+// of the step family.  The launchers only instantiate and launch what it names; `name` is what risvec_last_kernel()
+// and risvec_step_kernel() report.
+struct StepPlan {
+    enum Family { NONE, CACHED, FUSED, STEER, LAT, PIPE };
+    Family family = NONE;
+    int vp = 0;                        // CACHED / FUSED / STEER: lanes per env (pow2_ceil(V))
+    int g = 0, vec = 0;                // FUSED: lanes per h_r row, complex elements per load
+    int V = 0, M = 0, G = 0, NIT = 0;  // LAT: the FusedShape member (M = 0: run-time M); PIPE: the shape
+    int epwt = 0;                      // LAT: envs per wavefront
+    int pol = 0;                       // LAT / PIPE: 0 default cache policy, 1 non-temporal, 2 alternating walk (LAT)
+    bool ring = false, tk = false, multi = false;
+    char name[96] = "";
+};
+// form: RISVEC_FORM_*; flags: the RISVEC_STEP_* flags of the call (only STEER and THETA_BY_INDEX select)
+StepPlan plan_step(const RisVecState& s, uint32_t flags, int form);
+// the software pipeline of this shape for a core named `core` (NONE when the shape has none)
+StepPlan plan_pipe(const RisVecState& s, const char* core);
 bool step_fused_lat_covers(int V, int M);
 bool theta_by_index_supported(int V, int M);
+
+// the launchers of the plan's family: k_step_pipe.hip, k_step_lat.hip
+hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
+                                  hipStream_t st);
+hipError_t launch_gain_pipe(const RisVecState& s, hipStream_t st);
+hipError_t launch_step_fused_lat(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
+                                 int n_steps, const RisVecTraj& tj, hipStream_t st);
+// the T-step launch of the compile-time shapes; hipErrorNotSupported when the shape has none (the caller then issues
+// one fused launch + one launch of k_step_multi)
 hipError_t launch_step_fused_multi(const RisVecState& s, const RisVecParams& p, const StepArgs& a, int n_steps,
                                    const RisVecTraj* traj, hipStream_t st);
 // n_steps consecutive steps on the CACHED gains in one launch, any shape (k_step.hip)

@@ -299,3 +299,138 @@ def test_policy_split16_abi_without_a_gpu():
     assert lib.risvec_policy_layer1_split16(4, 8, 5, 510, None, None, None, None, None, None, None) == N.ERR_SHAPE
     assert lib.risvec_policy_layer1_split16(4, 8, 9, 512, None, None, None, None, None, None, None) == N.ERR_SHAPE
     assert lib.risvec_policy_layer1_split16(4, 8, 5, 512, None, None, None, None, None, None, None) == N.ERR_ARG
+
+
+def _kernel(E, V, M, flags=0, form=N.FORM_FUSED):
+    s = N.RisVecState(abi_version=N.ABI_VERSION, struct_bytes=C.sizeof(N.RisVecState), n_envs=E, n_veh=V, n_ris=M,
+                      control_bit=3)
+    return N.step_kernel(s, flags, form)
+
+
+# DESIGN.md 3.1 / plan_step(): each rule on both sides of its boundary.  Without a device tuning() takes the MI355X
+# values: 256 CUs, a 256 MiB Infinity Cache (IC).  Stream = h_r + theta per step = E (8VM + 8M): 4 608 B per env at 8 x 64.
+DISPATCH_TABLE = [
+    # lat vs pipe at 8 x 64 and 4 x 16: 24 wavefronts of 4 envs per CU; 16 x 64: 8
+    ((24576, 8, 64), "k_step_fused_lat<8,64,4>"),
+    ((24577, 8, 64), "k_step_fused_pipe<8,64,2,MarlCore>"),
+    ((24576, 4, 16), "k_step_fused_lat<4,16,4>"),
+    ((24577, 4, 16), "k_step_fused_pipe<4,16,4,MarlCore>"),
+    ((8192, 16, 64), "k_step_fused_lat<16,64,4>"),
+    ((8193, 16, 64), "k_step_fused_pipe<16,64,2,MarlCore>"),
+    ((100000, 8, 36), "k_step_fused_lat<8,36,4>"),                # M = 36 / 40: the latency-shaped kernel at every size
+    ((90000, 8, 40), "k_step_fused_lat<8,40,4>"),
+    # envs per wavefront: the largest of {4, 2, 1} with >= 8 wavefronts per CU (2 048 on 256 CUs)
+    ((8192, 8, 36), "k_step_fused_lat<8,36,4>"),
+    ((8191, 8, 36), "k_step_fused_lat<8,36,2>"),
+    ((4096, 8, 36), "k_step_fused_lat<8,36,2>"),
+    ((4095, 8, 36), "k_step_fused_lat<8,36,1>"),
+    ((4095, 16, 256), "k_step_fused_lat<16,256,1>"),              # 16 x 256: one env per wavefront at every size
+    ((4096, 16, 256), "k_step_fused_lat<16,256,1>"),
+    # the stream against the IC (58 254 envs = 268 434 432 B <= 256 MiB < 58 255 envs) and 1.29 IC (75 147 / 75 148 envs)
+    ((58254, 8, 64), "k_step_fused_pipe<8,64,2,MarlCore>"),
+    ((58255, 8, 64), "k_step_fused_lat<8,64,4,ALT>"),
+    ((75147, 8, 64), "k_step_fused_lat<8,64,4,ALT>"),
+    ((75148, 8, 64), "k_step_fused_lat<8,64,4,NT>"),
+    ((262144, 8, 64), "k_step_fused_lat<8,64,4,NT>"),
+    ((58254, 8, 36), "k_step_fused_lat<8,36,4>"),                 # 8 x 36: 2 592 B per env -> IC at 103 563 / 103 564 envs
+    ((103563, 8, 36), "k_step_fused_lat<8,36,4>"),
+    ((103564, 8, 36), "k_step_fused_lat<8,36,4,ALT>"),
+    ((133598, 8, 36), "k_step_fused_lat<8,36,4,NT>"),
+    ((32768, 16, 256), "k_step_fused_lat<16,256,1,NT>"),
+    # run-time M: the (V, G, NIT) member, envs per wavefront clamped to it
+    ((32768, 8, 20), "k_step_fused_lat<8,M=20(G=16,NIT=1),4>"),
+    ((3001, 8, 20), "k_step_fused_lat<8,M=20(G=16,NIT=1),2>"),
+    ((2049, 8, 256), "k_step_fused_lat<8,M=256(G=64,NIT=2),2>"),
+    ((16384, 16, 120), "k_step_fused_lat<16,M=120(G=64,NIT=1),2>"),
+    ((515, 16, 120), "k_step_fused_lat<16,M=120(G=64,NIT=1),1>"),
+    ((1027, 16, 200), "k_step_fused_lat<16,M=200(G=64,NIT=2),1>"),
+    ((4100, 4, 100), "k_step_fused_lat<4,M=100(G=64,NIT=1),2>"),
+    ((16384, 8, 120), "k_step_fused_lat<8,M=120(G=64,NIT=1),4>"),
+    ((32768, 8, 120), "k_step_fused_lat<8,M=120(G=64,NIT=1),4,ALT>"),
+    # outside the family: the generic kernel
+    ((130, 5, 21), "k_step_fused<8,32,1>"),
+    ((1000, 8, 63), "k_step_fused<8,64,1>"),
+    ((1000, 8, 300), "k_step_fused<8,64,2>"),
+    ((1000, 32, 64), "k_step_fused<32,32,2>"),
+    ((1000, 2, 64), "k_step_fused<2,32,2>"),
+]
+
+
+@pytest.mark.parametrize("shape,name", DISPATCH_TABLE)
+def test_dispatch_table(shape, name):
+    assert _kernel(*shape) == name
+
+
+def test_dispatch_table_forms_flags_and_overrides():
+    K = _kernel
+    # theta by index: the EMAX member's TK form, NT / ALT by stream size as the plain step
+    assert K(300, 8, 64, N.STEP_THETA_BY_INDEX) == "k_step_fused_lat<8,64,4,TK>"
+    assert K(32768, 8, 64, N.STEP_THETA_BY_INDEX) == "k_step_fused_lat<8,64,4,TK>"
+    assert K(58255, 8, 64, N.STEP_THETA_BY_INDEX) == "k_step_fused_lat<8,64,4,ALT,TK>"
+    assert K(75148, 8, 64, N.STEP_THETA_BY_INDEX) == "k_step_fused_lat<8,64,4,NT,TK>"
+    assert K(32768, 16, 256, N.STEP_THETA_BY_INDEX) == "k_step_fused_lat<16,256,1,NT,TK>"
+    assert K(257, 8, 100, N.STEP_THETA_BY_INDEX) == "k_step_fused_lat<8,M=100(G=64,NIT=1),4,TK>"
+    assert K(40000, 16, 64, N.STEP_THETA_BY_INDEX) == "k_step_fused_lat<16,64,4,TK>"         # 16 x 64 never NT
+    assert K(300, 8, 300, N.STEP_THETA_BY_INDEX) is None
+    # steering: while one wavefront's theta rows fit 64 KB of LDS (8 envs x (M + 1) at V = 8: float64 up to M = 79)
+    assert K(1000, 8, 79, N.STEP_STEER) == "k_step_steer<8,wide>"
+    assert K(1000, 8, 80, N.STEP_STEER) == "k_step_steer<8,narrow>"
+    assert K(1000, 8, 1023, N.STEP_STEER) == "k_step_steer<8,narrow>"
+    assert K(1000, 8, 1024, N.STEP_STEER) == "k_step_fused<8,64,2>"
+    assert K(32768, 16, 256, N.STEP_STEER) == "k_step_steer<16,narrow>"
+    assert K(1000, 1, 128, N.STEP_STEER) == "k_step_fused<1,64,2>"                          # 64 envs x 129 > 64 KB
+    # cached, ring and T-step forms
+    assert K(32768, 8, 64, form=N.FORM_CACHED) == "k_step<8>"
+    assert K(130, 5, 21, form=N.FORM_CACHED) == "k_step<8>"
+    assert K(1000, 16, 64, form=N.FORM_CACHED_RING) == "k_step<16,RING>"
+    assert K(1000, 5, 21, form=N.FORM_CACHED_RING) == "k_step<8,RING>"
+    assert K(1000, 2, 64, form=N.FORM_CACHED_RING) is None
+    assert K(32768, 8, 64, form=N.FORM_FUSED_RING) == "k_step_fused_pipe<8,64,2,MarlCore+ring>"
+    assert K(1000, 4, 16, form=N.FORM_FUSED_RING) == "k_step_fused_pipe<4,16,4,MarlCore+ring>"
+    assert K(61458, 8, 64, form=N.FORM_FUSED_RING) == "k_step_fused_pipe<8,64,2,MarlCore+ring>"   # 1.055 IC
+    assert K(61459, 8, 64, form=N.FORM_FUSED_RING) == "k_step_fused_pipe<8,64,2,MarlCore+ring,NT>"
+    assert K(1000, 8, 100, form=N.FORM_FUSED_RING) is None
+    assert K(8192, 8, 64, form=N.FORM_FUSED_MULTI) == "k_step_fused_lat<8,64,8,MULTI>"
+    assert K(8191, 8, 64, form=N.FORM_FUSED_MULTI) == "k_step_fused_lat<8,64,4,MULTI>"
+    assert K(4096, 8, 36, form=N.FORM_FUSED_MULTI) == "k_step_fused_lat<8,36,4,MULTI>"
+    assert K(4095, 8, 36, form=N.FORM_FUSED_MULTI) == "k_step_fused_lat<8,36,2,MULTI>"
+    assert K(1024, 8, 40, form=N.FORM_FUSED_MULTI) == "k_step_fused_lat<8,40,1,MULTI>"
+    assert K(8192, 4, 16, form=N.FORM_FUSED_MULTI) == "k_step_fused_lat<4,16,8,MULTI>"
+    assert K(8192, 16, 64, form=N.FORM_FUSED_MULTI) is None
+    assert K(8192, 8, 20, form=N.FORM_FUSED_MULTI) is None
+    # the test / A/B override, and the rules again after it
+    with N.forced(lat=False):
+        assert K(2100, 8, 64) == "k_step_fused_pipe<8,64,2,MarlCore>"
+        assert K(300, 16, 256) == "k_step_fused_pipe<16,256,2,MarlCore>"
+        assert K(262144, 8, 64) == "k_step_fused_pipe<8,64,2,MarlCore,NT>"
+        assert K(1500, 8, 80) == "k_step_fused_lat<8,M=80(G=64,NIT=1),2>"              # no pipeline: stays
+        assert K(300, 8, 64, N.STEP_THETA_BY_INDEX) == "k_step_fused_lat<8,64,4,TK>"
+    with N.forced(lat=True):
+        assert K(32768, 8, 64) == "k_step_fused_lat<8,64,4>"
+    with N.forced(lat=False, pipe_nt=True):
+        assert K(2100, 8, 64) == "k_step_fused_pipe<8,64,2,MarlCore,NT>"
+    with N.forced(pipe_nt=False):
+        assert K(61459, 8, 64, form=N.FORM_FUSED_RING) == "k_step_fused_pipe<8,64,2,MarlCore+ring>"
+    with N.forced(lat_epw=1):
+        assert K(3001, 8, 20) == "k_step_fused_lat<8,M=20(G=16,NIT=1),2>"             # clamped to the member
+        assert K(9000, 8, 40) == "k_step_fused_lat<8,40,1>"
+    with N.forced(lat_epw=4):
+        assert K(3001, 8, 20) == "k_step_fused_lat<8,M=20(G=16,NIT=1),4>"
+    with N.forced(lat_nt=True):
+        assert K(1500, 8, 36) == "k_step_fused_lat<8,36,4,NT>"
+        assert K(2050, 16, 64) == "k_step_fused_lat<16,64,1>"
+    with N.forced(lat_nt=False):
+        assert K(262144, 8, 64) == "k_step_fused_pipe<8,64,2,MarlCore,NT>"             # above the band: the pipeline
+    with N.forced(lat_alt=True):
+        assert K(2100, 8, 64) == "k_step_fused_lat<8,64,4,ALT>"
+    with N.forced(lat_alt=False):
+        assert K(65536, 8, 64) == "k_step_fused_pipe<8,64,2,MarlCore,NT>"
+    assert K(2100, 8, 64) == "k_step_fused_lat<8,64,1>"
+    with pytest.raises(TypeError):
+        with N.forced(lat_ept=1):
+            pass
+    with pytest.raises(ValueError):
+        with N.forced(lat_epw=3):
+            pass
+    assert K(0, 8, 64) is None and b"n_envs" in N.load().risvec_last_error()
+    assert K(100, 8, 64, form=7) is None
