@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RISVEC_ABI_VERSION 16
+#define RISVEC_ABI_VERSION 17
 #define RISVEC_POISSON_TABLE 64   /* entries of the arrival CDF table            */
 #define RISVEC_MAX_LANES 8        /* lane coordinates per direction (ref. has 4) */
 #define RISVEC_MAX_VEH 64         /* V <= 64: one env's vehicles fit a wavefront */
@@ -66,11 +66,13 @@ enum {
                                        updates state.theta_idx and does not write the complex64 state.theta, the fused
                                        step expands the indices through a 9-entry table.  Same outputs bit for bit;
                                        state.theta is stale until risvec_theta_from_index() materialises it. */
-    RISVEC_STEP_STEER = 64          /* risvec_step_fused: h_r is the steering vector risvec_geometry wrote
+    RISVEC_STEP_STEER = 64,         /* risvec_step_fused: h_r is the steering vector risvec_geometry wrote
                                        (phases_R_i[v,m] = z_v^m, z_v = exp(-j pi angle_v), ENV:249-253): do not
                                        read it; evaluate sum_m theta_m b_m z^m by Horner in float64 from
                                        state.z_r (16 bytes per vehicle instead of 8M).  Only valid while h_r is
                                        what the geometry kernel produced -- not for arbitrary channel draws. */
+    RISVEC_STEP_3GPP = 512          /* risvec_step_kernel() only: the 3GPP member of the form (risvec_step_fused_3gpp*
+                                       set it internally; every other step entry point rejects it) */
 };
 
 /* risvec_bcd flags */
@@ -545,6 +547,38 @@ typedef struct RisVecStepRing {
 int risvec_step_ring(const RisVecState *s, const RisVecParams *p, const RisVecStepRing *ring, const float *action,
                      const int32_t *partner, const int32_t *n_groups, const int32_t *arrivals, uint64_t seed,
                      uint32_t counter, uint32_t flags, int32_t fused, risvec_stream_t stream);
+
+/* The fused step under a 3GPP channel model (phy.channel_model 3gpp_umi / 3gpp_uma / other; ENV:8-25, 255-327): ONE
+ * launch does risvec_gain_3gpp(model, draws, seed, chan_counter) and then the step, bit for bit on every state tensor
+ * and output:
+ *   ring == NULL   risvec_gain_3gpp + risvec_step(..., counter, flags)
+ *   ring != NULL   risvec_gain_3gpp + risvec_step_ring(..., fused = 0): the transition store too (needs n_veh in
+ *                  {4, 8, 16} and flags with RISVEC_STEP_POLICY_ACTION | RISVEC_STEP_OBS, as risvec_step_ring)
+ * The gains are computed in registers from state.pos and also written to state.gain.  h_r, theta, b and pl are not
+ * read, so any n_veh <= 64 and any n_ris is served.  model: RISVEC_CH_3GPP_UMI, _UMA or _OTHER (0 dB path loss);
+ * RISVEC_CH_FREE is rejected (the RIS entry points serve it).  fading: injected draws or NULL (Philox, Rayleigh or
+ * Rice per p->rician_k_db, as risvec_gain_3gpp).  flags: RISVEC_STEP_METRICS / _POWER_W / _OBS / _POLICY_ACTION only.
+ * risvec_step_kernel(s, flags | RISVEC_STEP_3GPP, RISVEC_FORM_FUSED / _FUSED_RING / _FUSED_MULTI) names the kernel. */
+typedef struct RisVecFading {
+    const float *u_los;     /* u_los ~ U[0,1), z_shadow ~ N(0,1), small = small-scale power; [E,V] float32 each  */
+    const float *z_shadow;  /* ([T,E,V] for risvec_step_fused_3gpp_multi); all three or none (NULL: Philox)      */
+    const float *small;
+} RisVecFading;
+int risvec_step_fused_3gpp(const RisVecState *s, const RisVecParams *p, int32_t model, const float *action,
+                           const int32_t *partner, const int32_t *n_groups, const int32_t *arrivals,
+                           const RisVecFading *fading, uint64_t seed, uint32_t counter, uint32_t chan_counter,
+                           uint32_t flags, const RisVecStepRing *ring, risvec_stream_t stream);
+
+/* n_steps risvec_step_fused_3gpp calls (ring = NULL) in ONE launch: step t draws its fading with chan_counter + t and
+ * its arrivals with counter + t (or reads slice t of the injected [T,E,V] draws and arrivals), i.e. the counters T
+ * single calls would use.  Positions cannot change inside the launch, so distances, LOS probability and both path
+ * losses are computed once; the LOS decision, shadow and small-scale power are drawn every step.  Records and final
+ * state as risvec_step_fused_multi; state.gain ends up holding the last step's gains. */
+int risvec_step_fused_3gpp_multi(const RisVecState *s, const RisVecParams *p, int32_t model, int32_t n_steps,
+                                 const float *actions, const int32_t *partner, const int32_t *n_groups,
+                                 const int32_t *arrivals, const RisVecFading *fading, uint64_t seed, uint32_t counter,
+                                 uint32_t chan_counter, const RisVecTraj *traj, uint32_t flags, risvec_stream_t stream);
+
 
 /* risvec_replay_store with the action row built in the store kernel from the policy outputs -- power_raw [n,A,2],
  * probs [n,A,A]: per agent [probs_i with zero diagonal | raw power_i], exactly the action_store row of

@@ -9,7 +9,7 @@ import contextlib
 import ctypes as C
 import os
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 POISSON_TABLE = 64
 MAX_LANES = 8
 MAX_VEH = 64
@@ -26,6 +26,7 @@ STEP_REUSE_SSUM = 32
 STEP_STEER = 64
 STEP_REUSE_IDX = 128
 STEP_THETA_BY_INDEX = 256
+STEP_3GPP = 512          # risvec_step_kernel(): the 3GPP member of the form (the 3GPP entry points set it themselves)
 BCD_REUSE_COLSUM, BCD_REUSE_SSUM, BCD_REUSE_IDX, BCD_NO_THETA = 1, 2, 4, 8
 FORM_CACHED, FORM_FUSED, FORM_CACHED_RING, FORM_FUSED_RING, FORM_FUSED_MULTI = range(5)
 BY_RULE, FORCE_OFF, FORCE_ON = range(3)
@@ -81,6 +82,10 @@ class RisVecState(C.Structure):
 
 class RisVecTraj(C.Structure):
     _fields_ = [("reward", _FP), ("obs", _FP), ("metrics", _FP)]
+
+
+class RisVecFading(C.Structure):
+    _fields_ = [("u_los", _FP), ("z_shadow", _FP), ("small", _FP)]
 
 
 class RisVecSarlParams(C.Structure):
@@ -176,6 +181,12 @@ _PROTOS = {
                                         _FP, _FP, C.c_uint64, C.c_uint32, C.c_uint32, _FP]),
     "risvec_step_ring": (C.c_int, [C.POINTER(RisVecState), C.POINTER(RisVecParams), C.POINTER(RisVecStepRing), _FP, _FP, _FP,
                                    _FP, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, _FP]),
+    "risvec_step_fused_3gpp": (C.c_int, [C.POINTER(RisVecState), C.POINTER(RisVecParams), C.c_int32, _FP, _FP, _FP, _FP,
+                                         C.POINTER(RisVecFading), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.POINTER(RisVecStepRing), _FP]),
+    "risvec_step_fused_3gpp_multi": (C.c_int, [C.POINTER(RisVecState), C.POINTER(RisVecParams), C.c_int32, C.c_int32, _FP, _FP,
+                                               _FP, _FP, C.POINTER(RisVecFading), C.c_uint64, C.c_uint32, C.c_uint32,
+                                               C.POINTER(RisVecTraj), C.c_uint32, _FP]),
     "risvec_noma_default_params": (None, [C.POINTER(RisVecNomaParams), C.c_int32]),
     "risvec_noma_begin_episode": (C.c_int, [C.POINTER(RisVecNomaState), _FP]),
     "risvec_noma_mask": (C.c_int, [C.POINTER(RisVecNomaState), _FP, _FP, C.c_double, C.c_int32, _FP]),

@@ -7,14 +7,12 @@
 // add_new_vehicles_by_number ENV:381-410, renew_positions ENV:412-542,
 // compute_parms ENV:241-253, update_channel_gains (3GPP) ENV:275-327,
 // get_next_phase ENV:233-239, Random_phase ENV:203-206.
-#include "risvec_launch.hpp"
+#include "risvec_3gpp.hpp"
 
 namespace risvec {
 
 // ENV:29-42
-__device__ constexpr double kRisX = 220.0, kRisY = 220.0, kRisZ = 25.0;
-__device__ constexpr double kBsX = 0.0, kBsY = 0.0, kBsZ = 25.0;
-__device__ constexpr double kVehZ = 1.5;
+__device__ constexpr double kRisX = 220.0, kRisY = 220.0, kRisZ = 25.0;     // the BS and vehicle heights: risvec_3gpp.hpp
 __device__ constexpr double kRo = 1e-2, kAlpha1 = 2.2, kAlpha2 = 2.5;
 
 // ---------------------------------------------------------------------------
@@ -278,43 +276,13 @@ k_gain_3gpp(Dims d, RisVecParams P, int model, const double* __restrict__ pos,
     const long long idx = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (idx >= (long long)d.E * d.V) return;
     const int e = (int)(idx / d.V), v = (int)(idx % d.V);
-    double u, z, sm;
+    Draws3gpp r;
     if (u_los) {
-        u = u_los[idx]; z = z_shadow[idx]; sm = small_in[idx];
+        r.u = u_los[idx]; r.z = z_shadow[idx]; r.sm = small_in[idx];
     } else {
-        const uint32_t genv = (uint32_t)(d.env_offset + e);
-        const uint4 r = philox4x32_10(genv, (uint32_t)v, counter, kSite3gpp, seed);
-        u = u01(r.x);                                                       // ENV:299
-        const float2 n = normal2(r.y, r.z);
-        z = n.x;                                                            // ENV:10
-        if (P.rician_k_db <= 1e-6f) {
-            sm = -log(((double)(r.w >> 8) + 1.0) * 0x1p-24);               // Exp(1), ENV:17
-        } else {                                                            // ENV:19-25
-            const uint4 r2 = philox4x32_10(genv, (uint32_t)v, counter, kSite3gpp + 0x100u, seed);
-            const float2 n2 = normal2(r2.x, r2.y);
-            const double K = pow(10.0, (double)P.rician_k_db / 10.0);
-            const double s = sqrt(K / (K + 1.0)), sg = 1.0 / sqrt(2.0 * (K + 1.0));
-            const double hr = s + sg * n2.x, hi = sg * n2.y;
-            sm = hr * hr + hi * hi;
-        }
+        r = draws_3gpp(P.rician_k_db, (uint32_t)(d.env_offset + e), (uint32_t)v, counter, seed);
     }
-    const double dx = fabs(pos[idx * 2] - kBsX), dy = fabs(pos[idx * 2 + 1] - kBsY);
-    const double dz = fabs(kBsZ - kVehZ);
-    const double d2d = hypot(dx, dy);
-    const double d3d = sqrt(d2d * d2d + dz * dz);
-    const bool los = u < 0.7 * exp(-d2d / 200.0);                           // ENV:298-299
-    const double fc = (double)P.fc_ghz;
-    const double ld = log10(fmax(d3d, 1.0)), lf = log10(fc);
-    double pl_db = 0.0;                                                     // ENV:315-317
-    if (model == RISVEC_CH_3GPP_UMI)
-        pl_db = los ? 32.4 + 21.0 * lf + 20.0 * ld : 36.7 + 22.7 * lf + 26.0 * ld;       // ENV:281,285
-    else if (model == RISVEC_CH_3GPP_UMA)
-        pl_db = los ? 28.0 + 22.0 * lf + 20.0 * ld
-                    : 13.54 + 39.08 * ld + 20.0 * lf - 0.6 * (double)P.veh_ant_gain;     // ENV:289,293
-    const double large = pow(10.0, -pl_db / 10.0);
-    const double sd = los ? (double)P.shadow_std_los : (double)P.shadow_std_nlos;
-    const double shadow = pow(10.0, (z * sd) / 10.0);                       // ENV:10-11
-    gain[idx] = (float)(large * shadow * sm);                               // ENV:327
+    gain[idx] = gain_3gpp(P, model, pos[idx * 2], pos[idx * 2 + 1], r);      // ENV:327
 }
 
 // ---------------------------------------------------------------------------

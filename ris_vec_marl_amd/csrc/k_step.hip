@@ -296,6 +296,11 @@ static hipError_t launch_step_vp(const RisVecState& s, const RisVecParams& p, co
 // order it applies (DESIGN.md 3.1 points here).  stream = h_r + theta bytes of one step = E (8VM + 8M); IC = the
 // Infinity Cache; the thresholds are tuning()'s (risvec_pipe.hpp: 256 CUs and 256 MiB on MI355X).
 //
+//   RISVEC_STEP_3GPP (risvec_step_fused_3gpp*; reads neither h_r nor theta, so any V <= 64 and any M):
+//     fused                 k_step_3gpp<VP>
+//     fused + ring          k_step_3gpp<VP,RING>, V in {4, 8, 16}
+//     fused T-step          k_step_3gpp<VP,MULTI>
+//     (no cached forms: the cached step does not depend on the channel model)
 //   cached (risvec_step)    k_step<VP>, VP = pow2_ceil(V)
 //   cached + ring           k_step<VP,RING>, V in {4, 8, 16}
 //   fused + ring            the compile-time shapes' pipeline k_step_fused_pipe<V,M,D,MarlCore+ring> (NT as in 4.)
@@ -434,6 +439,20 @@ StepPlan plan_steer(const RisVecState& s) {
     return pl;
 }
 
+// the 3GPP members (k_step_3gpp.hip): one per form, any shape
+StepPlan plan_3gpp(const RisVecState& s, int form) {
+    StepPlan pl;
+    const int V = s.n_veh;
+    if (form == RISVEC_FORM_FUSED_RING && V != 4 && V != 8 && V != 16) return pl;
+    if (form != RISVEC_FORM_FUSED && form != RISVEC_FORM_FUSED_RING && form != RISVEC_FORM_FUSED_MULTI) return pl;
+    pl.family = StepPlan::G3;
+    pl.vp = pow2_ceil(V);
+    pl.ring = form == RISVEC_FORM_FUSED_RING;
+    pl.multi = form == RISVEC_FORM_FUSED_MULTI;
+    snprintf(pl.name, sizeof(pl.name), "k_step_3gpp<%d%s>", pl.vp, pl.ring ? ",RING" : (pl.multi ? ",MULTI" : ""));
+    return pl;
+}
+
 StepPlan plan_generic(const RisVecState& s, bool fused, bool ring) {
     StepPlan pl;
     pl.vp = pow2_ceil(s.n_veh);
@@ -464,6 +483,7 @@ StepPlan plan_pipe(const RisVecState& s, const char* core) {
 }
 
 StepPlan plan_step(const RisVecState& s, uint32_t flags, int form) {
+    if (flags & RISVEC_STEP_3GPP) return plan_3gpp(s, form);
     switch (form) {
         case RISVEC_FORM_CACHED: return plan_generic(s, false, false);
         case RISVEC_FORM_CACHED_RING: return plan_generic(s, false, true);

@@ -90,6 +90,63 @@ int check_step(const char* fn, const RisVecState* s, const float* action, const 
     return RISVEC_OK;
 }
 
+// the transition-store arguments of risvec_step_ring / risvec_step_fused_3gpp, checked and translated
+int check_ring(const char* fn, const RisVecState* s, const RisVecStepRing* ring, uint32_t flags, risvec::StepRing* out) {
+    const uint32_t need = RISVEC_STEP_POLICY_ACTION | RISVEC_STEP_OBS;
+    if ((flags & need) != need)
+        return fail(RISVEC_ERR_ARG, "%s: flags must hold RISVEC_STEP_POLICY_ACTION | RISVEC_STEP_OBS (the ring stores the raw policy "
+                    "output and both observations)", fn);
+    if (flags & (RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX | RISVEC_STEP_REUSE_COLSUM | RISVEC_STEP_REUSE_SSUM | RISVEC_STEP_REUSE_IDX))
+        return fail(RISVEC_ERR_ARG, "%s: steering / theta-by-index / BCD flags (0x%x) are not accepted here", fn, flags);
+    const RisVecReplay& rb = ring->rb;
+    const int V = s->n_veh;
+    if (V != 4 && V != 8 && V != 16)
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: n_veh=%d (the fused transition store exists for 4, 8 and 16 vehicles)", fn, V);
+    if (rb.n_agents != V || rb.input_shape != 5 || rb.n_actions != V + 2)
+        return fail(RISVEC_ERR_SHAPE, "%s: the ring must have n_agents = n_veh = %d, input_shape = 5, n_actions = %d (got %d, %d, %d)",
+                    fn, V, V + 2, rb.n_agents, rb.input_shape, rb.n_actions);
+    if (rb.mem_size < s->n_envs) return fail(RISVEC_ERR_SHAPE, "%s: n_envs=%d transitions do not fit mem_size=%lld", fn, s->n_envs,
+                                             (long long)rb.mem_size);
+    if (ring->mem_cntr < 0) return fail(RISVEC_ERR_ARG, "%s: mem_cntr < 0", fn);
+    REQ_PTR(rb.state_memory, "ring.state_memory"); REQ_PTR(rb.action_memory, "ring.action_memory");
+    REQ_PTR(rb.reward_global_memory, "ring.reward_global_memory"); REQ_PTR(rb.reward_local_memory, "ring.reward_local_memory");
+    REQ_PTR(rb.new_state_memory, "ring.new_state_memory"); REQ_PTR(rb.terminal_memory, "ring.terminal_memory");
+    REQ_PTR(rb.mask_memory, "ring.mask_memory"); REQ_PTR(ring->probs, "ring.probs"); OPT_PTR(ring->mask, "ring.mask");
+    REQ_PTR(s->obs, "state.obs");
+    *out = risvec::StepRing{rb.state_memory, rb.action_memory, rb.reward_global_memory, rb.reward_local_memory, rb.new_state_memory,
+                       rb.terminal_memory, rb.mask_memory, ring->probs, ring->mask, (long long)(ring->mem_cntr % rb.mem_size),
+                       (long long)rb.mem_size, ring->done ? 1 : 0};
+    return RISVEC_OK;
+}
+
+// the arguments of the fused 3GPP entry points besides the ring and the trajectory
+int check_step_3gpp(const char* fn, const RisVecState* s, const RisVecParams* p, int32_t model, const float* action,
+                    const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals, const RisVecFading* fading,
+                    uint32_t flags) {
+    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
+    if (int rc = check_common(fn, s, p)) return rc;
+    if (model != RISVEC_CH_3GPP_UMI && model != RISVEC_CH_3GPP_UMA && model != RISVEC_CH_OTHER)
+        return fail(RISVEC_ERR_ARG, "%s: model=%d is not a 3GPP/other model (the RIS step entry points serve 'free')", fn, model);
+    if (flags & ~(uint32_t)(RISVEC_STEP_METRICS | RISVEC_STEP_POWER_W | RISVEC_STEP_OBS | RISVEC_STEP_POLICY_ACTION))
+        return fail(RISVEC_ERR_ARG, "%s: flags 0x%x: only METRICS / POWER_W / OBS / POLICY_ACTION are accepted (steering, "
+                    "theta-by-index and BCD are forms of the RIS step)", fn, flags);
+    if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, false)) return rc;
+    REQ_PTR(s->pos, "state.pos");
+    if (fading) {
+        OPT_PTR(fading->u_los, "fading.u_los"); OPT_PTR(fading->z_shadow, "fading.z_shadow"); OPT_PTR(fading->small, "fading.small");
+        const int n_inj = (fading->u_los != nullptr) + (fading->z_shadow != nullptr) + (fading->small != nullptr);
+        if (n_inj != 0 && n_inj != 3)
+            return fail(RISVEC_ERR_ARG, "%s: fading.u_los, z_shadow, small must all be given or all be NULL", fn);
+    }
+    return RISVEC_OK;
+}
+
+risvec::Chan3gpp chan_3gpp(const RisVecState* s, int32_t model, const RisVecFading* fading, uint32_t chan_counter) {
+    risvec::Chan3gpp c{s->pos, nullptr, nullptr, nullptr, chan_counter, model};
+    if (fading && fading->u_los) { c.u_los = fading->u_los; c.z_shadow = fading->z_shadow; c.small = fading->small; }
+    return c;
+}
+
 }  // namespace
 
 namespace risvec {
@@ -464,35 +521,52 @@ int risvec_step_ring(const RisVecState* s, const RisVecParams* p, const RisVecSt
     if (!ring) return fail(RISVEC_ERR_ARG, "%s: ring is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, fused != 0)) return rc;
-    const uint32_t need = RISVEC_STEP_POLICY_ACTION | RISVEC_STEP_OBS;
-    if ((flags & need) != need)
-        return fail(RISVEC_ERR_ARG, "%s: flags must hold RISVEC_STEP_POLICY_ACTION | RISVEC_STEP_OBS (the ring stores the raw policy "
-                    "output and both observations)", fn);
-    if (flags & (RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX | RISVEC_STEP_REUSE_COLSUM | RISVEC_STEP_REUSE_SSUM | RISVEC_STEP_REUSE_IDX))
-        return fail(RISVEC_ERR_ARG, "%s: steering / theta-by-index / BCD flags (0x%x) are not accepted here", fn, flags);
-    const RisVecReplay& rb = ring->rb;
+    risvec::StepRing r;
+    if (int rc = check_ring(fn, s, ring, flags, &r)) return rc;
     const int V = s->n_veh;
-    if (V != 4 && V != 8 && V != 16)
-        return fail(RISVEC_ERR_UNSUPPORTED, "%s: n_veh=%d (the fused transition store exists for 4, 8 and 16 vehicles)", fn, V);
-    if (rb.n_agents != V || rb.input_shape != 5 || rb.n_actions != V + 2)
-        return fail(RISVEC_ERR_SHAPE, "%s: the ring must have n_agents = n_veh = %d, input_shape = 5, n_actions = %d (got %d, %d, %d)",
-                    fn, V, V + 2, rb.n_agents, rb.input_shape, rb.n_actions);
-    if (rb.mem_size < s->n_envs) return fail(RISVEC_ERR_SHAPE, "%s: n_envs=%d transitions do not fit mem_size=%lld", fn, s->n_envs,
-                                             (long long)rb.mem_size);
-    if (ring->mem_cntr < 0) return fail(RISVEC_ERR_ARG, "%s: mem_cntr < 0", fn);
-    REQ_PTR(rb.state_memory, "ring.state_memory"); REQ_PTR(rb.action_memory, "ring.action_memory");
-    REQ_PTR(rb.reward_global_memory, "ring.reward_global_memory"); REQ_PTR(rb.reward_local_memory, "ring.reward_local_memory");
-    REQ_PTR(rb.new_state_memory, "ring.new_state_memory"); REQ_PTR(rb.terminal_memory, "ring.terminal_memory");
-    REQ_PTR(rb.mask_memory, "ring.mask_memory"); REQ_PTR(ring->probs, "ring.probs"); OPT_PTR(ring->mask, "ring.mask");
-    REQ_PTR(s->obs, "state.obs");
-    risvec::StepRing r{rb.state_memory, rb.action_memory, rb.reward_global_memory, rb.reward_local_memory, rb.new_state_memory,
-                       rb.terminal_memory, rb.mask_memory, ring->probs, ring->mask, (long long)(ring->mem_cntr % rb.mem_size),
-                       (long long)rb.mem_size, ring->done ? 1 : 0};
     const hipError_t err = risvec::launch_step(*s, *p, action, partner, n_groups, arrivals, seed, counter, flags, fused != 0,
                                                (hipStream_t)stream, &r);
     if (err == hipErrorNotSupported)
         return fail(RISVEC_ERR_UNSUPPORTED, "%s: no fused-gains kernel with the transition store at n_veh=%d, n_ris=%d (use "
                     "risvec_step_fused + risvec_replay_store_policy)", fn, V, s->n_ris);
+    return finish(fn, err);
+}
+
+int risvec_step_fused_3gpp(const RisVecState* s, const RisVecParams* p, int32_t model, const float* action,
+                           const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals,
+                           const RisVecFading* fading, uint64_t seed, uint32_t counter, uint32_t chan_counter,
+                           uint32_t flags, const RisVecStepRing* ring, risvec_stream_t stream) {
+    const char* fn = "risvec_step_fused_3gpp";
+    if (int rc = check_step_3gpp(fn, s, p, model, action, partner, n_groups, arrivals, fading, flags)) return rc;
+    risvec::StepArgs a = risvec::make_step_args(*s, action, partner, n_groups, arrivals, seed, counter, flags);
+    if (ring)
+        if (int rc = check_ring(fn, s, ring, flags, &a.ring)) return rc;
+    const hipError_t err = risvec::launch_step_3gpp(*s, *p, a, chan_3gpp(s, model, fading, chan_counter),
+                                                    ring ? RISVEC_FORM_FUSED_RING : RISVEC_FORM_FUSED, 1, RisVecTraj{},
+                                                    (hipStream_t)stream);
+    if (err == hipErrorNotSupported)
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: no 3GPP step kernel at n_veh=%d%s", fn, s->n_veh, ring ? " with the ring" : "");
+    return finish(fn, err);
+}
+
+int risvec_step_fused_3gpp_multi(const RisVecState* s, const RisVecParams* p, int32_t model, int32_t n_steps,
+                                 const float* actions, const int32_t* partner, const int32_t* n_groups,
+                                 const int32_t* arrivals, const RisVecFading* fading, uint64_t seed, uint32_t counter,
+                                 uint32_t chan_counter, const RisVecTraj* traj, uint32_t flags, risvec_stream_t stream) {
+    const char* fn = "risvec_step_fused_3gpp_multi";
+    if (int rc = check_step_3gpp(fn, s, p, model, actions, partner, n_groups, arrivals, fading, flags)) return rc;
+    if (n_steps < 1 || n_steps > (1 << 20)) return fail(RISVEC_ERR_ARG, "%s: n_steps=%d outside [1, 2^20]", fn, n_steps);
+    RisVecTraj tj{nullptr, nullptr, nullptr};
+    if (traj) {
+        OPT_PTR(traj->reward, "traj.reward"); OPT_PTR(traj->obs, "traj.obs"); OPT_PTR(traj->metrics, "traj.metrics");
+        tj = *traj;
+        if (!(flags & RISVEC_STEP_OBS)) tj.obs = nullptr;      // obs records need the obs flag, as in risvec_step_multi
+    }
+    const risvec::StepArgs a = risvec::make_step_args(*s, actions, partner, n_groups, arrivals, seed, counter, flags);
+    const hipError_t err = risvec::launch_step_3gpp(*s, *p, a, chan_3gpp(s, model, fading, chan_counter),
+                                                    RISVEC_FORM_FUSED_MULTI, n_steps, tj, (hipStream_t)stream);
+    if (err == hipErrorNotSupported)
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: no 3GPP T-step kernel at n_veh=%d", fn, s->n_veh);
     return finish(fn, err);
 }
 

@@ -762,9 +762,9 @@ inline StepArgs make_step_args(const RisVecState& s, const float* action, const 
 // of the step family.  The launchers only instantiate and launch what it names; `name` is what risvec_last_kernel()
 // and risvec_step_kernel() report.
 struct StepPlan {
-    enum Family { NONE, CACHED, FUSED, STEER, LAT, PIPE };
+    enum Family { NONE, CACHED, FUSED, STEER, LAT, PIPE, G3 };   // G3: k_step_3gpp<VP[,RING|MULTI]>
     Family family = NONE;
-    int vp = 0;                        // CACHED / FUSED / STEER: lanes per env (pow2_ceil(V))
+    int vp = 0;                        // CACHED / FUSED / STEER / G3: lanes per env (pow2_ceil(V))
     int g = 0, vec = 0;                // FUSED: lanes per h_r row, complex elements per load
     int V = 0, M = 0, G = 0, NIT = 0;  // LAT: the FusedShape member (M = 0: run-time M); PIPE: the shape
     int epwt = 0;                      // LAT: envs per wavefront
@@ -772,7 +772,7 @@ struct StepPlan {
     bool ring = false, tk = false, multi = false;
     char name[96] = "";
 };
-// form: RISVEC_FORM_*; flags: the RISVEC_STEP_* flags of the call (only STEER and THETA_BY_INDEX select)
+// form: RISVEC_FORM_*; flags: the RISVEC_STEP_* flags of the call (only STEER, THETA_BY_INDEX and 3GPP select)
 StepPlan plan_step(const RisVecState& s, uint32_t flags, int form);
 // the software pipeline of this shape for a core named `core` (NONE when the shape has none)
 StepPlan plan_pipe(const RisVecState& s, const char* core);
@@ -800,9 +800,15 @@ hipError_t launch_step_multi(const RisVecState& s, const RisVecParams& p, const 
 // stride (zero for an absent buffer: a null pointer stays null) instead of being recomputed as `p ? p + t * stride :
 // nullptr` -- that was a branch around four scalar instructions per buffer per step, seven branches (and a
 // kernel-argument reload) in a loop whose lone wavefront pays an instruction-fetch restart for each.
-template <int VP>
+// The gain of step t: `g` itself for the cached-gain and RIS forms (constant over the launch), or a pointer to a functor
+// that draws step t's gain -- the fresh 3GPP fading of k_step_3gpp<VP,MULTI> (Gain3gppSteps, k_step_3gpp.hip).
+__device__ __forceinline__ float gain_at_step(float g, int) { return g; }
+template <class F>
+__device__ __forceinline__ float gain_at_step(F* f, int t) { return (*f)(t); }
+
+template <int VP, class GainT = float>
 __device__ __forceinline__ void multi_step_loop(const Dims& d, const RisVecParams& P, const StepArgs& A, const RisVecTraj& TJ,
-                                                int e, int v, bool active, float g, StepIn in, int n_steps) {
+                                                int e, int v, bool active, GainT g, StepIn in, int n_steps) {
     const int V = d.V;
     const long long ev = (long long)d.E * V, idx = (long long)e * V + v;
     const bool pol = (A.flags & RISVEC_STEP_POLICY_ACTION) != 0;
@@ -825,7 +831,7 @@ __device__ __forceinline__ void multi_step_loop(const Dims& d, const RisVecParam
         // next step's action: in flight during this step's arithmetic
         ap += 2 * ev;
         const float a0n = ap[0], a1n = ap[a1_off];
-        const StepCarry c = step_core<VP, true, true>(d, P, At, e, v, active, g, in, &tj);
+        const StepCarry c = step_core<VP, true, true>(d, P, At, e, v, active, gain_at_step(g, t), in, &tj);
         At.counter += 1u;
         At.arrivals += ar_stride;
         tj.reward += rw_stride;
@@ -837,7 +843,21 @@ __device__ __forceinline__ void multi_step_loop(const Dims& d, const RisVecParam
         in.a1 = a1n;
     }
     tj.store_state = true;
-    step_core<VP, true, true>(d, P, At, e, v, active, g, in, &tj);
+    step_core<VP, true, true>(d, P, At, e, v, active, gain_at_step(g, n_steps - 1), in, &tj);
 }
+
+// The fused 3GPP step family (k_step_3gpp.hip), the kernels' second argument: what the RIS forms read from StepArgs'
+// h_r / theta / pl is here the position and the draws of the channel update that runs in the same launch.
+struct Chan3gpp {
+    const double* pos;              // [E,V,2] float64
+    const float* u_los;             // injected draws, [E,V] ([T,E,V] for the T-step launch), all three or none:
+    const float* z_shadow;          //   nullptr = Philox at (env_offset + e, v, chan_counter (+ t), kSite3gpp)
+    const float* small;
+    uint32_t chan_counter;
+    int model;                      // RISVEC_CH_3GPP_UMI / _UMA / _OTHER
+};
+// form: RISVEC_FORM_FUSED (a.ring unused), _FUSED_RING (a.ring set), _FUSED_MULTI (n_steps, tj)
+hipError_t launch_step_3gpp(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const Chan3gpp& c, int form,
+                            int n_steps, const RisVecTraj& tj, hipStream_t st);
 
 }  // namespace risvec

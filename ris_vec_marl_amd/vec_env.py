@@ -452,9 +452,33 @@ class VecEnviron(ParamAttrs):
                              "(call compute_parms(); h_r written by hand has no steering base)")
         return N.STEP_STEER
 
+    def _model_3gpp(self) -> Optional[int]:
+        """RISVEC_CH_* of `channel_model` when the gain is NOT the RIS cascade ("free"), else None: what
+        `update_channel_gains` dispatches on (unknown keywords: CH_OTHER, a 0 dB path loss)."""
+        model = str(self.params.channel_model)
+        return None if model == "free" else CHANNEL_MODELS.get(model, N.CH_OTHER)
+
+    def _fading(self, fading, shape, bound: bool, fused: bool):
+        """Injected fading draws (u_los, z_shadow, small) of a fused 3GPP step -> (tensors, RisVecFading or None)."""
+        if fading is None:
+            return None, None
+        if not fused or self._model_3gpp() is None:
+            raise ValueError("fading= is accepted by the fused step forms under a 3GPP channel_model only (channel_model=%r)"
+                             % (self.params.channel_model,))
+        if len(fading) != 3 or any(x is None for x in fading):
+            raise ValueError("fading must be (u_los, z_shadow, small), all three given")
+        conv = self._bound if bound else self._arg
+        ts = tuple(conv(x, torch.float32, shape, n) for x, n in zip(fading, ("u_los", "z_shadow", "small")))
+        return ts, N.RisVecFading(*(_dev_ptr(x) for x in ts))
+
+    def _no_steer_3gpp(self, steer: bool) -> None:
+        if steer:
+            raise ValueError("steer=True is a form of the RIS cascade; channel_model=%r has no RIS in the gain"
+                             % (self.params.channel_model,))
+
     def step(self, action_power, partner, n_groups, arrivals=None, fused: bool = False, bcd: bool = False,
              metrics: bool = True, power_w: bool = True, obs: bool = True, policy_action: bool = False,
-             steer: bool = False) -> Tuple[torch.Tensor, ...]:
+             steer: bool = False, fading=None) -> Tuple[torch.Tensor, ...]:
         """Environment.py:547-731 for every env.
 
         action_power [E,2,V] float32 (or the policy output [E,V,2] with policy_action=True,
@@ -465,6 +489,9 @@ class VecEnviron(ParamAttrs):
         sweep first; steer=True (with fused) uses the fact that compute_parms made every h_r row a
         geometric sequence z^m and evaluates the cascade by Horner in float64 from the 16-byte base
         instead of reading the 8M-byte row (same results to ~1e-7; ~4x fewer bytes per step).
+        Under a 3GPP channel_model the fused forms update the 3GPP gains instead (`risvec_step_fused_3gpp`: what
+        update_channel_gains() + step(fused=False) do, in one launch; bcd=True runs optimize_phase_shift() first, as
+        the driver does); fading=(u_los, z_shadow, small) [E,V] injects their draws (None: Philox).
         Returns the reference's 7-tuple, batched:
         (per_user_reward [E,V], global_reward [E], DataBuf, data_t, data_p, over_power, over_data);
         the tensors are owned by the env and overwritten by the next step."""
@@ -474,6 +501,24 @@ class VecEnviron(ParamAttrs):
         pt = self._arg(partner, torch.int32, (E, V), "partner")
         ng = self._arg(n_groups, torch.int32, (E,), "n_groups")
         ar = self._arg(arrivals, torch.int32, (E, V), "arrivals")
+        model = self._model_3gpp()
+        fd_t, fd = self._fading(fading, (E, V), False, fused or bcd)
+        if model is not None and (fused or bcd):
+            self._no_steer_3gpp(steer)
+            if bcd:
+                self.optimize_phase_shift()
+            flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
+                     | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0))
+            self._chan += 1
+            N.check(N.load().risvec_step_fused_3gpp(C.byref(self._cstate), C.byref(self._p()), model, _dev_ptr(a),
+                                                    _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar),
+                                                    C.byref(fd) if fd is not None else None, self.seed, self._steps,
+                                                    self._chan, flags, None, self._stream()))
+            self._steps += 1
+            self._obs_stale = not obs
+            t = self._t
+            return (t["reward"], t["metrics"][:, 0], t["data_buf"], t["data_t"], t["data_p"], t["over_power"],
+                    t["over_data"])
         flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
                  | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0)
                  | (self._bcd_flags(None, step=True) if bcd else 0) | self._steer_flag(steer, fused or bcd))
@@ -502,7 +547,7 @@ class VecEnviron(ParamAttrs):
 
     def step_many(self, actions, partner, n_groups, arrivals=None, metrics: bool = True, power_w: bool = False,
                   obs: bool = True, policy_action: bool = False, record: Sequence[str] = ("reward", "obs", "metrics"),
-                  out: Optional[Dict[str, torch.Tensor]] = None, fused: bool = True) -> Dict[str, torch.Tensor]:
+                  out: Optional[Dict[str, torch.Tensor]] = None, fused: bool = True, fading=None) -> Dict[str, torch.Tensor]:
         """T consecutive fused `step()` calls in ONE launch (`risvec_step_fused_multi`): the driver's step loop
         marl_train_bcd.py:1304-1611 between two channel refreshes with the NOMA groups frozen, as they are
         inside an episode.  actions [T,E,2,V] float32 (or [T,E,V,2] with policy_action=True); partner / n_groups as
@@ -514,9 +559,11 @@ class VecEnviron(ParamAttrs):
         env's queues stay in registers: this is the launch to use when a batched step is shorter than a kernel
         launch (small E).  fused=False (`risvec_step_multi`) is the same on the CACHED gains -- T `step(...,
         fused=False)` calls, the reference driver's own cadence (gains only every 100 steps), any shape, h_r / theta
-        not read at all."""
+        not read at all.  Under a 3GPP channel_model fused=True is `risvec_step_fused_3gpp_multi`: T fused 3GPP steps,
+        fresh fading every step (fading=(u_los, z_shadow, small) [T,E,V] injects it)."""
         self._ensure_device()
-        if fused:
+        model = self._model_3gpp() if fused else None
+        if fused and model is None:
             self._sync_theta()
         E, V = self.n_envs, self.n_veh
         a = torch.as_tensor(actions)
@@ -543,6 +590,16 @@ class VecEnviron(ParamAttrs):
         tj = N.RisVecTraj(_dev_ptr(rec.get("reward")), _dev_ptr(rec.get("obs")), _dev_ptr(rec.get("metrics")))
         flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
                  | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0))
+        fd_t, fd = self._fading(fading, (T, E, V), False, fused)
+        if model is not None:
+            N.check(N.load().risvec_step_fused_3gpp_multi(
+                C.byref(self._cstate), C.byref(self._p()), model, T, _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng),
+                _dev_ptr(ar), C.byref(fd) if fd is not None else None, self.seed, self._steps, self._chan + 1,
+                C.byref(tj), flags, self._stream()))
+            self._chan += T
+            self._steps += T
+            self._obs_stale = not obs
+            return rec
         fn = N.load().risvec_step_fused_multi if fused else N.load().risvec_step_multi
         N.check(fn(C.byref(self._cstate), C.byref(self._p()), T, _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar),
                    self.seed, self._steps, flags, C.byref(tj), self._stream()))
@@ -553,7 +610,7 @@ class VecEnviron(ParamAttrs):
     def bind_step_many(self, actions: torch.Tensor, partner: torch.Tensor, n_groups: torch.Tensor,
                        arrivals: Optional[torch.Tensor] = None, metrics: bool = True, power_w: bool = False,
                        obs: bool = True, policy_action: bool = False,
-                       out: Optional[Dict[str, torch.Tensor]] = None, fused: bool = True):
+                       out: Optional[Dict[str, torch.Tensor]] = None, fused: bool = True, fading=None):
         """`step_many` validated and marshalled once: returns a zero-argument launcher that advances the env by
         T steps per call, reading `actions` [T,E,...] (and `arrivals`) in place and writing the per-step records
         into `out`'s tensors ("reward" [T,E,V], "obs" [T,E,V,5], "metrics" [T,E,16]; any subset)."""
@@ -572,19 +629,32 @@ class VecEnviron(ParamAttrs):
         flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
                  | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0))
         fn = N.load().risvec_step_fused_multi if fused else N.load().risvec_step_multi
+        fn3 = N.load().risvec_step_fused_3gpp_multi
         cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
         pa, pp, pn, par, ptj = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar), C.byref(tj)
+        fd_t, fd = self._fading(fading, (T, E, V), True, fused)
+        pfd = C.byref(fd) if fd is not None else None
 
         def launch() -> None:
-            if fused:
-                self._sync_theta()
-            rc = fn(cs, C.byref(self._p()), T, pa, pp, pn, par, seed, self._steps, flags, ptj, stream)
-            if rc:
-                N.check(rc)
+            model = self._model_3gpp() if fused else None
+            if model is not None:            # the fused form under a 3GPP channel model (the RIS is not in the gain)
+                rc = fn3(cs, C.byref(self._p()), model, T, pa, pp, pn, par, pfd, seed, self._steps, self._chan + 1, ptj,
+                         flags, stream)
+                if rc:
+                    N.check(rc)
+                self._chan += T
+            else:
+                if pfd is not None:
+                    raise ValueError("fading= is accepted under a 3GPP channel_model only")
+                if fused:
+                    self._sync_theta()
+                rc = fn(cs, C.byref(self._p()), T, pa, pp, pn, par, seed, self._steps, flags, ptj, stream)
+                if rc:
+                    N.check(rc)
             self._steps += T
             self._obs_stale = not obs
 
-        launch.inputs = (a, pt, ng, ar, rec, tj)
+        launch.inputs = (a, pt, ng, ar, rec, tj, fd_t, fd)
         launch.n_steps = T
         return launch
 
@@ -642,7 +712,7 @@ class VecEnviron(ParamAttrs):
 
     def bind_step(self, action_power, partner, n_groups, arrivals=None, fused: bool = False, bcd: bool = False,
                   metrics: bool = True, power_w: bool = True, obs: bool = True, policy_action: bool = False,
-                  steer: bool = False):
+                  steer: bool = False, fading=None):
         """Validate and marshal a `step()` call ONCE and return a zero-argument callable that
         launches one step per call on the stream current at bind time, reading the SAME input
         tensors each time (update them in place between calls).  Cuts the per-step host cost
@@ -661,11 +731,30 @@ class VecEnviron(ParamAttrs):
                       | self._steer_flag(steer, fused or bcd))
         lib = N.load()
         fn = lib.risvec_step_fused_bcd if bcd else (lib.risvec_step_fused if fused else lib.risvec_step)
+        fn3 = lib.risvec_step_fused_3gpp
         cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
         pa, pp, pn, par = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar)
-        keep = (a, pt, ng, ar)           # the closure owns the marshalled tensors
+        fd_t, fd = self._fading(fading, (E, V), True, fused or bcd)
+        pfd = C.byref(fd) if fd is not None else None
+        flags3 = base_flags & ~N.STEP_STEER
+        keep = (a, pt, ng, ar, fd_t, fd)           # the closure owns the marshalled tensors
 
         def launch() -> None:
+            model = self._model_3gpp() if (fused or bcd) else None
+            if model is not None:            # the fused forms under a 3GPP channel model (the RIS is not in the gain)
+                self._no_steer_3gpp(steer)
+                if bcd:
+                    self.optimize_phase_shift()
+                self._chan += 1
+                rc = fn3(cs, C.byref(self._p()), model, pa, pp, pn, par, pfd, seed, self._steps, self._chan, flags3, None,
+                         stream)
+                if rc:
+                    N.check(rc)
+                self._steps += 1
+                self._obs_stale = not obs
+                return
+            if pfd is not None:
+                raise ValueError("fading= is accepted under a 3GPP channel_model only")
             flags = base_flags | (self._bcd_flags(None, step=True) if bcd else 0)
             if self.lazy_theta or self._theta_stale:
                 flags = self._theta_mode(flags, fused or bcd, bcd, steer)
@@ -683,7 +772,7 @@ class VecEnviron(ParamAttrs):
 
     def bind_step_store(self, replay, power_raw: torch.Tensor, partner: torch.Tensor, n_groups: torch.Tensor,
                         probs: torch.Tensor, mask: Optional[torch.Tensor] = None, arrivals: Optional[torch.Tensor] = None,
-                        fused: bool = True, metrics: bool = True, power_w: bool = False):
+                        fused: bool = True, metrics: bool = True, power_w: bool = False, fading=None):
         """The rollout step with the transition store fused in (`risvec_step_ring`; marl_train_bcd.py:1601-1611,
         1776-1799): ONE launch runs `step()` on the raw policy output `power_raw` [E,V,2] and appends this step's E
         transitions to `replay` (a `VecReplayBuffer` with input_shape 5, n_actions V+2, n_agents V) -- state = the
@@ -692,7 +781,9 @@ class VecEnviron(ParamAttrs):
         of `bind_step(policy_action=True)` followed by `replay.bind_store(..., policy_out=(power_raw, probs))`, bit
         for bit.  Returns `launch(done=False, use_mask=True)`; all tensors are read in place on every call.
         fused=True needs a shape with a software-pipelined kernel ((8,64), (8,36), (8,40), (4,16), (16,64), (16,256));
-        fused=False steps on the cached gains, any M."""
+        fused=False steps on the cached gains, any M.  Under a 3GPP channel_model fused=True updates the 3GPP gains
+        in the same launch instead (`risvec_step_fused_3gpp` with the ring; any M, V in {4, 8, 16}); fading=(u_los,
+        z_shadow, small) [E,V] device tensors inject its draws, read in place."""
         self._ensure_device()
         E, V = self.n_envs, self.n_veh
         a = self._bound(power_raw, torch.float32, (E, V, 2), "power_raw")
@@ -709,24 +800,35 @@ class VecEnviron(ParamAttrs):
         ring.rb = replay._c
         ring.probs, ring.mask = pr.data_ptr(), None
         fn, cs, seed, stream = N.load().risvec_step_ring, C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
+        fn3 = N.load().risvec_step_fused_3gpp
         pa, pp, pn, par, pmask = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar), _dev_ptr(mk)
         fz = 1 if fused else 0
+        fd_t, fd = self._fading(fading, (E, V), True, fused)
+        pfd = C.byref(fd) if fd is not None else None
 
         def launch(done: bool = False, use_mask: bool = True) -> None:
             if self._obs_stale:
                 self.observe()                   # the ring's `state` is the observation tensor as the kernel finds it
-            if fused:
+            model = self._model_3gpp() if fused else None
+            if model is None and fused:
+                if pfd is not None:
+                    raise ValueError("fading= is accepted under a 3GPP channel_model only")
                 self._sync_theta()
             ring.mem_cntr, ring.done = replay.mem_cntr, 1 if done else 0
             ring.mask = pmask if use_mask else None
-            rc = fn(cs, C.byref(self._p()), C.byref(ring), pa, pp, pn, par, seed, self._steps, flags, fz, stream)
+            if model is not None:                # fused under a 3GPP channel model: 3GPP gains + step + store
+                self._chan += 1
+                rc = fn3(cs, C.byref(self._p()), model, pa, pp, pn, par, pfd, seed, self._steps, self._chan, flags,
+                         C.byref(ring), stream)
+            else:
+                rc = fn(cs, C.byref(self._p()), C.byref(ring), pa, pp, pn, par, seed, self._steps, flags, fz, stream)
             if rc:
                 N.check(rc)
             replay.mem_cntr += E
             self._steps += 1
             self._obs_stale = False
 
-        launch.inputs = (a, pt, ng, pr, mk, ar, ring, replay)
+        launch.inputs = (a, pt, ng, pr, mk, ar, ring, replay, fd_t, fd)
         return launch
 
     # ------------------------------------------------------------------ driver-side helpers
