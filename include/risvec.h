@@ -221,7 +221,8 @@ typedef void *risvec_stream_t;
 
 uint32_t risvec_abi_version(void);
 /* Name of the kernel the calling thread's last risvec_step* / risvec_bcd call dispatched ("" before the first): which
- * member of the fused-step family a shape / batch size takes is a dispatch decision; tests assert it. */
+ * member of the fused-step family a shape / batch size takes is a dispatch decision; tests assert it.
+ * risvec_colsum and risvec_geometry (when it refreshes c_col) name the column-sum member they launched. */
 const char *risvec_last_kernel(void);
 const char *risvec_last_error(void);
 

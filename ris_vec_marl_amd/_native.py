@@ -266,7 +266,7 @@ def resolve_device(device):
 
 
 def last_kernel() -> str:
-    """Name of the kernel the calling thread's last step / BCD call dispatched (risvec_last_kernel)."""
+    """Name of the kernel the calling thread's last step / BCD / column-sum call dispatched (risvec_last_kernel)."""
     k = load().risvec_last_kernel()
     return k.decode() if k else ""
 

@@ -817,6 +817,7 @@ hipError_t launch_colsum(const RisVecState& s, hipStream_t st) {
             if (nt) hipLaunchKernelGGL((k_colsum_rows256<16, true>), g, b, 0, st, dims_of(s), s.h_r, s.b, s.c_col);
             else hipLaunchKernelGGL((k_colsum_rows256<16, false>), g, b, 0, st, dims_of(s), s.h_r, s.b, s.c_col);
         }
+        note_kernel("k_colsum_rows256<%d%s>", s.n_veh <= 8 ? 8 : 16, nt ? ",NT" : "");
         return hipGetLastError();
     }
     if (s.n_ris % kSlabM == 0 && s.n_veh <= 16) {
@@ -830,6 +831,7 @@ hipError_t launch_colsum(const RisVecState& s, hipStream_t st) {
                 if (nt) hipLaunchKernelGGL((k_colsum_slab<16, true>), g, b, 0, st, dims_of(s), s.h_r, s.b, s.c_col);
                 else hipLaunchKernelGGL((k_colsum_slab<16, false>), g, b, 0, st, dims_of(s), s.h_r, s.b, s.c_col);
             }
+            note_kernel("k_colsum_slab<%d%s>", s.n_veh <= 8 ? 8 : 16, nt ? ",NT" : "");
             return hipGetLastError();
         }
     }
@@ -838,6 +840,7 @@ hipError_t launch_colsum(const RisVecState& s, hipStream_t st) {
     const unsigned grid = (unsigned)((n_slot + kBlock / 2 - 1) / (kBlock / 2));
     if (even) hipLaunchKernelGGL((k_colsum<2>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), s.h_r, s.b, s.c_col);
     else hipLaunchKernelGGL((k_colsum<1>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), s.h_r, s.b, s.c_col);
+    note_kernel("k_colsum<%d>", even ? 2 : 1);
     return hipGetLastError();
 }
 

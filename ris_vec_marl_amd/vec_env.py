@@ -101,6 +101,7 @@ class VecEnviron(ParamAttrs):
         # materialised when somebody asks for it (`tensors`, any other consumer).  Same step outputs bit for bit.
         self.lazy_theta = bool(lazy_theta)
         self._theta_stale = False      # tensors["theta"] lags behind theta_idx (only ever True with lazy_theta)
+        self._stale_version = -1       # tensors["theta"]._version when it went stale: a later write through torch moves it
         self._tk_ok = None             # does the fused step have a theta-by-index form at this shape? (asked lazily)
         self._cstate: Optional[N.RisVecState] = None
         self._cparams: Optional[N.RisVecParams] = None
@@ -332,7 +333,8 @@ class VecEnviron(ParamAttrs):
     def rebuild_colsum(self) -> None:
         """Recompute the BCD cache c_col[e,m] = (sum_v h_r[e,v,m]) b[m] (float64).  compute_parms()
         does it already; call this after writing `tensors["h_r"]` directly (which also ends the
-        validity of the steering form of the fused step, `steer=True`)."""
+        validity of the steering form of the fused step, `steer=True`).  theta, its cached sum aside, is
+        left as it is: candidate indices the last sweep kept stay valid (the next sweep re-sums theta.c)."""
         self._ensure_device()
         N.check(N.load().risvec_colsum(C.byref(self._cstate), self._stream()))
         self._colsum_valid = True
@@ -345,15 +347,34 @@ class VecEnviron(ParamAttrs):
         return c.permute(0, 2, 1).reshape(-1, self.M)[: self.n_envs].clone()
 
     def invalidate_colsum(self) -> None:
-        """Tell the env that h_r or theta was modified behind its back (a direct write to
-        `tensors[...]`): the next BCD rebuilds c_col, re-sums theta.c and re-derives the candidate indices."""
+        """Announce a direct write to `tensors["h_r"]` (and/or `tensors["theta"]`): the next BCD rebuilds c_col,
+        re-sums theta.c and re-derives the candidate indices, and the steering form of the fused step
+        (`steer=True`) is refused until compute_parms() writes steering vectors again.  theta is handled as by
+        invalidate_theta(): if it was not written, what the sweeps left in it is kept."""
         self._colsum_valid = False
-        self._theta_changed()
+        self._steer_valid = False      # h_r is no longer known to be the steering vectors z_r^m
+        self._theta_written()
 
     def invalidate_theta(self) -> None:
-        """Tell the env that `tensors["theta"]` was written directly: the next BCD sweep re-sums theta.c and
-        re-derives the candidate indices (the phase setters and the sweeps themselves keep track on their own)."""
+        """Announce a direct write to `tensors["theta"]`: the written tensor becomes theta, and the next BCD sweep
+        re-sums theta.c and re-derives the candidate indices (the phase setters and the sweeps themselves keep
+        track on their own).  With lazy_theta, where the last sweeps may have kept theta by index only, a theta
+        tensor that torch has not written since (its `_version` has not moved) is first materialised from those
+        indices, so an announcement without a theta write loses no sweep."""
+        self._theta_written()
+
+    def _theta_written(self) -> None:
+        """An announced direct write (invalidate_colsum / invalidate_theta) that may or may not have touched theta."""
+        # (read through `_t`: `tensors` would materialise theta before the check)
+        if self._theta_stale and self._t["theta"]._version == self._stale_version:
+            self._sync_theta()         # theta not written: the indices hold the swept theta, keep it
         self._theta_changed()
+
+    def _mark_theta_stale(self, stale: bool) -> None:
+        """The last sweep kept theta by index (stale) or wrote the complex64 tensor."""
+        self._theta_stale = stale
+        if stale:
+            self._stale_version = self._t["theta"]._version     # kernels write through raw pointers: no bump
 
     def _theta_changed(self) -> None:
         """theta was written by something other than a BCD sweep: its cached sum and candidate indices are stale."""
@@ -389,7 +410,7 @@ class VecEnviron(ParamAttrs):
             flags |= N.BCD_NO_THETA        # the indices are the state; theta follows on demand
         N.check(N.load().risvec_bcd(C.byref(self._cstate), C.byref(self._p()), _dev_ptr(idx), flags, self._stream()))
         self._bcd_done(flags, step=False)
-        self._theta_stale = lazy
+        self._mark_theta_stale(lazy)
         return idx
 
     def update_channel_gains(self, u_los=None, z_shadow=None, small=None) -> None:
@@ -529,7 +550,7 @@ class VecEnviron(ParamAttrs):
                    _dev_ptr(ar), self.seed, self._steps, flags, self._stream()))
         if bcd:
             self._bcd_done(flags, step=True)
-            self._theta_stale = bool(flags & N.STEP_THETA_BY_INDEX)
+            self._mark_theta_stale(bool(flags & N.STEP_THETA_BY_INDEX))
         self._steps += 1
         self._obs_stale = not obs
         t = self._t
@@ -763,7 +784,7 @@ class VecEnviron(ParamAttrs):
                 N.check(rc)
             if bcd:
                 self._bcd_done(flags, step=True)
-                self._theta_stale = bool(flags & N.STEP_THETA_BY_INDEX)
+                self._mark_theta_stale(bool(flags & N.STEP_THETA_BY_INDEX))
             self._steps += 1
             self._obs_stale = not obs
 

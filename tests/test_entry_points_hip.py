@@ -28,7 +28,8 @@ def _bcd_step_reference(t, th_in, B0, Q0, action, partner, ng, arrivals, p, bbit
     return o_th, o_idx, safe, h, b
 
 
-@pytest.mark.parametrize("V,M,E", [(16, 256, 96), (8, 64, 300)])
+@pytest.mark.parametrize("V,M,E", [(16, 256, 96), (8, 64, 300), (8, 36, 130), (5, 21, 97), (8, 100, 257), (16, 20, 65),
+                                   (8, 520, 33)])
 @pytest.mark.parametrize("bound", [False, True])
 def test_step_bcd_entry_vs_oracle(V, M, E, bound):
     """The launch path BASELINE configs[4] is benchmarked through (bench.py --mode bcd): consecutive
@@ -692,9 +693,14 @@ def test_full_size_properties_c5():
         return env
 
     def objective(env):
-        t = env.tensors
-        th = torch.view_as_complex(t["theta"]); hr = torch.view_as_complex(t["h_r"]); b = torch.view_as_complex(t["b"])
-        return (th * hr.sum(1) * b[None]).sum(1).abs().double() ** 2
+        """K |sum_m theta_m c_m|^2 / K in complex128: theta as the exact candidate phasors its float32 images stand for
+        (the diagonal ones are the only inexact images), c = the sweep's own float64 column sums"""
+        th = torch.view_as_complex(env.tensors["theta"])
+        diag = (th.real.abs() == 0.70710677) & (th.imag.abs() == 0.70710677)
+        r = 0.70710678118654757
+        re = torch.where(diag, torch.sign(th.real.double()) * r, th.real.double())
+        im = torch.where(diag, torch.sign(th.imag.double()) * r, th.imag.double())
+        return (torch.complex(re, im) * env.colsum_rows()).sum(1).abs() ** 2
 
     keys = ("reward", "gain", "data_buf", "mec_q", "rate", "metrics", "obs", "theta")
     whole = build(E, 0, True)
@@ -702,17 +708,25 @@ def test_full_size_properties_c5():
     obj = [objective(whole)]
     names = []
     for i in range(3):
+        if i == 2:                                       # the backlog the last step starts from, and its step counter
+            B_last, k_last = whole.tensors["data_buf"].clone(), whole._steps
         whole.step(action, partner, ng, None, fused=True, bcd=True)
         names.append(N.last_kernel())
         obj.append(objective(whole))                     # (materialises theta: the next step is by index again)
     assert names[0] == "k_step_fused_lat<16,256,1,NT>", names          # first sweep: indices unknown, theta written
     assert names[1] == names[2] == "k_step_fused_lat<16,256,1,NT,TK>", names
     for a, b in zip(obj[:-1], obj[1:]):
-        assert bool((b >= a * (1 - 1e-5)).all())         # coordinate ascent (the check itself is a complex64 sum)
+        assert bool((b >= a * (1 - 1e-9)).all())         # coordinate ascent, float64 objective of the swept phasors
     got = {k: whole.tensors[k].clone() for k in keys}
     # kbit conservation of the last step: what left the backlog was processed locally or offloaded
     m = got["metrics"]
     assert bool((m[:, 1] >= 0).all()) and bool((m[:, 2] >= 0).all())
+    lam = orc.OracleParams.yaml_effective().rate
+    arr = torch.from_numpy(orc.philox_arrivals(np.arange(E), V, k_last, 3, lam).astype(np.float32)).cuda()
+    left = got["data_buf"] - arr                         # DataBuf' - arrivals = max(0, B - data_p - off) >= 0
+    assert bool((left >= -1e-5).all())
+    spent = (B_last - left).sum(1)
+    assert torch.allclose(spent, m[:, 1] + m[:, 2], rtol=1e-4, atol=1e-4)
     for lo, hi in ((0, E // 2), (E // 2, E)):
         h = build(hi - lo, lo, False)
         for i in range(3):
