@@ -36,7 +36,9 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
             return fail(RISVEC_ERR_ARG, "%s: %s is not 16-byte aligned", fn, name);          \
     } while (0)
 
-int check_common(const char* fn, const RisVecState* s, const RisVecParams* p) {
+// every entry point opens with this; `params` = false for the ones that take no RisVecParams (p is NULL there)
+int check_common(const char* fn, const RisVecState* s, const RisVecParams* p, bool params = true) {
+    if (params && !p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (!s) return fail(RISVEC_ERR_ARG, "%s: state is NULL", fn);
     if (s->abi_version != RISVEC_ABI_VERSION || s->struct_bytes != sizeof(RisVecState))
         return fail(RISVEC_ERR_ARG, "%s: RisVecState ABI mismatch (version %u/%u, bytes %u/%zu)", fn,
@@ -65,8 +67,22 @@ int finish(const char* fn, hipError_t err) {
     return RISVEC_OK;
 }
 
+// The arguments every step entry point shares.  A T-step entry point passes `tj` as well: n_steps and the records are
+// checked, and *tj becomes the records its kernels write (an obs record needs RISVEC_STEP_OBS).
 int check_step(const char* fn, const RisVecState* s, const float* action, const int32_t* partner,
-               const int32_t* n_groups, const int32_t* arrivals, uint32_t flags, bool fused) {
+               const int32_t* n_groups, const int32_t* arrivals, uint32_t flags, bool fused, int32_t n_steps = 1,
+               const RisVecTraj* traj = nullptr, RisVecTraj* tj = nullptr) {
+    if (tj) {
+        if (n_steps < 1 || n_steps > (1 << 20)) return fail(RISVEC_ERR_ARG, "%s: n_steps=%d outside [1, 2^20]", fn, n_steps);
+        if (flags & (RISVEC_STEP_REUSE_COLSUM | RISVEC_STEP_REUSE_SSUM | RISVEC_STEP_REUSE_IDX | RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX))
+            return fail(RISVEC_ERR_ARG, "%s: the BCD / steering flags (0x%x) are not accepted by the multi-step launch", fn, flags);
+        *tj = RisVecTraj{nullptr, nullptr, nullptr};
+        if (traj) {
+            OPT_PTR(traj->reward, "traj.reward"); OPT_PTR(traj->obs, "traj.obs"); OPT_PTR(traj->metrics, "traj.metrics");
+            *tj = *traj;
+            if (!(flags & RISVEC_STEP_OBS)) tj->obs = nullptr;
+        }
+    }
     REQ_PTR(action, "action"); REQ_PTR(partner, "partner"); REQ_PTR(n_groups, "n_groups");
     OPT_PTR(arrivals, "arrivals");
     REQ_PTR(s->gain, "state.gain"); REQ_PTR(s->data_buf, "state.data_buf"); REQ_PTR(s->mec_q, "state.mec_q");
@@ -119,25 +135,34 @@ int check_ring(const char* fn, const RisVecState* s, const RisVecStepRing* ring,
     return RISVEC_OK;
 }
 
-// the arguments of the fused 3GPP entry points besides the ring and the trajectory
+// the model and the injected fading draws of a 3GPP gain; `pre` + name is what the caller calls a draw, `free_fn` serves 'free'
+int check_3gpp(const char* fn, int32_t model, const float* u_los, const float* z_shadow, const float* small, const char* pre,
+               const char* free_fn) {
+    if (model != RISVEC_CH_3GPP_UMI && model != RISVEC_CH_3GPP_UMA && model != RISVEC_CH_OTHER)
+        return fail(RISVEC_ERR_ARG, "%s: model=%d is not a 3GPP/other model (%s 'free')", fn, model, free_fn);
+    const struct { const float* ptr; const char* name; } draws[3] = {{u_los, "u_los"}, {z_shadow, "z_shadow"}, {small, "small"}};
+    int n_inj = 0;
+    for (const auto& d : draws) {
+        if (!aligned16(d.ptr)) return fail(RISVEC_ERR_ARG, "%s: %s%s is not 16-byte aligned", fn, pre, d.name);
+        n_inj += d.ptr != nullptr;
+    }
+    if (n_inj != 0 && n_inj != 3)
+        return fail(RISVEC_ERR_ARG, "%s: %su_los, z_shadow, small must all be given or all be NULL", fn, pre);
+    return RISVEC_OK;
+}
+
+// the arguments of the fused 3GPP entry points besides the ring (`tj`: as for check_step)
 int check_step_3gpp(const char* fn, const RisVecState* s, const RisVecParams* p, int32_t model, const float* action,
                     const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals, const RisVecFading* fading,
-                    uint32_t flags) {
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
+                    uint32_t flags, int32_t n_steps = 1, const RisVecTraj* traj = nullptr, RisVecTraj* tj = nullptr) {
     if (int rc = check_common(fn, s, p)) return rc;
-    if (model != RISVEC_CH_3GPP_UMI && model != RISVEC_CH_3GPP_UMA && model != RISVEC_CH_OTHER)
-        return fail(RISVEC_ERR_ARG, "%s: model=%d is not a 3GPP/other model (the RIS step entry points serve 'free')", fn, model);
+    const RisVecFading fd = fading ? *fading : RisVecFading{nullptr, nullptr, nullptr};
+    if (int rc = check_3gpp(fn, model, fd.u_los, fd.z_shadow, fd.small, "fading.", "the RIS step entry points serve")) return rc;
     if (flags & ~(uint32_t)(RISVEC_STEP_METRICS | RISVEC_STEP_POWER_W | RISVEC_STEP_OBS | RISVEC_STEP_POLICY_ACTION))
         return fail(RISVEC_ERR_ARG, "%s: flags 0x%x: only METRICS / POWER_W / OBS / POLICY_ACTION are accepted (steering, "
                     "theta-by-index and BCD are forms of the RIS step)", fn, flags);
-    if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, false)) return rc;
+    if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, false, n_steps, traj, tj)) return rc;
     REQ_PTR(s->pos, "state.pos");
-    if (fading) {
-        OPT_PTR(fading->u_los, "fading.u_los"); OPT_PTR(fading->z_shadow, "fading.z_shadow"); OPT_PTR(fading->small, "fading.small");
-        const int n_inj = (fading->u_los != nullptr) + (fading->z_shadow != nullptr) + (fading->small != nullptr);
-        if (n_inj != 0 && n_inj != 3)
-            return fail(RISVEC_ERR_ARG, "%s: fading.u_los, z_shadow, small must all be given or all be NULL", fn);
-    }
     return RISVEC_OK;
 }
 
@@ -171,7 +196,7 @@ const char* risvec_last_error(void) { return g_err; }
 const char* risvec_step_kernel(const RisVecState* s, uint32_t flags, int32_t form) {
     const char* fn = "risvec_step_kernel";
     thread_local char name[sizeof(risvec::StepPlan::name)];
-    if (check_common(fn, s, nullptr)) return nullptr;
+    if (check_common(fn, s, nullptr, false)) return nullptr;
     if (form < RISVEC_FORM_CACHED || form > RISVEC_FORM_FUSED_MULTI) {
         fail(RISVEC_ERR_ARG, "%s: form=%d is not a RISVEC_FORM_*", fn, form);
         return nullptr;
@@ -245,7 +270,6 @@ void risvec_default_params(RisVecParams* p) {
 int risvec_reset(const RisVecState* s, const RisVecParams* p, const int32_t* spawn_ints,
                  const int32_t* buf0, uint64_t seed, uint32_t counter, risvec_stream_t stream) {
     const char* fn = "risvec_reset";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     REQ_PTR(s->pos, "state.pos"); REQ_PTR(s->dir, "state.dir"); REQ_PTR(s->vel, "state.vel");
     REQ_PTR(s->data_buf, "state.data_buf");
@@ -260,7 +284,6 @@ int risvec_reset(const RisVecState* s, const RisVecParams* p, const int32_t* spa
 int risvec_mobility(const RisVecState* s, const RisVecParams* p, const float* u_turn, int32_t* n_used,
                     uint64_t seed, uint32_t counter, risvec_stream_t stream) {
     const char* fn = "risvec_mobility";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     REQ_PTR(s->pos, "state.pos"); REQ_PTR(s->dir, "state.dir"); REQ_PTR(s->vel, "state.vel");
     OPT_PTR(u_turn, "u_turn"); OPT_PTR(n_used, "n_used");
@@ -269,7 +292,6 @@ int risvec_mobility(const RisVecState* s, const RisVecParams* p, const float* u_
 
 int risvec_geometry(const RisVecState* s, const RisVecParams* p, risvec_stream_t stream) {
     const char* fn = "risvec_geometry";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     REQ_PTR(s->pos, "state.pos"); REQ_PTR(s->dist_r, "state.dist_r"); REQ_PTR(s->ang_r, "state.ang_r");
     OPT_PTR(s->z_r, "state.z_r");
@@ -285,7 +307,6 @@ int risvec_geometry(const RisVecState* s, const RisVecParams* p, risvec_stream_t
 
 int risvec_gain(const RisVecState* s, const RisVecParams* p, risvec_stream_t stream) {
     const char* fn = "risvec_gain";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->b, "state.b");
     REQ_PTR(s->pl, "state.pl"); REQ_PTR(s->gain, "state.gain"); OPT_PTR(s->h_d, "state.h_d");
@@ -296,22 +317,16 @@ int risvec_gain_3gpp(const RisVecState* s, const RisVecParams* p, int32_t model,
                      const float* z_shadow, const float* small, uint64_t seed, uint32_t counter,
                      risvec_stream_t stream) {
     const char* fn = "risvec_gain_3gpp";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
-    if (model != RISVEC_CH_3GPP_UMI && model != RISVEC_CH_3GPP_UMA && model != RISVEC_CH_OTHER)
-        return fail(RISVEC_ERR_ARG, "%s: model=%d is not a 3GPP/other model (use risvec_gain for 'free')", fn, model);
+    if (int rc = check_3gpp(fn, model, u_los, z_shadow, small, "", "use risvec_gain for")) return rc;
     REQ_PTR(s->pos, "state.pos"); REQ_PTR(s->gain, "state.gain");
-    OPT_PTR(u_los, "u_los"); OPT_PTR(z_shadow, "z_shadow"); OPT_PTR(small, "small");
-    const int n_inj = (u_los != nullptr) + (z_shadow != nullptr) + (small != nullptr);
-    if (n_inj != 0 && n_inj != 3)
-        return fail(RISVEC_ERR_ARG, "%s: u_los, z_shadow, small must all be given or all be NULL", fn);
     return finish(fn, risvec::launch_gain_3gpp(*s, *p, model, u_los, z_shadow, small, seed, counter,
                                                (hipStream_t)stream));
 }
 
 int risvec_colsum(const RisVecState* s, risvec_stream_t stream) {
     const char* fn = "risvec_colsum";
-    if (int rc = check_common(fn, s, nullptr)) return rc;
+    if (int rc = check_common(fn, s, nullptr, false)) return rc;
     REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->b, "state.b"); REQ_PTR(s->c_col, "state.c_col");
     return finish(fn, risvec::launch_colsum(*s, (hipStream_t)stream));
 }
@@ -319,7 +334,6 @@ int risvec_colsum(const RisVecState* s, risvec_stream_t stream) {
 int risvec_bcd(const RisVecState* s, const RisVecParams* p, int32_t* idx_out, uint32_t flags,
                risvec_stream_t stream) {
     const char* fn = "risvec_bcd";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->b, "state.b");
     REQ_PTR(s->c_col, "state.c_col");
@@ -341,7 +355,7 @@ int risvec_bcd(const RisVecState* s, const RisVecParams* p, int32_t* idx_out, ui
 
 int risvec_theta_from_index(const RisVecState* s, risvec_stream_t stream) {
     const char* fn = "risvec_theta_from_index";
-    if (int rc = check_common(fn, s, nullptr)) return rc;
+    if (int rc = check_common(fn, s, nullptr, false)) return rc;
     REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->theta_idx, "state.theta_idx");
     if (s->control_bit != 3) return fail(RISVEC_ERR_UNSUPPORTED, "%s: candidate indices exist for control_bit = 3 only", fn);
     return finish(fn, risvec::launch_theta_from_index(*s, (hipStream_t)stream));
@@ -353,7 +367,7 @@ int risvec_theta_by_index_supported(int32_t n_veh, int32_t n_ris) {
 
 int risvec_set_phase(const RisVecState* s, const float* angle, risvec_stream_t stream) {
     const char* fn = "risvec_set_phase";
-    if (int rc = check_common(fn, s, nullptr)) return rc;
+    if (int rc = check_common(fn, s, nullptr, false)) return rc;
     REQ_PTR(angle, "angle"); REQ_PTR(s->theta, "state.theta");
     return finish(fn, risvec::launch_set_phase(*s, angle, (hipStream_t)stream));
 }
@@ -361,7 +375,7 @@ int risvec_set_phase(const RisVecState* s, const float* angle, risvec_stream_t s
 int risvec_random_phase(const RisVecState* s, const int32_t* idx, uint64_t seed, uint32_t counter,
                         risvec_stream_t stream) {
     const char* fn = "risvec_random_phase";
-    if (int rc = check_common(fn, s, nullptr)) return rc;
+    if (int rc = check_common(fn, s, nullptr, false)) return rc;
     OPT_PTR(idx, "idx"); REQ_PTR(s->theta, "state.theta");
     return finish(fn, risvec::launch_random_phase(*s, idx, seed, counter, (hipStream_t)stream));
 }
@@ -370,7 +384,6 @@ int risvec_step(const RisVecState* s, const RisVecParams* p, const float* action
                 const int32_t* n_groups, const int32_t* arrivals, uint64_t seed, uint32_t counter,
                 uint32_t flags, risvec_stream_t stream) {
     const char* fn = "risvec_step";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, false)) return rc;
     if (flags & RISVEC_STEP_THETA_BY_INDEX)
@@ -382,7 +395,6 @@ int risvec_step(const RisVecState* s, const RisVecParams* p, const float* action
 int risvec_data_rate(const RisVecState* s, const RisVecParams* p, const float* p_off, const int32_t* partner,
                      const int32_t* n_groups, float* rate_out, risvec_stream_t stream) {
     const char* fn = "risvec_data_rate";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     REQ_PTR(p_off, "p_off"); REQ_PTR(partner, "partner"); REQ_PTR(n_groups, "n_groups");
     REQ_PTR(rate_out, "rate_out"); REQ_PTR(s->gain, "state.gain");
@@ -393,7 +405,6 @@ int risvec_step_fused(const RisVecState* s, const RisVecParams* p, const float* 
                       const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals,
                       uint64_t seed, uint32_t counter, uint32_t flags, risvec_stream_t stream) {
     const char* fn = "risvec_step_fused";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, true)) return rc;
     if (flags & RISVEC_STEP_THETA_BY_INDEX) {                  // theta as the last sweep's candidate indices (no sweep here)
@@ -410,15 +421,12 @@ int risvec_step_fused_multi(const RisVecState* s, const RisVecParams* p, int32_t
                             const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals, uint64_t seed,
                             uint32_t counter, uint32_t flags, const RisVecTraj* traj, risvec_stream_t stream) {
     const char* fn = "risvec_step_fused_multi";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
-    if (n_steps < 1 || n_steps > (1 << 20)) return fail(RISVEC_ERR_ARG, "%s: n_steps=%d outside [1, 2^20]", fn, n_steps);
-    if (flags & (RISVEC_STEP_REUSE_COLSUM | RISVEC_STEP_REUSE_SSUM | RISVEC_STEP_REUSE_IDX | RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX))
-        return fail(RISVEC_ERR_ARG, "%s: the BCD / steering flags (0x%x) are not accepted by the multi-step launch", fn, flags);
-    if (int rc = check_step(fn, s, actions, partner, n_groups, arrivals, flags, true)) return rc;
-    if (traj) { OPT_PTR(traj->reward, "traj.reward"); OPT_PTR(traj->obs, "traj.obs"); OPT_PTR(traj->metrics, "traj.metrics"); }
+    RisVecTraj tj;
+    if (int rc = check_step(fn, s, actions, partner, n_groups, arrivals, flags, true, n_steps, traj, &tj)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const risvec::StepArgs a = risvec::make_step_args(*s, actions, partner, n_groups, arrivals, seed, counter, flags);
+    // `traj`, not `tj`: this kernel writes an obs record even without RISVEC_STEP_OBS (the other T-step paths drop it); kept as is
     const hipError_t err = risvec::launch_step_fused_multi(*s, *p, a, n_steps, traj, st);
     if (err != hipErrorNotSupported) return finish(fn, err);
     // Shapes without a compile-time fused kernel: step 0 through the single fused launch (gains computed and stored, its
@@ -427,24 +435,18 @@ int risvec_step_fused_multi(const RisVecState* s, const RisVecParams* p, int32_t
     const long long ev = (long long)s->n_envs * s->n_veh;
     const hipError_t e1 = risvec::launch_step(*s, *p, actions, partner, n_groups, arrivals, seed, counter, flags, true, st);
     if (e1 != hipSuccess) return finish(fn, e1);
-    if (traj) {
-        hipError_t e2 = hipSuccess;
-        if (traj->reward) e2 = hipMemcpyAsync(traj->reward, s->reward, ev * 4, hipMemcpyDeviceToDevice, st);
-        if (e2 == hipSuccess && traj->obs && (flags & RISVEC_STEP_OBS))
-            e2 = hipMemcpyAsync(traj->obs, s->obs, ev * 20, hipMemcpyDeviceToDevice, st);
-        if (e2 == hipSuccess && traj->metrics)
-            e2 = hipMemcpyAsync(traj->metrics, s->metrics, (size_t)s->n_envs * RISVEC_METRICS * 4, hipMemcpyDeviceToDevice, st);
-        if (e2 != hipSuccess) return finish(fn, e2);
-    }
+    hipError_t e2 = hipSuccess;
+    if (tj.reward) e2 = hipMemcpyAsync(tj.reward, s->reward, ev * 4, hipMemcpyDeviceToDevice, st);
+    if (e2 == hipSuccess && tj.obs) e2 = hipMemcpyAsync(tj.obs, s->obs, ev * 20, hipMemcpyDeviceToDevice, st);
+    if (e2 == hipSuccess && tj.metrics)
+        e2 = hipMemcpyAsync(tj.metrics, s->metrics, (size_t)s->n_envs * RISVEC_METRICS * 4, hipMemcpyDeviceToDevice, st);
+    if (e2 != hipSuccess) return finish(fn, e2);
     if (n_steps == 1) return RISVEC_OK;
     const risvec::StepArgs rest = risvec::make_step_args(*s, actions + 2 * ev, partner, n_groups,
                                                          arrivals ? arrivals + ev : nullptr, seed, counter + 1u, flags);
-    RisVecTraj tj{nullptr, nullptr, nullptr};
-    if (traj) {
-        tj.reward = traj->reward ? traj->reward + ev : nullptr;
-        tj.obs = (traj->obs && (flags & RISVEC_STEP_OBS)) ? traj->obs + ev * 5 : nullptr;
-        tj.metrics = traj->metrics ? traj->metrics + (long long)s->n_envs * RISVEC_METRICS : nullptr;
-    }
+    if (tj.reward) tj.reward += ev;
+    if (tj.obs) tj.obs += ev * 5;
+    if (tj.metrics) tj.metrics += (long long)s->n_envs * RISVEC_METRICS;
     return finish(fn, risvec::launch_step_multi(*s, *p, rest, n_steps - 1, &tj, st));
 }
 
@@ -452,19 +454,10 @@ int risvec_step_multi(const RisVecState* s, const RisVecParams* p, int32_t n_ste
                       const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals, uint64_t seed,
                       uint32_t counter, uint32_t flags, const RisVecTraj* traj, risvec_stream_t stream) {
     const char* fn = "risvec_step_multi";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
-    if (n_steps < 1 || n_steps > (1 << 20)) return fail(RISVEC_ERR_ARG, "%s: n_steps=%d outside [1, 2^20]", fn, n_steps);
-    if (flags & (RISVEC_STEP_REUSE_COLSUM | RISVEC_STEP_REUSE_SSUM | RISVEC_STEP_REUSE_IDX | RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX))
-        return fail(RISVEC_ERR_ARG, "%s: the BCD / steering flags (0x%x) are not accepted by the multi-step launch", fn, flags);
-    if (int rc = check_step(fn, s, actions, partner, n_groups, arrivals, flags, false)) return rc;
-    if (traj) { OPT_PTR(traj->reward, "traj.reward"); OPT_PTR(traj->obs, "traj.obs"); OPT_PTR(traj->metrics, "traj.metrics"); }
+    RisVecTraj tj;
+    if (int rc = check_step(fn, s, actions, partner, n_groups, arrivals, flags, false, n_steps, traj, &tj)) return rc;
     const risvec::StepArgs a = risvec::make_step_args(*s, actions, partner, n_groups, arrivals, seed, counter, flags);
-    RisVecTraj tj{nullptr, nullptr, nullptr};
-    if (traj) {
-        tj = *traj;
-        if (!(flags & RISVEC_STEP_OBS)) tj.obs = nullptr;      // obs records need the obs flag, as in the fused form
-    }
     return finish(fn, risvec::launch_step_multi(*s, *p, a, n_steps, &tj, (hipStream_t)stream));
 }
 
@@ -476,7 +469,7 @@ int risvec_sarl_step(const RisVecState* s, const RisVecSarlParams* p, const floa
     if (p->abi_version != RISVEC_ABI_VERSION || p->struct_bytes != sizeof(RisVecSarlParams))
         return fail(RISVEC_ERR_ARG, "%s: RisVecSarlParams ABI mismatch (version %u/%u, bytes %u/%zu)", fn,
                     p->abi_version, (unsigned)RISVEC_ABI_VERSION, p->struct_bytes, sizeof(RisVecSarlParams));
-    if (int rc = check_common(fn, s, nullptr)) return rc;
+    if (int rc = check_common(fn, s, nullptr, false)) return rc;
     REQ_PTR(action_power, "action_power"); OPT_PTR(action_phase, "action_phase"); OPT_PTR(arrivals, "arrivals");
     REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->b, "state.b"); REQ_PTR(s->pl, "state.pl");
     REQ_PTR(s->gain, "state.gain"); REQ_PTR(s->data_buf, "state.data_buf"); REQ_PTR(s->rate, "state.rate");
@@ -493,7 +486,6 @@ int risvec_step_fused_bcd(const RisVecState* s, const RisVecParams* p, const flo
                           const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals,
                           uint64_t seed, uint32_t counter, uint32_t flags, risvec_stream_t stream) {
     const char* fn = "risvec_step_fused_bcd";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
     if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, true)) return rc;
     REQ_PTR(s->c_col, "state.c_col");
@@ -517,9 +509,8 @@ int risvec_step_ring(const RisVecState* s, const RisVecParams* p, const RisVecSt
                      const int32_t* partner, const int32_t* n_groups, const int32_t* arrivals, uint64_t seed,
                      uint32_t counter, uint32_t flags, int32_t fused, risvec_stream_t stream) {
     const char* fn = "risvec_step_ring";
-    if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
-    if (!ring) return fail(RISVEC_ERR_ARG, "%s: ring is NULL", fn);
     if (int rc = check_common(fn, s, p)) return rc;
+    if (!ring) return fail(RISVEC_ERR_ARG, "%s: ring is NULL", fn);
     if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, fused != 0)) return rc;
     risvec::StepRing r;
     if (int rc = check_ring(fn, s, ring, flags, &r)) return rc;
@@ -554,14 +545,8 @@ int risvec_step_fused_3gpp_multi(const RisVecState* s, const RisVecParams* p, in
                                  const int32_t* arrivals, const RisVecFading* fading, uint64_t seed, uint32_t counter,
                                  uint32_t chan_counter, const RisVecTraj* traj, uint32_t flags, risvec_stream_t stream) {
     const char* fn = "risvec_step_fused_3gpp_multi";
-    if (int rc = check_step_3gpp(fn, s, p, model, actions, partner, n_groups, arrivals, fading, flags)) return rc;
-    if (n_steps < 1 || n_steps > (1 << 20)) return fail(RISVEC_ERR_ARG, "%s: n_steps=%d outside [1, 2^20]", fn, n_steps);
-    RisVecTraj tj{nullptr, nullptr, nullptr};
-    if (traj) {
-        OPT_PTR(traj->reward, "traj.reward"); OPT_PTR(traj->obs, "traj.obs"); OPT_PTR(traj->metrics, "traj.metrics");
-        tj = *traj;
-        if (!(flags & RISVEC_STEP_OBS)) tj.obs = nullptr;      // obs records need the obs flag, as in risvec_step_multi
-    }
+    RisVecTraj tj;
+    if (int rc = check_step_3gpp(fn, s, p, model, actions, partner, n_groups, arrivals, fading, flags, n_steps, traj, &tj)) return rc;
     const risvec::StepArgs a = risvec::make_step_args(*s, actions, partner, n_groups, arrivals, seed, counter, flags);
     const hipError_t err = risvec::launch_step_3gpp(*s, *p, a, chan_3gpp(s, model, fading, chan_counter),
                                                     RISVEC_FORM_FUSED_MULTI, n_steps, tj, (hipStream_t)stream);

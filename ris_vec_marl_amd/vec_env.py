@@ -473,30 +473,48 @@ class VecEnviron(ParamAttrs):
                              "(call compute_parms(); h_r written by hand has no steering base)")
         return N.STEP_STEER
 
-    def _model_3gpp(self) -> Optional[int]:
-        """RISVEC_CH_* of `channel_model` when the gain is NOT the RIS cascade ("free"), else None: what
-        `update_channel_gains` dispatches on (unknown keywords: CH_OTHER, a 0 dB path loss)."""
-        model = str(self.params.channel_model)
-        return None if model == "free" else CHANNEL_MODELS.get(model, N.CH_OTHER)
+    @staticmethod
+    def _step_flags(metrics: bool, power_w: bool, obs: bool, policy_action: bool) -> int:
+        return ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
+                | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0))
 
-    def _fading(self, fading, shape, bound: bool, fused: bool):
+    def _model(self, fused: bool, steer: bool, fading) -> Optional[int]:
+        """Which kind of launch a step call is NOW (`params.channel_model` may change between calls): RISVEC_CH_* when a
+        fused form updates the 3GPP gains (what `update_channel_gains` dispatches on; unknown keywords: CH_OTHER, a
+        0 dB path loss), None for a RIS-cascade / cached-gain launch.  Each kind refuses what the other owns."""
+        model = str(self.params.channel_model)
+        if fused and model != "free":
+            if steer:
+                raise ValueError("steer=True is a form of the RIS cascade; channel_model=%r has no RIS in the gain"
+                                 % (model,))
+            return CHANNEL_MODELS.get(model, N.CH_OTHER)
+        if fading is not None:
+            raise ValueError("fading= is accepted by the fused step forms under a 3GPP channel_model only "
+                             "(channel_model=%r)" % (model,))
+        return None
+
+    @staticmethod
+    def _fading(conv, fading, shape):
         """Injected fading draws (u_los, z_shadow, small) of a fused 3GPP step -> (tensors, RisVecFading or None)."""
         if fading is None:
             return None, None
-        if not fused or self._model_3gpp() is None:
-            raise ValueError("fading= is accepted by the fused step forms under a 3GPP channel_model only (channel_model=%r)"
-                             % (self.params.channel_model,))
         if len(fading) != 3 or any(x is None for x in fading):
             raise ValueError("fading must be (u_los, z_shadow, small), all three given")
-        conv = self._bound if bound else self._arg
         ts = tuple(conv(x, torch.float32, shape, n) for x, n in zip(fading, ("u_los", "z_shadow", "small")))
         return ts, N.RisVecFading(*(_dev_ptr(x) for x in ts))
 
-    def _no_steer_3gpp(self, steer: bool) -> None:
-        if steer:
-            raise ValueError("steer=True is a form of the RIS cascade; channel_model=%r has no RIS in the gain"
-                             % (self.params.channel_model,))
+    def _theta_mode(self, flags: int, fused: bool, bcd: bool, steer: bool) -> int:
+        """Decide how a step gets at theta: by index (flag added) where lazy_theta allows, else make sure the complex64
+        tensor is current for the kernels that read it."""
+        if self._by_index(fused, steer) and (not bcd or bool(flags & N.STEP_REUSE_IDX)):
+            return flags | N.STEP_THETA_BY_INDEX
+        if fused:
+            self._sync_theta()
+        return flags
 
+    # Every step call has ONE implementation, `_bind_*(conv, ...)`: validate, marshal once, return the launcher.  `conv`
+    # is the whole difference between the public twins: `bind_*` passes `_bound` (inputs used in place or refused), the
+    # unbound method passes `_arg` (converted, copied if needed) and calls the launcher once.
     def step(self, action_power, partner, n_groups, arrivals=None, fused: bool = False, bcd: bool = False,
              metrics: bool = True, power_w: bool = True, obs: bool = True, policy_action: bool = False,
              steer: bool = False, fading=None) -> Tuple[torch.Tensor, ...]:
@@ -516,55 +534,78 @@ class VecEnviron(ParamAttrs):
         Returns the reference's 7-tuple, batched:
         (per_user_reward [E,V], global_reward [E], DataBuf, data_t, data_p, over_power, over_data);
         the tensors are owned by the env and overwritten by the next step."""
-        self._ensure_device()
-        E, V = self.n_envs, self.n_veh
-        a = self._arg(action_power, torch.float32, (E, V, 2) if policy_action else (E, 2, V), "action_power")
-        pt = self._arg(partner, torch.int32, (E, V), "partner")
-        ng = self._arg(n_groups, torch.int32, (E,), "n_groups")
-        ar = self._arg(arrivals, torch.int32, (E, V), "arrivals")
-        model = self._model_3gpp()
-        fd_t, fd = self._fading(fading, (E, V), False, fused or bcd)
-        if model is not None and (fused or bcd):
-            self._no_steer_3gpp(steer)
-            if bcd:
-                self.optimize_phase_shift()
-            flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
-                     | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0))
-            self._chan += 1
-            N.check(N.load().risvec_step_fused_3gpp(C.byref(self._cstate), C.byref(self._p()), model, _dev_ptr(a),
-                                                    _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar),
-                                                    C.byref(fd) if fd is not None else None, self.seed, self._steps,
-                                                    self._chan, flags, None, self._stream()))
-            self._steps += 1
-            self._obs_stale = not obs
-            t = self._t
-            return (t["reward"], t["metrics"][:, 0], t["data_buf"], t["data_t"], t["data_p"], t["over_power"],
-                    t["over_data"])
-        flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
-                 | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0)
-                 | (self._bcd_flags(None, step=True) if bcd else 0) | self._steer_flag(steer, fused or bcd))
-        flags = self._theta_mode(flags, fused or bcd, bcd, steer)
-        lib = N.load()
-        fn = lib.risvec_step_fused_bcd if bcd else (lib.risvec_step_fused if fused else lib.risvec_step)
-        N.check(fn(C.byref(self._cstate), C.byref(self._p()), _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng),
-                   _dev_ptr(ar), self.seed, self._steps, flags, self._stream()))
-        if bcd:
-            self._bcd_done(flags, step=True)
-            self._mark_theta_stale(bool(flags & N.STEP_THETA_BY_INDEX))
-        self._steps += 1
-        self._obs_stale = not obs
+        self._bind_step(self._arg, action_power, partner, n_groups, arrivals, fused, bcd, metrics, power_w, obs,
+                        policy_action, steer, fading)()
         t = self._t
         return (t["reward"], t["metrics"][:, 0], t["data_buf"], t["data_t"], t["data_p"], t["over_power"],
                 t["over_data"])
 
-    def _theta_mode(self, flags: int, fused: bool, bcd: bool, steer: bool) -> int:
-        """Decide how a step gets at theta: by index (flag added) where lazy_theta allows, else make sure the complex64
-        tensor is current for the kernels that read it."""
-        if self._by_index(fused, steer) and (not bcd or bool(flags & N.STEP_REUSE_IDX)):
-            return flags | N.STEP_THETA_BY_INDEX
-        if fused:
-            self._sync_theta()
-        return flags
+    def bind_step(self, action_power, partner, n_groups, arrivals=None, fused: bool = False, bcd: bool = False,
+                  metrics: bool = True, power_w: bool = True, obs: bool = True, policy_action: bool = False,
+                  steer: bool = False, fading=None):
+        """Validate and marshal a `step()` call ONCE and return a zero-argument callable that
+        launches one step per call on the stream current at bind time, reading the SAME input
+        tensors each time (update them in place between calls).  Cuts the per-step host cost
+        from ~10 us of Python argument handling to one ctypes call, which matters when a
+        batched step is only a few microseconds of GPU time (small E)."""
+        # the launcher reads these tensors IN PLACE on every call, so they must already be what the
+        # kernel reads: a silent .to()/.contiguous() copy would detach the caller's later updates
+        return self._bind_step(self._bound, action_power, partner, n_groups, arrivals, fused, bcd, metrics, power_w, obs,
+                               policy_action, steer, fading)
+
+    def _bind_step(self, conv, action_power, partner, n_groups, arrivals, fused, bcd, metrics, power_w, obs,
+                   policy_action, steer, fading):
+        self._ensure_device()
+        E, V = self.n_envs, self.n_veh
+        a = conv(action_power, torch.float32, (E, V, 2) if policy_action else (E, 2, V), "action_power")
+        pt = conv(partner, torch.int32, (E, V), "partner")
+        ng = conv(n_groups, torch.int32, (E,), "n_groups")
+        ar = conv(arrivals, torch.int32, (E, V), "arrivals")
+        fused = fused or bcd                           # a sweep only exists in front of the fused step
+        fd_t, fd = self._fading(conv, fading, (E, V))
+        self._model(fused, steer, fd)                  # refuse now what every launch would refuse
+        flags3 = self._step_flags(metrics, power_w, obs, policy_action)
+        base_flags = flags3 | self._steer_flag(steer, fused)
+        lib = N.load()
+        fn = lib.risvec_step_fused_bcd if bcd else (lib.risvec_step_fused if fused else lib.risvec_step)
+        fn3 = lib.risvec_step_fused_3gpp
+        cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
+        pa, pp, pn, par = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar)
+        pfd = C.byref(fd) if fd is not None else None
+
+        def launch() -> None:
+            model = self._model(fused, steer, fd) if fused else None
+            if model is not None:            # the fused forms under a 3GPP channel model (the RIS is not in the gain)
+                if bcd:
+                    self.optimize_phase_shift()
+                self._chan += 1
+                rc = fn3(cs, C.byref(self._p()), model, pa, pp, pn, par, pfd, seed, self._steps, self._chan, flags3, None,
+                         stream)
+                if rc:
+                    N.check(rc)
+            else:
+                flags = base_flags | (self._bcd_flags(None, step=True) if bcd else 0)
+                if self.lazy_theta or self._theta_stale:       # otherwise theta is the tensor, and current
+                    flags = self._theta_mode(flags, fused, bcd, steer)
+                rc = fn(cs, C.byref(self._p()), pa, pp, pn, par, seed, self._steps, flags, stream)
+                if rc:
+                    N.check(rc)
+                if bcd:
+                    self._bcd_done(flags, step=True)
+                    self._mark_theta_stale(bool(flags & N.STEP_THETA_BY_INDEX))
+            self._steps += 1
+            self._obs_stale = not obs
+
+        launch.inputs = (a, pt, ng, ar, fd_t, fd)      # the closure owns the marshalled tensors
+        return launch
+
+    def _traj_shapes(self, actions) -> Tuple[int, Dict[str, tuple]]:
+        """(T, shapes of the per-step records) of a T-step call on `actions` [T,E,...]."""
+        shape = np.shape(actions)
+        if len(shape) != 4 or shape[0] < 1:
+            raise ValueError("actions must be a [T, E, ...] array holding at least one step, got shape %s" % (tuple(shape),))
+        T, E, V = int(shape[0]), self.n_envs, self.n_veh
+        return T, {"reward": (T, E, V), "obs": (T, E, V, 5), "metrics": (T, E, N.METRICS)}
 
     def step_many(self, actions, partner, n_groups, arrivals=None, metrics: bool = True, power_w: bool = False,
                   obs: bool = True, policy_action: bool = False, record: Sequence[str] = ("reward", "obs", "metrics"),
@@ -583,49 +624,17 @@ class VecEnviron(ParamAttrs):
         not read at all.  Under a 3GPP channel_model fused=True is `risvec_step_fused_3gpp_multi`: T fused 3GPP steps,
         fresh fading every step (fading=(u_los, z_shadow, small) [T,E,V] injects it)."""
         self._ensure_device()
-        model = self._model_3gpp() if fused else None
-        if fused and model is None:
-            self._sync_theta()
-        E, V = self.n_envs, self.n_veh
-        a = torch.as_tensor(actions)
-        if a.dim() != 4 or tuple(a.shape[1:]) != ((E, V, 2) if policy_action else (E, 2, V)):
-            raise ValueError("actions must have shape [T, %d, %s]" % (E, "%d, 2" % V if policy_action else "2, %d" % V))
-        T = int(a.shape[0])
-        if T < 1:
-            raise ValueError("actions holds no step")
-        a = a.to(device=self.device, dtype=torch.float32).contiguous()
-        pt = self._arg(partner, torch.int32, (E, V), "partner")
-        ng = self._arg(n_groups, torch.int32, (E,), "n_groups")
-        ar = self._arg(arrivals, torch.int32, (T, E, V), "arrivals")
-        shapes = {"reward": (T, E, V), "obs": (T, E, V, 5), "metrics": (T, E, N.METRICS)}
+        shapes = self._traj_shapes(actions)[1]
         rec: Dict[str, torch.Tensor] = {}
         for k in record:
             if k not in shapes:
                 raise ValueError("record: unknown trajectory record %r (choose from %s)" % (k, sorted(shapes)))
-            if k == "obs" and not obs:
-                raise ValueError("record 'obs' needs obs=True")
             if out is not None and k in out:
-                rec[k] = self._bound(out[k], torch.float32, shapes[k], "out[%r]" % k)
+                rec[k] = out[k]
             else:
                 rec[k] = torch.empty(shapes[k], dtype=torch.float32, device=self.device)
-        tj = N.RisVecTraj(_dev_ptr(rec.get("reward")), _dev_ptr(rec.get("obs")), _dev_ptr(rec.get("metrics")))
-        flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
-                 | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0))
-        fd_t, fd = self._fading(fading, (T, E, V), False, fused)
-        if model is not None:
-            N.check(N.load().risvec_step_fused_3gpp_multi(
-                C.byref(self._cstate), C.byref(self._p()), model, T, _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng),
-                _dev_ptr(ar), C.byref(fd) if fd is not None else None, self.seed, self._steps, self._chan + 1,
-                C.byref(tj), flags, self._stream()))
-            self._chan += T
-            self._steps += T
-            self._obs_stale = not obs
-            return rec
-        fn = N.load().risvec_step_fused_multi if fused else N.load().risvec_step_multi
-        N.check(fn(C.byref(self._cstate), C.byref(self._p()), T, _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar),
-                   self.seed, self._steps, flags, C.byref(tj), self._stream()))
-        self._steps += T
-        self._obs_stale = not obs
+        self._bind_step_many(self._arg, actions, partner, n_groups, arrivals, metrics, power_w, obs, policy_action, rec,
+                             fused, fading)()
         return rec
 
     def bind_step_many(self, actions: torch.Tensor, partner: torch.Tensor, n_groups: torch.Tensor,
@@ -635,38 +644,42 @@ class VecEnviron(ParamAttrs):
         """`step_many` validated and marshalled once: returns a zero-argument launcher that advances the env by
         T steps per call, reading `actions` [T,E,...] (and `arrivals`) in place and writing the per-step records
         into `out`'s tensors ("reward" [T,E,V], "obs" [T,E,V,5], "metrics" [T,E,16]; any subset)."""
+        return self._bind_step_many(self._bound, actions, partner, n_groups, arrivals, metrics, power_w, obs,
+                                    policy_action, out, fused, fading)
+
+    def _bind_step_many(self, conv, actions, partner, n_groups, arrivals, metrics, power_w, obs, policy_action, out,
+                        fused, fading):
         self._ensure_device()
         E, V = self.n_envs, self.n_veh
-        if not isinstance(actions, torch.Tensor) or actions.dim() != 4:
-            raise ValueError("actions must be a [T, E, ...] device tensor")
-        T = int(actions.shape[0])
-        a = self._bound(actions, torch.float32, (T, E, V, 2) if policy_action else (T, E, 2, V), "actions")
-        pt = self._bound(partner, torch.int32, (E, V), "partner")
-        ng = self._bound(n_groups, torch.int32, (E,), "n_groups")
-        ar = self._bound(arrivals, torch.int32, (T, E, V), "arrivals")
-        shapes = {"reward": (T, E, V), "obs": (T, E, V, 5), "metrics": (T, E, N.METRICS)}
+        T, shapes = self._traj_shapes(actions)
+        a = conv(actions, torch.float32, (T, E, V, 2) if policy_action else (T, E, 2, V), "actions")
+        pt = conv(partner, torch.int32, (E, V), "partner")
+        ng = conv(n_groups, torch.int32, (E,), "n_groups")
+        ar = conv(arrivals, torch.int32, (T, E, V), "arrivals")
+        if not obs and "obs" in (out or {}):
+            raise ValueError("record 'obs' needs obs=True")
+        # the records are written in place whoever asks: never converted
         rec = {k: self._bound(t, torch.float32, shapes[k], "out[%r]" % k) for k, t in (out or {}).items()}
         tj = N.RisVecTraj(_dev_ptr(rec.get("reward")), _dev_ptr(rec.get("obs")), _dev_ptr(rec.get("metrics")))
-        flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
-                 | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0))
+        fd_t, fd = self._fading(conv, fading, (T, E, V))
+        self._model(fused, False, fd)                  # refuse now what every launch would refuse
+        flags = self._step_flags(metrics, power_w, obs, policy_action)
         fn = N.load().risvec_step_fused_multi if fused else N.load().risvec_step_multi
         fn3 = N.load().risvec_step_fused_3gpp_multi
         cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
         pa, pp, pn, par, ptj = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar), C.byref(tj)
-        fd_t, fd = self._fading(fading, (T, E, V), True, fused)
         pfd = C.byref(fd) if fd is not None else None
 
         def launch() -> None:
-            model = self._model_3gpp() if fused else None
+            model = self._model(fused, False, fd) if fused else None
             if model is not None:            # the fused form under a 3GPP channel model (the RIS is not in the gain)
+                # handed the FIRST channel counter of its T draws; the single step advances before its call
                 rc = fn3(cs, C.byref(self._p()), model, T, pa, pp, pn, par, pfd, seed, self._steps, self._chan + 1, ptj,
                          flags, stream)
                 if rc:
                     N.check(rc)
                 self._chan += T
             else:
-                if pfd is not None:
-                    raise ValueError("fading= is accepted under a 3GPP channel_model only")
                 if fused:
                     self._sync_theta()
                 rc = fn(cs, C.byref(self._p()), T, pa, pp, pn, par, seed, self._steps, flags, ptj, stream)
@@ -685,21 +698,7 @@ class VecEnviron(ParamAttrs):
         action_power [E,2,V] float32 used as given, action_phase [E,M] radians (None keeps the
         current theta), arrivals [E,V] int32 injected Poisson draws (None: Philox).  Returns the
         reference's 6-tuple, batched: (Reward [E], DataBuf, data_t, data_p, over_power, over_data)."""
-        from .sarl import SarlParams
-        self._ensure_device()
-        E, V, M = self.n_envs, self.n_veh, self.M
-        a = self._arg(action_power, torch.float32, (E, 2, V), "action_power")
-        ph = self._arg(action_phase, torch.float32, (E, M), "action_phase")
-        ar = self._arg(arrivals, torch.int32, (E, V), "arrivals")
-        sp = (sarl_params or SarlParams()).to_c()
-        self._sync_theta()
-        N.check(N.load().risvec_sarl_step(C.byref(self._cstate), C.byref(sp), _dev_ptr(a), _dev_ptr(ph),
-                                          _dev_ptr(ar), self.seed, self._steps, N.STEP_OBS if obs else 0,
-                                          self._stream()))
-        if ph is not None:
-            self._theta_changed()
-        self._steps += 1
-        self._obs_stale = False        # sarl_observe assembles its own observation from the state tensors
+        self._bind_sarl_step(self._arg, action_power, action_phase, arrivals, sarl_params, obs)()
         t = self._t
         return (t["metrics"][:, 0], t["data_buf"], t["data_t"], t["data_p"], t["over_power"], t["over_data"])
 
@@ -708,12 +707,15 @@ class VecEnviron(ParamAttrs):
         """`sarl_step` validated and marshalled once: returns a zero-argument launcher that reads the SAME device
         tensors on every call (update them in place between calls).  The parameters are those of `sarl_params` at
         bind time."""
+        return self._bind_sarl_step(self._bound, action_power, action_phase, arrivals, sarl_params, obs)
+
+    def _bind_sarl_step(self, conv, action_power, action_phase, arrivals, sarl_params, obs):
         from .sarl import SarlParams
         self._ensure_device()
         E, V, M = self.n_envs, self.n_veh, self.M
-        a = self._bound(action_power, torch.float32, (E, 2, V), "action_power")
-        ph = self._bound(action_phase, torch.float32, (E, M), "action_phase")
-        ar = self._bound(arrivals, torch.int32, (E, V), "arrivals")
+        a = conv(action_power, torch.float32, (E, 2, V), "action_power")
+        ph = conv(action_phase, torch.float32, (E, M), "action_phase")
+        ar = conv(arrivals, torch.int32, (E, V), "arrivals")
         sp = (sarl_params or SarlParams()).to_c()
         fn, cs, psp, seed, stream = N.load().risvec_sarl_step, C.byref(self._cstate), C.byref(sp), C.c_uint64(self.seed), self._stream()
         pa, pph, par, flags = _dev_ptr(a), _dev_ptr(ph), _dev_ptr(ar), N.STEP_OBS if obs else 0
@@ -726,69 +728,9 @@ class VecEnviron(ParamAttrs):
             if ph is not None:
                 self._theta_changed()
             self._steps += 1
-            self._obs_stale = False
+            self._obs_stale = False        # sarl_observe assembles its own observation from the state tensors
 
         launch.inputs = (a, ph, ar, sp)
-        return launch
-
-    def bind_step(self, action_power, partner, n_groups, arrivals=None, fused: bool = False, bcd: bool = False,
-                  metrics: bool = True, power_w: bool = True, obs: bool = True, policy_action: bool = False,
-                  steer: bool = False, fading=None):
-        """Validate and marshal a `step()` call ONCE and return a zero-argument callable that
-        launches one step per call on the stream current at bind time, reading the SAME input
-        tensors each time (update them in place between calls).  Cuts the per-step host cost
-        from ~10 us of Python argument handling to one ctypes call, which matters when a
-        batched step is only a few microseconds of GPU time (small E)."""
-        self._ensure_device()
-        E, V = self.n_envs, self.n_veh
-        # the launcher reads these tensors IN PLACE on every call, so they must already be what the
-        # kernel reads: a silent .to()/.contiguous() copy would detach the caller's later updates
-        a = self._bound(action_power, torch.float32, (E, V, 2) if policy_action else (E, 2, V), "action_power")
-        pt = self._bound(partner, torch.int32, (E, V), "partner")
-        ng = self._bound(n_groups, torch.int32, (E,), "n_groups")
-        ar = self._bound(arrivals, torch.int32, (E, V), "arrivals")
-        base_flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0)
-                      | (N.STEP_OBS if obs else 0) | (N.STEP_POLICY_ACTION if policy_action else 0)
-                      | self._steer_flag(steer, fused or bcd))
-        lib = N.load()
-        fn = lib.risvec_step_fused_bcd if bcd else (lib.risvec_step_fused if fused else lib.risvec_step)
-        fn3 = lib.risvec_step_fused_3gpp
-        cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
-        pa, pp, pn, par = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar)
-        fd_t, fd = self._fading(fading, (E, V), True, fused or bcd)
-        pfd = C.byref(fd) if fd is not None else None
-        flags3 = base_flags & ~N.STEP_STEER
-        keep = (a, pt, ng, ar, fd_t, fd)           # the closure owns the marshalled tensors
-
-        def launch() -> None:
-            model = self._model_3gpp() if (fused or bcd) else None
-            if model is not None:            # the fused forms under a 3GPP channel model (the RIS is not in the gain)
-                self._no_steer_3gpp(steer)
-                if bcd:
-                    self.optimize_phase_shift()
-                self._chan += 1
-                rc = fn3(cs, C.byref(self._p()), model, pa, pp, pn, par, pfd, seed, self._steps, self._chan, flags3, None,
-                         stream)
-                if rc:
-                    N.check(rc)
-                self._steps += 1
-                self._obs_stale = not obs
-                return
-            if pfd is not None:
-                raise ValueError("fading= is accepted under a 3GPP channel_model only")
-            flags = base_flags | (self._bcd_flags(None, step=True) if bcd else 0)
-            if self.lazy_theta or self._theta_stale:
-                flags = self._theta_mode(flags, fused or bcd, bcd, steer)
-            rc = fn(cs, C.byref(self._p()), pa, pp, pn, par, seed, self._steps, flags, stream)
-            if rc:
-                N.check(rc)
-            if bcd:
-                self._bcd_done(flags, step=True)
-                self._mark_theta_stale(bool(flags & N.STEP_THETA_BY_INDEX))
-            self._steps += 1
-            self._obs_stale = not obs
-
-        launch.inputs = keep
         return launch
 
     def bind_step_store(self, replay, power_raw: torch.Tensor, partner: torch.Tensor, n_groups: torch.Tensor,
@@ -816,7 +758,9 @@ class VecEnviron(ParamAttrs):
         if replay.device != self.device or replay.n_agents != V or replay.input_shape != 5 or replay.n_actions != V + 2:
             raise ValueError("bind_step_store: the replay buffer must live on %s with n_agents=%d, input_shape=5, n_actions=%d"
                              % (self.device, V, V + 2))
-        flags = ((N.STEP_METRICS if metrics else 0) | (N.STEP_POWER_W if power_w else 0) | N.STEP_OBS | N.STEP_POLICY_ACTION)
+        fd_t, fd = self._fading(self._bound, fading, (E, V))
+        self._model(fused, False, fd)                  # refuse now what every launch would refuse
+        flags = self._step_flags(metrics, power_w, True, True)
         ring = N.RisVecStepRing()
         ring.rb = replay._c
         ring.probs, ring.mask = pr.data_ptr(), None
@@ -824,17 +768,12 @@ class VecEnviron(ParamAttrs):
         fn3 = N.load().risvec_step_fused_3gpp
         pa, pp, pn, par, pmask = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar), _dev_ptr(mk)
         fz = 1 if fused else 0
-        fd_t, fd = self._fading(fading, (E, V), True, fused)
         pfd = C.byref(fd) if fd is not None else None
 
         def launch(done: bool = False, use_mask: bool = True) -> None:
             if self._obs_stale:
                 self.observe()                   # the ring's `state` is the observation tensor as the kernel finds it
-            model = self._model_3gpp() if fused else None
-            if model is None and fused:
-                if pfd is not None:
-                    raise ValueError("fading= is accepted under a 3GPP channel_model only")
-                self._sync_theta()
+            model = self._model(fused, False, fd) if fused else None
             ring.mem_cntr, ring.done = replay.mem_cntr, 1 if done else 0
             ring.mask = pmask if use_mask else None
             if model is not None:                # fused under a 3GPP channel model: 3GPP gains + step + store
@@ -842,6 +781,8 @@ class VecEnviron(ParamAttrs):
                 rc = fn3(cs, C.byref(self._p()), model, pa, pp, pn, par, pfd, seed, self._steps, self._chan, flags,
                          C.byref(ring), stream)
             else:
+                if fused:
+                    self._sync_theta()
                 rc = fn(cs, C.byref(self._p()), C.byref(ring), pa, pp, pn, par, seed, self._steps, flags, fz, stream)
             if rc:
                 N.check(rc)

@@ -437,6 +437,9 @@ def test_multi_step_launch_options_and_errors():
         b.step_many(pol, pt, ngt, record=("rewards",))
     with pytest.raises(ValueError):
         b.step_many(np.zeros((0, E, 2, V), np.float32), pt, ngt)
+    with pytest.raises(ValueError):          # the bound twin refuses an obs record without obs=True, as step_many does
+        b.bind_step_many(torch.zeros(T, E, 2, V, device="cuda:0"), torch.as_tensor(pt).cuda(), torch.as_tensor(ngt).cuda(),
+                         obs=False, out={"obs": torch.empty(T, E, V, 5, device="cuda:0")})
     import ctypes as C
     from ris_vec_marl_amd import _native as N
     lib = N.load()
