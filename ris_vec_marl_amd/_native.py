@@ -9,6 +9,8 @@ import contextlib
 import ctypes as C
 import os
 
+import torch
+
 ABI_VERSION = 17
 POISSON_TABLE = 64
 MAX_LANES = 8
@@ -258,11 +260,54 @@ def resolve_device(device):
     `tensor.device == self.device` holds for tensors the object allocates itself: torch compares
     `cuda` and `cuda:0` as different devices.  Without a HIP device the argument is returned as
     given (the compute calls raise later: there is no CPU fallback)."""
-    import torch
     d = torch.device(device if device is not None else "cuda")
     if d.type == "cuda" and d.index is None and torch.cuda.is_available():
         d = torch.device("cuda", torch.cuda.current_device())
     return d
+
+
+# What every module does at the boundary to the C ABI.  `converted` and `in_place` are the two rules an input of a
+# launcher is taken by -- the whole difference between an unbound method (inputs converted, copied if needed) and its
+# `bind_*` twin (inputs read in place on every call, so used as they are or refused).
+def require_hip(device) -> None:
+    if device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("ris_vec_marl_amd needs a HIP device; there is no CPU fallback")
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def stream(device) -> int:
+    """Handle of the stream current on `device`."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def converted(x, dtype, shape, name, device):
+    if x is None:
+        return None
+    tt = torch.as_tensor(x)
+    if tuple(tt.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(tt.shape)))
+    return tt.to(device=device, dtype=dtype).contiguous()
+
+
+def in_place(x, dtype, shape, name, device):
+    """An input of a pre-marshalled launcher: used as is or refused, never copied."""
+    if x is None:
+        return None
+    if (not isinstance(x, torch.Tensor) or x.dtype != dtype or x.device != device or not x.is_contiguous()
+            or tuple(x.shape) != tuple(shape)):
+        raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (bound launchers read their inputs "
+                         "in place; convert it once before binding)" % (name, dtype, tuple(shape), device))
+    return x
+
+
+def mask_u8(mask):
+    """A NOMA / action mask as the kernels read it: uint8, nonzero = allowed (bool and float masks are converted)."""
+    if mask is None or mask.dtype == torch.uint8:
+        return mask
+    return (mask != 0).to(torch.uint8)
 
 
 def last_kernel() -> str:

@@ -66,6 +66,26 @@ def encode_noma_groups(groups_per_env: Sequence[Sequence[Sequence[int]]], n_veh:
     return partner, n_groups
 
 
+class Staging:
+    """The inputs of a one-env step on their way to the device in ONE copy: named sections of 32-bit words, each 16-byte
+    aligned (the C ABI wants aligned pointers), in a pinned host buffer and its device mirror.  `host[name]` is the flat
+    NumPy view to fill, `dev[name]` the typed tensor view a bound launcher reads, `upload()` the copy."""
+
+    def __init__(self, device, sections):
+        """sections: (name, words, torch.float32 or torch.int32, shape of the device view), laid out in this order."""
+        offs, n = {}, 0
+        for name, words, _, _ in sections:
+            offs[name] = n
+            n += (words + 3) // 4 * 4
+        self._host = torch.zeros(n, dtype=torch.int32).pin_memory()
+        self._dev = torch.zeros(n, dtype=torch.int32, device=device)
+        self.host = {name: self._host[offs[name]:offs[name] + w].view(dt).numpy() for name, w, dt, _ in sections}
+        self.dev = {name: self._dev[offs[name]:offs[name] + w].view(dt).view(shape) for name, w, dt, shape in sections}
+
+    def upload(self) -> None:
+        self._dev.copy_(self._host, non_blocking=True)
+
+
 class Vehicle:
     """Environment.py:45-53."""
 
@@ -104,7 +124,7 @@ class Environ(ParamAttrs):
         self.last_mec_queue_cycles = 0.0
         self._n_vehicles = 0
         self._cache = {}
-        self._stage = None       # step(): pinned host words, their device mirror and the two pre-bound launchers
+        self._stage = None       # step(): (Staging, launcher, launcher with injected arrivals)
 
     # ---------------------------------------------------------------- host <-> device plumbing
     def _host(self, key: str) -> np.ndarray:
@@ -290,37 +310,31 @@ class Environ(ParamAttrs):
                 self._host("over_power"), self.over_data)
 
     def _step_launch(self, a: np.ndarray, partner: np.ndarray, ng: int, arrivals) -> None:
-        """One env, one step: the inputs go to the device in ONE copy (a pinned staging buffer of 32-bit words:
-        action | partner | n_groups | arrivals) and the launch is pre-bound -- the per-call cost of the facade is what
-        a script that swaps `Environment` for this module pays on every step."""
+        """One env, one step: the inputs go to the device in ONE copy (`Staging`: action | partner | n_groups | arrivals)
+        and the launch is pre-bound -- the per-call cost of the facade is what a script that swaps `Environment` for
+        this module pays on every step."""
         V, vec = self.n_veh, self._vec
         if self._stage is None:
             vec._ensure_device()
-            up4 = lambda n: (n + 3) // 4 * 4                   # noqa: E731  (the C ABI wants 16-byte aligned pointers)
-            o_p = up4(2 * V)
-            o_g = o_p + up4(V)
-            o_r = o_g + 4
-            host = torch.zeros(o_r + up4(V), dtype=torch.int32).pin_memory()
-            dev = torch.zeros(o_r + up4(V), dtype=torch.int32, device=vec.device)
-            hn = host.numpy()
-            views = dict(a=hn[:2 * V].view(np.float32), p=hn[o_p:o_p + V], g=hn[o_g:o_g + 1], r=hn[o_r:o_r + V])
-            d_a = dev[:2 * V].view(torch.float32).view(1, 2, V)
-            d_p, d_g, d_r = dev[o_p:o_p + V].view(1, V), dev[o_g:o_g + 1], dev[o_r:o_r + V].view(1, V)
-            self._stage = dict(host=host, dev=dev, views=views,
-                               plain=vec.bind_step(d_a, d_p, d_g, None, fused=False),
-                               injected=vec.bind_step(d_a, d_p, d_g, d_r, fused=False))
-        st = self._stage
-        v = st["views"]
-        v["a"][:] = a.reshape(-1)
-        v["p"][:] = partner
-        v["g"][0] = ng
+            st = Staging(vec.device, (("a", 2 * V, torch.float32, (1, 2, V)), ("p", V, torch.int32, (1, V)),
+                                      ("g", 1, torch.int32, (1,)), ("r", V, torch.int32, (1, V))))
+            d = st.dev
+            self._stage = (st, vec.bind_step(d["a"], d["p"], d["g"], None, fused=False),
+                           vec.bind_step(d["a"], d["p"], d["g"], d["r"], fused=False))
+        st, plain, injected = self._stage
+        st.host["a"][:] = a.reshape(-1)
+        st.host["p"][:] = partner
+        st.host["g"][0] = ng
         if arrivals is not None:
-            arr = np.asarray(arrivals)
-            if arr.shape != (V,):
-                raise ValueError("arrivals must have shape [n_veh]")
-            v["r"][:] = arr
-        st["dev"].copy_(st["host"], non_blocking=True)
-        st["injected" if arrivals is not None else "plain"]()
+            st.host["r"][:] = self._arrivals(arrivals)
+        st.upload()
+        (plain if arrivals is None else injected)()
+
+    def _arrivals(self, arrivals) -> np.ndarray:
+        arr = np.asarray(arrivals)
+        if arr.shape != (self.n_veh,):
+            raise ValueError("arrivals must have shape [n_veh]")
+        return arr
 
     # dead code on the MARL path (Environment.py:192-201, 544-545); never called by the driver
     def get_path_loss(self, position_A):

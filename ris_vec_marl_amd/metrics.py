@@ -55,8 +55,7 @@ class EpisodeMeter:
         if env is not None:
             n_envs, n_veh, device = env.n_envs, env.n_veh, env.device
         self.device = N.resolve_device(device)
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("ris_vec_marl_amd needs a HIP device; there is no CPU fallback")
+        N.require_hip(self.device)
         self.n_envs, self.n_veh, self.user_clip = int(n_envs), int(n_veh), float(user_clip)
         if self.n_envs < 1 or not 1 <= self.n_veh <= N.MAX_VEH:
             raise ValueError("EpisodeMeter: n_envs=%d n_veh=%d" % (self.n_envs, self.n_veh))
@@ -69,22 +68,17 @@ class EpisodeMeter:
         self._last_metrics: Optional[torch.Tensor] = None
         self.begin_episode()
 
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def begin_episode(self) -> None:
-        N.check(N.load().risvec_episode_clear(self.n_envs, self.n_veh, self.acc.data_ptr(), self._stream()))
+        N.check(N.load().risvec_episode_clear(self.n_envs, self.n_veh, self.acc.data_ptr(), N.stream(self.device)))
         self.n_steps = 0
 
     def _check(self, metrics, reward, power_w):
         E, V = self.n_envs, self.n_veh
-
-        def ok(t, shape):
-            return (t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()
-                    and tuple(t.shape) == shape)
-        if not ok(metrics, (E, N.METRICS)) or not ok(reward, (E, V)) or (power_w is not None and not ok(power_w, (E, 2, V))):
-            raise ValueError("EpisodeMeter: metrics [E,%d], reward [E,V], power_w [E,2,V] must be contiguous float32 "
-                             "tensors on %s" % (N.METRICS, self.device))
+        if metrics is None or reward is None:
+            raise ValueError("EpisodeMeter: metrics [E,%d] and reward [E,V] are needed (or the env)" % N.METRICS)
+        N.in_place(metrics, torch.float32, (E, N.METRICS), "metrics", self.device)
+        N.in_place(reward, torch.float32, (E, V), "reward", self.device)
+        N.in_place(power_w, torch.float32, (E, 2, V), "power_w", self.device)
 
     def bind(self, env=None, metrics=None, reward=None, power_w=None):
         """Validate once; returns `launch()`, one C-ABI call adding the CURRENT contents of the env's
@@ -95,8 +89,8 @@ class EpisodeMeter:
         self._check(metrics, reward, power_w)
         fn, check = N.load().risvec_episode_accumulate, N.check
         args = (self.n_envs, self.n_veh, metrics.data_ptr(), reward.data_ptr(),
-                None if power_w is None else power_w.data_ptr(), self.user_clip, self.acc.data_ptr())
-        stream = self._stream()
+                N.ptr(power_w), self.user_clip, self.acc.data_ptr())
+        stream = N.stream(self.device)
         self._last_metrics = metrics
 
         def launch() -> None:
@@ -117,7 +111,7 @@ class EpisodeMeter:
             raise RuntimeError("EpisodeMeter: no step was accumulated")               # ep_steps == 0 -> nan (TRAIN:1853)
         N.check(N.load().risvec_episode_summary(self.n_envs, self.n_veh, self.n_steps, self.acc.data_ptr(), m.data_ptr(),
                                                self.per_env.data_ptr(), self._partial.data_ptr(),
-                                               self.summary.data_ptr(), self._stream()))
+                                               self.summary.data_ptr(), N.stream(self.device)))
 
     def end_episode(self, metrics: Optional[torch.Tensor] = None) -> Dict[str, float]:
         """`summarize()` and return {tag: mean over envs} (this call synchronises)."""

@@ -141,10 +141,6 @@ class NomaConfig:
         return p
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 class NomaGrouper:
     """Episode-scoped pairing state of TRAIN:1282-1300 for E envs + the three driver moments."""
 
@@ -170,8 +166,7 @@ class NomaGrouper:
         if self._cstate is not None:
             return
         N.load()
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("ris_vec_marl_amd needs a HIP device; there is no CPU fallback")
+        N.require_hip(self.device)
         E, V, dev = self.n_envs, self.n_veh, self.device
         z = lambda *shape, dt: torch.zeros(*shape, dtype=dt, device=dev)   # noqa: E731
         t = self._t
@@ -197,9 +192,6 @@ class NomaGrouper:
             s.scratch, s.scratch_bytes = t["scratch"].data_ptr(), n_scratch
         self._cstate = s
 
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _params(self) -> N.RisVecNomaParams:
         return self.config.to_c(float(self.env.noise_power), float(self.env.P_max))
 
@@ -209,7 +201,7 @@ class NomaGrouper:
         cached mask / (q, K, tau)."""
         self._ensure_device()
         self.i_episode = int(i_episode)
-        N.check(N.load().risvec_noma_begin_episode(C.byref(self._cstate), self._stream()))
+        N.check(N.load().risvec_noma_begin_episode(C.byref(self._cstate), N.stream(self.device)))
         self._mask_fresh = self._have_mask = self._have_reward = False
         self._q_now = self._K_now = None
 
@@ -222,13 +214,17 @@ class NomaGrouper:
         if not self.config.mask_enable:
             return None
         q_now, K_now = self.config.mask_schedule(self.i_episode)
-        g = self._gain(gain)
-        N.check(N.load().risvec_noma_mask(C.byref(self._cstate), _ptr(g), _ptr(self._f64(gdb15)), q_now, K_now,
-                                          self._stream()))
+        g = self._gain(N.converted, gain)
+        db15 = N.converted(gdb15, torch.float64, (self.n_envs, self.n_veh), "gdb15", self.device)
+        N.check(N.load().risvec_noma_mask(C.byref(self._cstate), g.data_ptr(), N.ptr(db15), q_now, K_now,
+                                          N.stream(self.device)))
         self._q_now, self._K_now = q_now, K_now
         self._mask_fresh = self._have_mask = True
         return self._t["mask"]
 
+    # group() and bind_group() have ONE implementation, `_bind_group(conv, ...)`: validate, marshal once, return the
+    # launcher.  `bind_group` passes `N.in_place` (inputs read in place on every call, so used as they are or refused),
+    # `group` passes `N.converted` (copied if needed) plus its parity injections, and calls the launcher once.
     def group(self, p_off01: Optional[torch.Tensor], i_step: int, gain: Optional[torch.Tensor] = None,
               prev_global: Optional[torch.Tensor] = None, gdb12: Optional[torch.Tensor] = None,
               gdb15: Optional[torch.Tensor] = None, u_unstick: Optional[torch.Tensor] = None,
@@ -237,117 +233,75 @@ class NomaGrouper:
         `noma_groups` `VecEnviron.step` takes (views of the grouper's state, valid until the next call).
         `p_off01` [E,N] is the offload power in [0,1] the policy chose (TRAIN:1391-1396); alternatively
         `power_raw` [E,N,2], the SAC power head itself in [-1,1], mapped in-kernel exactly as `marshal_actions`
-        maps it (`risvec_noma_group_raw`).  `prev_global` defaults to the global reward the env's last
-        `step` left in `metrics[:,0]` (none before the first step of the episode).  `gdb12` / `gdb15`
-        inject a host's float64 dB gains (parity interface); `u_unstick` injects the TRAIN:1539 draw."""
-        self._ensure_device()
-        cfg, t = self.config, self._t
-        g = self._gain(gain)
-        if prev_global is None and self._have_reward:
-            prev_global = self.env._t["metrics"]
-        stride = 1
-        if prev_global is not None:
-            if prev_global.dim() == 2:
-                stride = prev_global.stride(0)
-            if prev_global.dtype != torch.float32 or prev_global.device != self.device:
-                raise ValueError("prev_global must be a float32 tensor on %s" % self.device)
-        if cfg.mask_enable and self._have_mask:                        # TRAIN:1486-1491
-            K_back, tau_back = self._K_now, t["tau"]
-        else:
-            q_back = float(cfg.pairing_threshold_quantile)
-            K_back = anneal_topk(self.i_episode, self.n_veh, cfg.mask_topk_start, cfg.mask_topk_end,
-                                 cfg.mask_warmup_episodes)
-            N.check(N.load().risvec_noma_mask(C.byref(self._cstate), _ptr(g), _ptr(self._f64(gdb15)), q_back, 0,
-                                              self._stream()))
-            tau_back = t["tau"]
-        p01 = None
-        fn = N.load().risvec_noma_group
-        if power_raw is not None:
-            if p_off01 is not None:
-                raise ValueError("give p_off01 or power_raw, not both")
-            p01 = power_raw.to(self.device, torch.float32).contiguous()
-            if tuple(p01.shape) != (self.n_envs, self.n_veh, 2):
-                raise ValueError("power_raw must have shape [n_envs, n_veh, 2]")
-            fn = N.load().risvec_noma_group_raw
-        elif p_off01 is not None:
-            p01 = p_off01.to(self.device, torch.float32).contiguous()
-            if tuple(p01.shape) != (self.n_envs, self.n_veh):
-                raise ValueError("p_off01 must have shape [n_envs, n_veh]")
-        uu = None if u_unstick is None else u_unstick.to(self.device, torch.float32).contiguous()
-        self._calls += 1
-        N.check(fn(
-            C.byref(self._cstate), C.byref(self._params()), _ptr(g), _ptr(self._f64(gdb12)), _ptr(p01),
-            1 if (cfg.mask_enable and self._mask_fresh) else 0, int(K_back), _ptr(tau_back),
-            _ptr(prev_global), int(stride), int(i_step), _ptr(uu), int(getattr(self.env, "seed", 0)),
-            self._calls, _ptr(t["info"]), self._stream()))
-        self._mask_fresh = False
-        self._have_reward = True        # the caller steps the env next; its metrics[:,0] feeds the next call
-        return t["partner"], t["n_groups"]
+        maps it (the `_raw` entry point).  `prev_global` ([E], or [E,k] whose column 0 is read) defaults to the
+        global reward the env's last `step` left in `metrics[:,0]` (none before the first step of the episode).
+        `gdb12` / `gdb15` inject a host's float64 dB gains (parity interface); `u_unstick` [E] injects the TRAIN:1539
+        draw."""
+        self._bind_group(N.converted, p_off01, power_raw, gain, prev_global, gdb12, gdb15, u_unstick, info=True)(i_step)
+        return self._t["partner"], self._t["n_groups"]
 
     def bind_group(self, p_off01: Optional[torch.Tensor] = None, power_raw: Optional[torch.Tensor] = None):
         """`group()` with everything that does not change from step to step validated and
         marshalled once: returns `launch(i_step)`, one pre-built C-ABI call per step (the frozen
         steps of an episode are launch-bound, so host time matters).  Inputs are read in place:
         `p_off01` (updated by the caller between steps), the env's `gain` and the global reward
-        its last `step` left in `metrics[:,0]`; `info` is not refreshed on this path.  Valid for the current episode's mask state and
-        config; `begin_episode` / `refresh_mask` / config changes need a new binding only if
-        `mask_enable` is off (tau is then recomputed per call by `group()`, not here)."""
-        self._ensure_device()
-        cfg, t = self.config, self._t
-        if not cfg.mask_enable:
+        its last `step` left in `metrics[:,0]`; `info` is not refreshed on this path.  The mask state (`refresh_mask`,
+        `begin_episode`) is looked at on every call, as `group()` does; the config is the one at bind time, and
+        `mask_enable` must be on (the cached tau / K of the last refresh_mask is what makes a call one launch)."""
+        if not self.config.mask_enable:
             raise ValueError("bind_group needs mask_enable (the cached tau / K of the last refresh_mask)")
-        p01 = None
-        lib, cs, prm = N.load(), C.byref(self._cstate), self._params()
-        fn, check = lib.risvec_noma_group, N.check
+        return self._bind_group(N.in_place, p_off01, power_raw)
+
+    def _bind_group(self, conv, p_off01, power_raw, gain=None, prev_global=None, gdb12=None, gdb15=None, u_unstick=None,
+                    info: bool = False):
+        self._ensure_device()
+        cfg, t, dev, E, V = self.config, self._t, self.device, self.n_envs, self.n_veh
+        lib, check, cs, prm = N.load(), N.check, C.byref(self._cstate), self._params()
         if power_raw is not None:                     # the SAC power head itself, mapped in-kernel (no marshalling launch)
             if p_off01 is not None:
                 raise ValueError("give p_off01 or power_raw, not both")
-            if (power_raw.dtype != torch.float32 or power_raw.device != self.device or not power_raw.is_contiguous()
-                    or tuple(power_raw.shape) != (self.n_envs, self.n_veh, 2)):
-                raise ValueError("power_raw must be a contiguous float32 [n_envs, n_veh, 2] tensor on %s" % self.device)
-            p01, fn = power_raw, lib.risvec_noma_group_raw
-        elif p_off01 is not None:
-            if (p_off01.dtype != torch.float32 or p_off01.device != self.device or not p_off01.is_contiguous()
-                    or tuple(p_off01.shape) != (self.n_envs, self.n_veh)):
-                raise ValueError("p_off01 must be a contiguous float32 [n_envs, n_veh] tensor on %s" % self.device)
-            p01 = p_off01
-        g, metrics = self.env._t["gain"], self.env._t["metrics"]
-        gp, pp, tp, mp, ip = g.data_ptr(), _ptr(p01), t["tau"].data_ptr(), metrics.data_ptr(), t["info"].data_ptr()
-        stride, seed, stream = int(metrics.stride(0)), int(getattr(self.env, "seed", 0)), self._stream()
-        pref = C.byref(prm)
+            fn, p01 = lib.risvec_noma_group_raw, conv(power_raw, torch.float32, (E, V, 2), "power_raw", dev)
+        else:
+            fn, p01 = lib.risvec_noma_group, conv(p_off01, torch.float32, (E, V), "p_off01", dev)
+        g, metrics = self._gain(conv, gain), self.env._t["metrics"]
+        db12, db15 = conv(gdb12, torch.float64, (E, V), "gdb12", dev), conv(gdb15, torch.float64, (E, V), "gdb15", dev)
+        uu = conv(u_unstick, torch.float32, (E,), "u_unstick", dev)
+        if prev_global is not None:                   # injected: read where it is, like the env's own metrics
+            if (prev_global.dtype != torch.float32 or prev_global.device != dev or prev_global.dim() < 1
+                    or prev_global.shape[0] != E):
+                raise ValueError("prev_global must be a float32 tensor of n_envs rows on %s" % dev)
+            metrics = prev_global
+        gp, pp, tp, ip = g.data_ptr(), N.ptr(p01), t["tau"].data_ptr(), t["info"].data_ptr() if info else None
+        p12, p15, pu, mp, stride = N.ptr(db12), N.ptr(db15), N.ptr(uu), metrics.data_ptr(), int(metrics.stride(0))
+        seed, stream, pref = int(getattr(self.env, "seed", 0)), N.stream(dev), C.byref(prm)
 
         def launch(i_step: int) -> None:
-            if not self._have_mask:
-                raise RuntimeError("bind_group: call refresh_mask() first in each episode")
+            if cfg.mask_enable and self._have_mask:                        # TRAIN:1486-1491
+                K_back = self._K_now
+            else:                                     # no mask held: tau of the pairing quantile, recomputed per call
+                K_back = anneal_topk(self.i_episode, V, cfg.mask_topk_start, cfg.mask_topk_end, cfg.mask_warmup_episodes)
+                check(lib.risvec_noma_mask(cs, gp, p15, float(cfg.pairing_threshold_quantile), 0, stream))
             self._calls += 1
-            check(fn(cs, pref, gp, None, pp, 1 if self._mask_fresh else 0, self._K_now, tp,
-                     mp if self._have_reward else None, stride, i_step, None, seed, self._calls, None, stream))
+            check(fn(cs, pref, gp, p12, pp, 1 if (cfg.mask_enable and self._mask_fresh) else 0, K_back, tp,
+                     mp if (prev_global is not None or self._have_reward) else None, stride, int(i_step), pu, seed,
+                     self._calls, ip, stream))
             self._mask_fresh = False
-            self._have_reward = True
+            self._have_reward = True        # the caller steps the env next; its metrics[:,0] feeds the next call
 
-        launch.keepalive = (prm, p01, g, metrics)
+        launch.keepalive = (prm, p01, g, metrics, db12, db15, uu)
         return launch
 
     def flush(self) -> None:
         """Apply the frozen steps still owed to `pair_affinity_hist` / `unpaired_streak` (the kernels
         defer that bookkeeping and replay it operation for operation when it is next needed)."""
         self._ensure_device()
-        N.check(N.load().risvec_noma_flush(C.byref(self._cstate), C.byref(self._params()), self._stream()))
+        N.check(N.load().risvec_noma_flush(C.byref(self._cstate), C.byref(self._params()), N.stream(self.device)))
 
     # ------------------------------------------------------------------ views
-    def _gain(self, gain):
-        g = self.env._t["gain"] if gain is None else gain.to(self.device, torch.float32).contiguous()
-        if tuple(g.shape) != (self.n_envs, self.n_veh):
-            raise ValueError("gain must have shape [n_envs, n_veh]")
-        return g
-
-    def _f64(self, x):
-        if x is None:
-            return None
-        x = x.to(self.device, torch.float64).contiguous()
-        if tuple(x.shape) != (self.n_envs, self.n_veh):
-            raise ValueError("dB gains must have shape [n_envs, n_veh]")
-        return x
+    def _gain(self, conv, gain):
+        if gain is None:
+            return self.env._t["gain"]
+        return conv(gain, torch.float32, (self.n_envs, self.n_veh), "gain", self.device)
 
     @property
     def mask(self) -> torch.Tensor:

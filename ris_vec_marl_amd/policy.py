@@ -22,10 +22,6 @@ from . import _native as N
 _LAYERS = ("fc1", "fc2", "mu", "log_std", "intent_logits")
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 class BatchedPolicy:
     """V stacked `PolicyNetwork`s (SAC:9-60): input_dims -> fc1 -> LayerNorm -> ReLU -> fc2 -> LayerNorm
     -> ReLU -> heads mu[n_actions], log_std[n_actions], intent_logits[n_agents]."""
@@ -47,8 +43,7 @@ class BatchedPolicy:
         if n_actions != 2:
             raise ValueError("the reference's power head has 2 outputs (offload, local); got %d" % n_actions)
         self.device = N.resolve_device(device)
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("ris_vec_marl_amd needs a HIP device; there is no CPU fallback")
+        N.require_hip(self.device)
         self.n_agents, self.input_dims, self.fc1_dims, self.fc2_dims = int(n_agents), int(input_dims), int(fc1_dims), int(fc2_dims)
         self.seed, self.env_offset, self._calls = int(seed), int(env_offset), 0
         split_ok = self.fc1_dims % 4 == 0 and self.fc1_dims <= 1024 and self.input_dims <= 8
@@ -166,7 +161,7 @@ class BatchedPolicy:
         hand-written launch, so the normalised hidden layers never make an extra HBM round trip."""
         E, V = int(obs.shape[0]), self.n_agents
         x = obs.to(self.device, torch.float32).contiguous()
-        lib, stream = N.load(), torch.cuda.current_stream(self.device).cuda_stream
+        lib, stream = N.load(), N.stream(self.device)
         if self.gemm == "fused":
             gram, w1f, frag, unscale, hfrag, hunscale = self._fused_weights()
             heads = torch.empty(V, E, 4 + V, device=self.device)
@@ -222,11 +217,7 @@ class BatchedPolicy:
             raise ValueError("obs must have shape [E, %d, %d]" % (V, self.input_dims))
         heads = self.forward_heads(obs)
         dev = self.device
-        mk = None
-        if mask is not None:
-            mk = mask.to(dev)
-            mk = (mk != 0).to(torch.uint8) if mk.dtype != torch.uint8 else mk
-            mk = mk.reshape(E, V, V).contiguous()
+        mk = None if mask is None else N.mask_u8(mask.to(dev)).reshape(E, V, V).contiguous()
         ep = None if eps is None else eps.to(dev, torch.float32).reshape(E, V, 2).contiguous()
         ex = None if expo is None else expo.to(dev, torch.float32).reshape(E, V, V).contiguous()
         power = torch.empty(E, V, 2, device=dev)
@@ -237,19 +228,20 @@ class BatchedPolicy:
             if not marsh:
                 raise ValueError("choose_action: out= needs cpu_share_floor (the marshalled outputs)")
             a_env, p01, a_store = out
+            if any(t is None for t in out):
+                raise ValueError("choose_action: out = (action_env, p_off01, action_store), all three given")
             for t, shape in ((a_env, (E, 2, V)), (p01, (E, V)), (a_store, (E, V * (V + 2)))):
-                if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
-                    raise ValueError("choose_action: out tensors must be contiguous float32 [E,2,V], [E,V], [E,V*(V+2)] on %s" % dev)
+                N.in_place(t, torch.float32, shape, "choose_action: out tensor", dev)
         else:
             a_env = torch.empty(E, 2, V, device=dev) if marsh else None
             p01 = torch.empty(E, V, device=dev) if marsh else None
             a_store = torch.empty(E, V * (V + 2), device=dev) if marsh else None
         self._calls += 1
         N.check(N.load().risvec_policy_sample(
-            E, V, self.env_offset, heads.data_ptr(), _ptr(mk), self.tau.data_ptr(), self.gumbel_hard.data_ptr(), _ptr(ep),
-            _ptr(ex), self.seed,
-            self._calls, float(cpu_share_floor) if marsh else 0.0, power.data_ptr(), probs.data_ptr(), _ptr(onehot),
-            _ptr(a_env), _ptr(p01), _ptr(a_store), torch.cuda.current_stream(dev).cuda_stream))
+            E, V, self.env_offset, heads.data_ptr(), N.ptr(mk), self.tau.data_ptr(), self.gumbel_hard.data_ptr(), N.ptr(ep),
+            N.ptr(ex), self.seed,
+            self._calls, float(cpu_share_floor) if marsh else 0.0, power.data_ptr(), probs.data_ptr(), N.ptr(onehot),
+            N.ptr(a_env), N.ptr(p01), N.ptr(a_store), N.stream(dev)))
         out = (power, probs, onehot)
         return out + (a_env, p01, a_store) if marsh else out
 

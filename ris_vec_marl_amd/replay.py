@@ -19,18 +19,13 @@ import torch
 from . import _native as N
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 class VecReplayBuffer:
     """ReplayBuffer(max_size, input_shape, n_actions, n_agents) of BUF:3-14, arrays on `device`."""
 
     def __init__(self, max_size: int, input_shape: int, n_actions: int, n_agents: int, device="cuda", seed: int = 0):
         N.load()
         self.device = N.resolve_device(device)
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("ris_vec_marl_amd needs a HIP device; there is no CPU fallback")
+        N.require_hip(self.device)
         self.mem_size = int(max_size)
         self.mem_cntr = 0
         self.input_shape, self.n_actions, self.n_agents = int(input_shape), int(n_actions), int(n_agents)
@@ -52,64 +47,23 @@ class VecReplayBuffer:
             setattr(rb, k, getattr(self, k).data_ptr())
         self._c = rb
 
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _f32(self, x, shape, name):
-        t = torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
-        t = t.to(self.device, torch.float32).reshape(shape).contiguous()
-        return t
-
     # ------------------------------------------------------------------ stores
+    # Both stores have ONE implementation, `_bind_store(conv, ...)`: validate, marshal once, return the launcher.  `conv`
+    # is the whole difference between the twins: `bind_store` passes `N.in_place` (inputs read in place on every call, so
+    # used as they are or refused), `store_batch` passes `N.converted` (copied if needed) and calls the launcher once.
     def store_batch(self, state: torch.Tensor, action: Optional[torch.Tensor], reward_g: torch.Tensor, reward_l: torch.Tensor,
                     state_: torch.Tensor, done=False, mask: Optional[torch.Tensor] = None,
                     policy_out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> None:
         """n consecutive store_transition calls (BUF:16-25), env 0 first.  state / state_ [n, ...]
         (any trailing shape with input_shape*n_agents elements, e.g. the env's obs [E,V,5]); action
-        [n, n_actions*n_agents]; reward_g [n] or a strided [n, k] tensor whose column 0 is used
+        [n, n_actions*n_agents]; reward_g [n] or an [n, k] tensor whose column 0 is used
         (the env's metrics); reward_l [n, n_agents]; done: bool or [n] bool/uint8; mask [n, A, A]
         uint8/bool (the NOMA mask) or None = all ones (TRAIN:1786-1787).
         `action=None, policy_out=(power_raw [n,A,2], probs [n,A,A])`: the action row is built in the store kernel
         from the policy outputs (what `marshal_actions` would have written, TRAIN:1386-1390, 1776-1784)."""
-        n = int(state.shape[0])
-        S, A, L = self.input_shape * self.n_agents, self.n_actions * self.n_agents, self.n_agents
-        st, st2 = self._f32(state, (n, S), "state"), self._f32(state_, (n, S), "state_")
-        rl = self._f32(reward_l, (n, L), "reward_l")
-        ac = pw = pr = None
-        if action is not None:
-            ac = self._f32(action, (n, A), "action")
-        elif policy_out is None:
-            raise ValueError("store_batch: give action or policy_out=(power_raw, probs)")
-        else:
-            pw, pr = self._f32(policy_out[0], (n, L, 2), "power_raw"), self._f32(policy_out[1], (n, L, L), "probs")
-        rg = reward_g if isinstance(reward_g, torch.Tensor) else torch.as_tensor(reward_g)
-        if rg.dtype != torch.float32 or rg.device != self.device:
-            rg = rg.to(self.device, torch.float32)
-        if rg.dim() == 2:
-            stride = rg.stride(0)
-        else:
-            rg = rg.reshape(n).contiguous()
-            stride = 1
-        if rg.shape[0] != n:
-            raise ValueError("reward_g must have n rows")
-        dn, done_all = None, 0
-        if isinstance(done, (bool, np.bool_, int)):
-            done_all = int(bool(done))
-        else:
-            dn = torch.as_tensor(done).to(self.device).to(torch.uint8).reshape(n).contiguous()
-        mk = None
-        if mask is not None:
-            mk = mask.to(self.device)
-            mk = (mk != 0).to(torch.uint8).reshape(n, L * L).contiguous() if mk.dtype != torch.uint8 \
-                else mk.reshape(n, L * L).contiguous()
-        if ac is not None:
-            N.check(N.load().risvec_replay_store(C.byref(self._c), self.mem_cntr, n, _ptr(st), _ptr(ac), _ptr(rg), int(stride),
-                                                 _ptr(rl), _ptr(st2), _ptr(dn), done_all, _ptr(mk), None, self._stream()))
-        else:
-            N.check(N.load().risvec_replay_store_policy(C.byref(self._c), self.mem_cntr, n, _ptr(st), _ptr(pw), _ptr(pr),
-                                                        _ptr(rg), int(stride), _ptr(rl), _ptr(st2), _ptr(dn), done_all,
-                                                        _ptr(mk), None, self._stream()))
-        self.mem_cntr += n
+        per_row = None if isinstance(done, (bool, np.bool_, int)) else done
+        self._bind_store(N.converted, state, action, reward_g, reward_l, state_, N.mask_u8(mask), policy_out,
+                         per_row)(done=per_row is None and bool(done))
 
     def bind_store(self, state: Optional[torch.Tensor], action: Optional[torch.Tensor], reward_g: torch.Tensor,
                    reward_l: torch.Tensor, state_: torch.Tensor, mask: Optional[torch.Tensor] = None,
@@ -125,52 +79,53 @@ class VecReplayBuffer:
         the first call then stores the CURRENT `state_` as `state`.
         `action=None, policy_out=(power_raw, probs)`: the action row is built in the store kernel from the policy
         outputs, read in place (no marshalling launch; see `store_batch`)."""
+        return self._bind_store(N.in_place, state, action, reward_g, reward_l, state_, mask, policy_out)
+
+    def _bind_store(self, conv, state, action, reward_g, reward_l, state_, mask, policy_out, done_rows=None):
         n = int(state_.shape[0])
-        carry = None
-        if state is None:
-            carry = [state_.detach().clone().reshape(n, -1), torch.empty_like(state_).reshape(n, -1)]
-            state = carry[0]
         S, A, L = self.input_shape * self.n_agents, self.n_actions * self.n_agents, self.n_agents
 
-        def ok(t, numel, dt=torch.float32):
-            return t.dtype == dt and t.device == self.device and t.is_contiguous() and t.numel() == numel
-        if action is None:
-            if policy_out is None or not (ok(policy_out[0], n * L * 2) and ok(policy_out[1], n * L * L)):
-                raise ValueError("bind_store: without action, policy_out = (power_raw [n,A,2], probs [n,A,A]) contiguous "
-                                 "float32 on %s is needed" % self.device)
-            if self.n_actions != L + 2:
-                raise ValueError("bind_store: the policy-output form needs n_actions = n_agents + 2")
-        elif not ok(action, n * A):
-            raise ValueError("bind_store: action must be a contiguous float32 [n, %d] tensor on %s" % (A, self.device))
-        if not (ok(state, n * S) and ok(state_, n * S) and ok(reward_l, n * L)):
-            raise ValueError("bind_store: state/reward_l/state_ must be contiguous float32 tensors of n rows on %s"
-                             % self.device)
-        if reward_g.dtype != torch.float32 or reward_g.device != self.device or reward_g.shape[0] != n:
-            raise ValueError("bind_store: reward_g must be a float32 tensor with n rows on %s" % self.device)
-        stride = int(reward_g.stride(0)) if reward_g.dim() == 2 else 1
-        if mask is not None and not ok(mask, n * L * L, torch.uint8):
-            raise ValueError("bind_store: mask must be a contiguous uint8 [n, A, A] tensor")
-        lib, check, rb = N.load(), N.check, C.byref(self._c)
+        def rows(x, width, name, dtype=torch.float32):
+            """x [n, ...] of `width` elements per row, whatever its trailing shape (only its memory is handed on)."""
+            if x is None:
+                return None
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(x)
+            if t.numel() != n * width:
+                raise ValueError("%s must hold n = %d rows of %d elements, got shape %s" % (name, n, width, tuple(t.shape)))
+            return conv(t, dtype, t.shape, name, self.device)
+        st2, rl = rows(state_, S, "state_"), rows(reward_l, L, "reward_l")
+        carry, st = None, rows(state, S, "state")
+        if st is None:
+            carry = [st2.detach().clone(), torch.empty_like(st2)]
         if action is not None:
-            fn_a, a_args = lib.risvec_replay_store, (action.data_ptr(),)
+            fn, act = N.load().risvec_replay_store, (rows(action, A, "action"),)
+        elif policy_out is None:
+            raise ValueError("give action or policy_out=(power_raw [n,A,2], probs [n,A,A])")
+        elif self.n_actions != L + 2:
+            raise ValueError("the policy-output form needs n_actions = n_agents + 2")
         else:
-            fn_a, a_args = lib.risvec_replay_store_policy, (policy_out[0].data_ptr(), policy_out[1].data_ptr())
-        ptrs = (state.data_ptr(), None, reward_g.data_ptr(), stride, reward_l.data_ptr(), state_.data_ptr())
-        mp, stream = _ptr(mask), self._stream()
-
+            fn = N.load().risvec_replay_store_policy
+            act = (rows(policy_out[0], L * 2, "power_raw"), rows(policy_out[1], L * L, "probs"))
+        rg = reward_g if isinstance(reward_g, torch.Tensor) else torch.as_tensor(reward_g)
+        if rg.dim() < 1 or rg.shape[0] != n:
+            raise ValueError("reward_g must have n = %d rows, got shape %s" % (n, tuple(rg.shape)))
+        rg = conv(rg, torch.float32, rg.shape, "reward_g", self.device)     # [n], or [n, k] whose column 0 is read
+        mk, dn = rows(mask, L * L, "mask", torch.uint8), rows(done_rows, 1, "done", torch.uint8)
+        check, rb, stream = N.check, C.byref(self._c), N.stream(self.device)
+        p_st, p_act, p_mk = N.ptr(st), tuple(t.data_ptr() for t in act), N.ptr(mk)
+        tail = (rg.data_ptr(), int(rg.stride(0)), rl.data_ptr(), st2.data_ptr(), N.ptr(dn))
         flip = [0]
 
         def launch(done: bool = False, use_mask: bool = True) -> None:
             if carry is None:
-                src, dst = ptrs[0], None
+                src, dst = p_st, None
             else:
                 src, dst = carry[flip[0]].data_ptr(), carry[flip[0] ^ 1].data_ptr()
                 flip[0] ^= 1
-            check(fn_a(rb, self.mem_cntr, n, src, *a_args, ptrs[2], ptrs[3], ptrs[4], ptrs[5], None,
-                       1 if done else 0, mp if use_mask else None, dst, stream))
+            check(fn(rb, self.mem_cntr, n, src, *p_act, *tail, 1 if done else 0, p_mk if use_mask else None, dst, stream))
             self.mem_cntr += n
 
-        launch.keepalive = (state, action, policy_out, reward_g, reward_l, state_, mask, carry)
+        launch.keepalive = (st, act, rg, rl, st2, mk, dn, carry)
         return launch
 
     def store_transition(self, state, action, reward_g, reward_l, state_, done, mask_flat) -> None:
@@ -226,8 +181,8 @@ class VecReplayBuffer:
                 raise ValueError("idx outside [0, %d)" % max_mem)
         self.last_batch = torch.empty(B, dtype=torch.int64, device=dev)
         self._samples += 1
-        N.check(N.load().risvec_replay_sample(C.byref(self._c), max_mem, B, _ptr(ix), self.seed, self._samples,
-                                              *(t.data_ptr() for t in out), self.last_batch.data_ptr(), self._stream()))
+        N.check(N.load().risvec_replay_sample(C.byref(self._c), max_mem, B, N.ptr(ix), self.seed, self._samples,
+                                              *(t.data_ptr() for t in out), self.last_batch.data_ptr(), N.stream(dev)))
         return out
 
 
@@ -240,8 +195,7 @@ def marshal_actions(power_raw: torch.Tensor, probs: Optional[torch.Tensor], cpu_
     power_i]).  power_raw [E,V,2] float32 in [-1,1]; probs [E,V,V] float32.  `out` = preallocated
     (action_env, p_off01, action_store) to write into."""
     N.load()
-    if power_raw.device.type != "cuda":
-        raise RuntimeError("ris_vec_marl_amd needs a HIP device; there is no CPU fallback")
+    N.require_hip(power_raw.device)
     E, V = int(power_raw.shape[0]), int(power_raw.shape[1])
     pr = power_raw.to(torch.float32).contiguous()
     if tuple(pr.shape) != (E, V, 2):
@@ -254,14 +208,13 @@ def marshal_actions(power_raw: torch.Tensor, probs: Optional[torch.Tensor], cpu_
     dev = pr.device
     if out is not None:             # preallocated (action_env, p_off01, action_store): stable pointers for bound launches
         action_env, p01, store = out
-        for t, shape in ((action_env, (E, 2, V)), (p01, (E, V))) + (((store, (E, V * (V + 2))),) if want_store else ()):
-            if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError("marshal_actions: out tensors must be contiguous float32 of shapes "
-                                 "[E,2,V], [E,V], [E,V*(V+2)] on %s" % dev)
+        N.in_place(action_env, torch.float32, (E, 2, V), "out[0] (action_env)", dev)
+        N.in_place(p01, torch.float32, (E, V), "out[1] (p_off01)", dev)
+        N.in_place(store if want_store else None, torch.float32, (E, V * (V + 2)), "out[2] (action_store)", dev)
     else:
         action_env = torch.empty(E, 2, V, device=dev)
         p01 = torch.empty(E, V, device=dev)
         store = torch.empty(E, V * (V + 2), device=dev) if want_store else None
-    N.check(N.load().risvec_marshal_actions(E, V, pr.data_ptr(), _ptr(pb), float(cpu_share_floor), action_env.data_ptr(),
-                                            p01.data_ptr(), _ptr(store), torch.cuda.current_stream(dev).cuda_stream))
+    N.check(N.load().risvec_marshal_actions(E, V, pr.data_ptr(), N.ptr(pb), float(cpu_share_floor), action_env.data_ptr(),
+                                            p01.data_ptr(), N.ptr(store), N.stream(dev)))
     return action_env, p01, store

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .compat import Environ
+from .compat import Environ, Staging
 from .params import poisson_cdf_table
 
 
@@ -90,37 +90,25 @@ class SarlEnviron(Environ):
         super().__setattr__(name, value)
 
     def _sarl_launch(self, a: np.ndarray, ph: np.ndarray, arrivals) -> None:
-        """One env, one step: power | phase | arrivals go to the device in ONE copy of pinned 32-bit words and the launch
-        is pre-bound (re-bound when a parameter of `self.sarl` changed), as in `Environ._step_launch`."""
-        import torch
+        """One env, one step: power | phase | arrivals go to the device in ONE copy (`Staging`) and the launch is
+        pre-bound (re-bound when a parameter of `self.sarl` changed), as in `Environ._step_launch`."""
         V, M, vec = self.n_veh, self.M, self._vec
         key = tuple(sorted(vars(self.sarl).items()))
-        st = self.__dict__.get("_sarl_stage")
-        if st is None or st["key"] != key:
+        if self.__dict__.get("_sarl_stage", (None,))[0] != key:
             vec._ensure_device()
-            up4 = lambda n: (n + 3) // 4 * 4                   # noqa: E731  (16-byte aligned sections)
-            o_ph = up4(2 * V)
-            o_ar = o_ph + up4(M)
-            host = torch.zeros(o_ar + up4(V), dtype=torch.int32).pin_memory()
-            dev = torch.zeros(o_ar + up4(V), dtype=torch.int32, device=vec.device)
-            hn = host.numpy()
-            d_a = dev[:2 * V].view(torch.float32).view(1, 2, V)
-            d_ph = dev[o_ph:o_ph + M].view(torch.float32).view(1, M)
-            d_ar = dev[o_ar:o_ar + V].view(1, V)
-            st = dict(key=key, host=host, dev=dev,
-                      a=hn[:2 * V].view(np.float32), ph=hn[o_ph:o_ph + M].view(np.float32), ar=hn[o_ar:o_ar + V],
-                      plain=vec.bind_sarl_step(d_a, d_ph, None, sarl_params=self.sarl),
-                      injected=vec.bind_sarl_step(d_a, d_ph, d_ar, sarl_params=self.sarl))
-            object.__setattr__(self, "_sarl_stage", st)
-        st["a"][:] = a.reshape(-1)
-        st["ph"][:] = ph
+            st = Staging(vec.device, (("a", 2 * V, torch.float32, (1, 2, V)), ("ph", M, torch.float32, (1, M)),
+                                      ("ar", V, torch.int32, (1, V))))
+            d = st.dev
+            plain = vec.bind_sarl_step(d["a"], d["ph"], None, sarl_params=self.sarl)
+            injected = vec.bind_sarl_step(d["a"], d["ph"], d["ar"], sarl_params=self.sarl)
+            object.__setattr__(self, "_sarl_stage", (key, st, plain, injected))
+        _, st, plain, injected = self._sarl_stage
+        st.host["a"][:] = a.reshape(-1)
+        st.host["ph"][:] = ph
         if arrivals is not None:
-            arr = np.asarray(arrivals)
-            if arr.shape != (V,):
-                raise ValueError("arrivals must have shape [n_veh]")
-            st["ar"][:] = arr
-        st["dev"].copy_(st["host"], non_blocking=True)
-        st["injected" if arrivals is not None else "plain"]()
+            st.host["ar"][:] = self._arrivals(arrivals)
+        st.upload()
+        (plain if arrivals is None else injected)()
 
     def step(self, action_power, action_phase, arrivals=None):   # noqa: D102  (signature of SENV:321)
         a = np.asarray(action_power, dtype=np.float64)

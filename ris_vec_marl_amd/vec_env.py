@@ -48,10 +48,6 @@ class ParamAttrs:
             object.__setattr__(self, name, value)
 
 
-def _dev_ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 class VecEnviron(ParamAttrs):
     """Batched environment.  Constructor mirrors Environment.py:57 plus batching args."""
 
@@ -118,9 +114,7 @@ class VecEnviron(ParamAttrs):
         lib = N.load()       # raises if the extension is not built
         del lib
         self.device = N.resolve_device(self.device)      # a bare "cuda" becomes cuda:<current>
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("ris_vec_marl_amd needs a HIP device (torch.cuda.is_available() is False); "
-                               "there is no CPU fallback")
+        N.require_hip(self.device)
         E, V, M = self.n_envs, self.n_veh, self.M
         dev = self.device
         z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)   # noqa: E731
@@ -187,7 +181,7 @@ class VecEnviron(ParamAttrs):
         n_max = min(10, 1 + int(0.25 * free // nbytes))
         if n_max < 2:
             return
-        lib, cs, pp, stream = N.load(), C.byref(self._cstate), C.byref(self._p()), self._stream()
+        lib, cs, pp, stream = N.load(), C.byref(self._cstate), C.byref(self._p()), N.stream(self.device)
         E, V = self.n_envs, self.n_veh
         act = torch.zeros(E, 2, V, device=self.device)
         part = torch.full((E, V), -1, dtype=torch.int32, device=self.device)
@@ -240,26 +234,11 @@ class VecEnviron(ParamAttrs):
             self._cparams_version = self.params.version
         return self._cparams
 
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _arg(self, x, dtype, shape, name) -> Optional[torch.Tensor]:
-        if x is None:
-            return None
-        tt = torch.as_tensor(x)
-        if tuple(tt.shape) != tuple(shape):
-            raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(tt.shape)))
-        return tt.to(device=self.device, dtype=dtype).contiguous()
+        return N.converted(x, dtype, shape, name, self.device)
 
     def _bound(self, x, dtype, shape, name) -> Optional[torch.Tensor]:
-        """An input of a pre-marshalled launcher: used as is or refused, never copied."""
-        if x is None:
-            return None
-        if (not isinstance(x, torch.Tensor) or x.dtype != dtype or x.device != self.device or not x.is_contiguous()
-                or tuple(x.shape) != tuple(shape)):
-            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (bound launchers read their inputs "
-                             "in place; convert it once before binding)" % (name, dtype, tuple(shape), self.device))
-        return x
+        return N.in_place(x, dtype, shape, name, self.device)
 
     # ------------------------------------------------------------------ tensors (views)
     @property
@@ -271,7 +250,7 @@ class VecEnviron(ParamAttrs):
     def _sync_theta(self) -> None:
         """Materialise tensors["theta"] from the candidate indices if the last sweeps kept theta by index."""
         if self._theta_stale:
-            N.check(N.load().risvec_theta_from_index(C.byref(self._cstate), self._stream()))
+            N.check(N.load().risvec_theta_from_index(C.byref(self._cstate), N.stream(self.device)))
             self._theta_stale = False
 
     def _by_index(self, fused: bool, steer: bool) -> bool:
@@ -307,8 +286,8 @@ class VecEnviron(ParamAttrs):
         si = self._arg(spawn_ints, torch.int32, (E, V, 3), "spawn_ints")
         b0 = self._arg(buf0, torch.int32, (E,), "buf0")
         self._epoch += 1
-        N.check(N.load().risvec_reset(C.byref(self._cstate), C.byref(self._p()), _dev_ptr(si), _dev_ptr(b0),
-                                      self.seed, self._epoch, self._stream()))
+        N.check(N.load().risvec_reset(C.byref(self._cstate), C.byref(self._p()), N.ptr(si), N.ptr(b0),
+                                      self.seed, self._epoch, N.stream(self.device)))
         self._obs_stale = True         # DataBuf changed under the observation the last step wrote
 
     def renew_positions(self, u_turn=None, return_n_used: bool = False):
@@ -318,14 +297,14 @@ class VecEnviron(ParamAttrs):
         u = self._arg(u_turn, torch.float32, (E, V, 8), "u_turn")
         nu = torch.zeros(E, V, dtype=torch.int32, device=self.device) if return_n_used else None
         self._moves += 1
-        N.check(N.load().risvec_mobility(C.byref(self._cstate), C.byref(self._p()), _dev_ptr(u), _dev_ptr(nu),
-                                         self.seed, self._moves, self._stream()))
+        N.check(N.load().risvec_mobility(C.byref(self._cstate), C.byref(self._p()), N.ptr(u), N.ptr(nu),
+                                         self.seed, self._moves, N.stream(self.device)))
         return nu
 
     def compute_parms(self) -> None:
         """Environment.py:241-253: pos -> distances_R_i, angles_R_i, phases_R_i (+ path-loss factor)."""
         self._ensure_device()
-        N.check(N.load().risvec_geometry(C.byref(self._cstate), C.byref(self._p()), self._stream()))
+        N.check(N.load().risvec_geometry(C.byref(self._cstate), C.byref(self._p()), N.stream(self.device)))
         self._colsum_valid = True
         self._steer_valid = True       # h_r[e,v,m] = z_r[e,v]^m from here on
         self._ssum_sweeps = 0          # c changed: the cached sum is stale (the candidate indices are not)
@@ -336,7 +315,7 @@ class VecEnviron(ParamAttrs):
         validity of the steering form of the fused step, `steer=True`).  theta, its cached sum aside, is
         left as it is: candidate indices the last sweep kept stay valid (the next sweep re-sums theta.c)."""
         self._ensure_device()
-        N.check(N.load().risvec_colsum(C.byref(self._cstate), self._stream()))
+        N.check(N.load().risvec_colsum(C.byref(self._cstate), N.stream(self.device)))
         self._colsum_valid = True
         self._steer_valid = False
         self._ssum_sweeps = 0
@@ -408,7 +387,7 @@ class VecEnviron(ParamAttrs):
         lazy = self.lazy_theta and bool(flags & N.BCD_REUSE_IDX)
         if lazy:
             flags |= N.BCD_NO_THETA        # the indices are the state; theta follows on demand
-        N.check(N.load().risvec_bcd(C.byref(self._cstate), C.byref(self._p()), _dev_ptr(idx), flags, self._stream()))
+        N.check(N.load().risvec_bcd(C.byref(self._cstate), C.byref(self._p()), N.ptr(idx), flags, N.stream(self.device)))
         self._bcd_done(flags, step=False)
         self._mark_theta_stale(lazy)
         return idx
@@ -420,7 +399,7 @@ class VecEnviron(ParamAttrs):
         model = str(self.params.channel_model)
         if model == "free":
             self._sync_theta()
-            N.check(N.load().risvec_gain(C.byref(self._cstate), C.byref(self._p()), self._stream()))
+            N.check(N.load().risvec_gain(C.byref(self._cstate), C.byref(self._p()), N.stream(self.device)))
             return
         E, V = self.n_envs, self.n_veh
         ul = self._arg(u_los, torch.float32, (E, V), "u_los")
@@ -428,8 +407,8 @@ class VecEnviron(ParamAttrs):
         sm = self._arg(small, torch.float32, (E, V), "small")
         self._chan += 1
         N.check(N.load().risvec_gain_3gpp(C.byref(self._cstate), C.byref(self._p()),
-                                          CHANNEL_MODELS.get(model, N.CH_OTHER), _dev_ptr(ul), _dev_ptr(zs),
-                                          _dev_ptr(sm), self.seed, self._chan, self._stream()))
+                                          CHANNEL_MODELS.get(model, N.CH_OTHER), N.ptr(ul), N.ptr(zs),
+                                          N.ptr(sm), self.seed, self._chan, N.stream(self.device)))
 
     def get_channel_gains(self) -> torch.Tensor:
         """Environment.py:374-376."""
@@ -439,7 +418,7 @@ class VecEnviron(ParamAttrs):
         """Environment.py:233-239: theta = exp(j * angle), angle [E,M]."""
         self._ensure_device()
         a = self._arg(action_phase, torch.float32, (self.n_envs, self.M), "action_phase")
-        N.check(N.load().risvec_set_phase(C.byref(self._cstate), _dev_ptr(a), self._stream()))
+        N.check(N.load().risvec_set_phase(C.byref(self._cstate), N.ptr(a), N.stream(self.device)))
         self._theta_changed()
 
     def Random_phase(self, idx=None) -> None:
@@ -447,8 +426,8 @@ class VecEnviron(ParamAttrs):
         self._ensure_device()
         i = self._arg(idx, torch.int32, (self.n_envs, self.M), "idx")
         self._chan += 1
-        N.check(N.load().risvec_random_phase(C.byref(self._cstate), _dev_ptr(i), self.seed, self._chan,
-                                             self._stream()))
+        N.check(N.load().risvec_random_phase(C.byref(self._cstate), N.ptr(i), self.seed, self._chan,
+                                             N.stream(self.device)))
         self._theta_changed()
 
     def data_rate(self, p_off, partner, n_groups) -> torch.Tensor:
@@ -459,8 +438,8 @@ class VecEnviron(ParamAttrs):
         pt = self._arg(partner, torch.int32, (E, V), "partner")
         ng = self._arg(n_groups, torch.int32, (E,), "n_groups")
         out = torch.empty(E, V, dtype=torch.float32, device=self.device)
-        N.check(N.load().risvec_data_rate(C.byref(self._cstate), C.byref(self._p()), _dev_ptr(pw), _dev_ptr(pt),
-                                          _dev_ptr(ng), _dev_ptr(out), self._stream()))
+        N.check(N.load().risvec_data_rate(C.byref(self._cstate), C.byref(self._p()), N.ptr(pw), N.ptr(pt),
+                                          N.ptr(ng), N.ptr(out), N.stream(self.device)))
         return out
 
     def _steer_flag(self, steer: bool, fused: bool) -> int:
@@ -501,7 +480,7 @@ class VecEnviron(ParamAttrs):
         if len(fading) != 3 or any(x is None for x in fading):
             raise ValueError("fading must be (u_los, z_shadow, small), all three given")
         ts = tuple(conv(x, torch.float32, shape, n) for x, n in zip(fading, ("u_los", "z_shadow", "small")))
-        return ts, N.RisVecFading(*(_dev_ptr(x) for x in ts))
+        return ts, N.RisVecFading(*(N.ptr(x) for x in ts))
 
     def _theta_mode(self, flags: int, fused: bool, bcd: bool, steer: bool) -> int:
         """Decide how a step gets at theta: by index (flag added) where lazy_theta allows, else make sure the complex64
@@ -569,8 +548,8 @@ class VecEnviron(ParamAttrs):
         lib = N.load()
         fn = lib.risvec_step_fused_bcd if bcd else (lib.risvec_step_fused if fused else lib.risvec_step)
         fn3 = lib.risvec_step_fused_3gpp
-        cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
-        pa, pp, pn, par = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar)
+        cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), N.stream(self.device)
+        pa, pp, pn, par = N.ptr(a), N.ptr(pt), N.ptr(ng), N.ptr(ar)
         pfd = C.byref(fd) if fd is not None else None
 
         def launch() -> None:
@@ -660,14 +639,14 @@ class VecEnviron(ParamAttrs):
             raise ValueError("record 'obs' needs obs=True")
         # the records are written in place whoever asks: never converted
         rec = {k: self._bound(t, torch.float32, shapes[k], "out[%r]" % k) for k, t in (out or {}).items()}
-        tj = N.RisVecTraj(_dev_ptr(rec.get("reward")), _dev_ptr(rec.get("obs")), _dev_ptr(rec.get("metrics")))
+        tj = N.RisVecTraj(N.ptr(rec.get("reward")), N.ptr(rec.get("obs")), N.ptr(rec.get("metrics")))
         fd_t, fd = self._fading(conv, fading, (T, E, V))
         self._model(fused, False, fd)                  # refuse now what every launch would refuse
         flags = self._step_flags(metrics, power_w, obs, policy_action)
         fn = N.load().risvec_step_fused_multi if fused else N.load().risvec_step_multi
         fn3 = N.load().risvec_step_fused_3gpp_multi
-        cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
-        pa, pp, pn, par, ptj = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar), C.byref(tj)
+        cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), N.stream(self.device)
+        pa, pp, pn, par, ptj = N.ptr(a), N.ptr(pt), N.ptr(ng), N.ptr(ar), C.byref(tj)
         pfd = C.byref(fd) if fd is not None else None
 
         def launch() -> None:
@@ -717,8 +696,8 @@ class VecEnviron(ParamAttrs):
         ph = conv(action_phase, torch.float32, (E, M), "action_phase")
         ar = conv(arrivals, torch.int32, (E, V), "arrivals")
         sp = (sarl_params or SarlParams()).to_c()
-        fn, cs, psp, seed, stream = N.load().risvec_sarl_step, C.byref(self._cstate), C.byref(sp), C.c_uint64(self.seed), self._stream()
-        pa, pph, par, flags = _dev_ptr(a), _dev_ptr(ph), _dev_ptr(ar), N.STEP_OBS if obs else 0
+        fn, cs, psp, seed, stream = N.load().risvec_sarl_step, C.byref(self._cstate), C.byref(sp), C.c_uint64(self.seed), N.stream(self.device)
+        pa, pph, par, flags = N.ptr(a), N.ptr(ph), N.ptr(ar), N.STEP_OBS if obs else 0
 
         def launch() -> None:
             self._sync_theta()
@@ -764,9 +743,9 @@ class VecEnviron(ParamAttrs):
         ring = N.RisVecStepRing()
         ring.rb = replay._c
         ring.probs, ring.mask = pr.data_ptr(), None
-        fn, cs, seed, stream = N.load().risvec_step_ring, C.byref(self._cstate), C.c_uint64(self.seed), self._stream()
+        fn, cs, seed, stream = N.load().risvec_step_ring, C.byref(self._cstate), C.c_uint64(self.seed), N.stream(self.device)
         fn3 = N.load().risvec_step_fused_3gpp
-        pa, pp, pn, par, pmask = _dev_ptr(a), _dev_ptr(pt), _dev_ptr(ng), _dev_ptr(ar), _dev_ptr(mk)
+        pa, pp, pn, par, pmask = N.ptr(a), N.ptr(pt), N.ptr(ng), N.ptr(ar), N.ptr(mk)
         fz = 1 if fused else 0
         pfd = C.byref(fd) if fd is not None else None
 
