@@ -378,6 +378,54 @@ int risvec_sarl_step(const RisVecState *s, const RisVecSarlParams *p, const floa
                      const float *action_phase, const int32_t *arrivals, uint64_t seed,
                      uint32_t counter, uint32_t flags, risvec_stream_t stream);
 
+/* The SARL rollout step in ONE launch (Simulation-SARL ddpg_train.py:114-185 between the actor's output and the replay
+ * buffer), per env with A = 2 n_veh + n_ris:
+ *   1. OU exploration noise (noise.py:12-17): x' = x + ou_theta (ou_mu - x) ou_dt + ou_sigma sqrt(ou_dt) z on ou_x [E,A]
+ *      in place; z [E,A] ~ N(0,1) injected, or NULL: Philox4x32-10 at (ou_env_offset + e, j, counter, site 11; ou_seed)
+ *      for the element PAIR j, Box-Muller of its words (.x, .y) giving elements 2j and 2j + 1.  ou_x NULL: no noise.
+ *   2. a = clamp(mu + x', -0.999, 0.999) -> action [E,A] (ddpg_torch.py:42, ddpg_train.py:151): the stored action row.
+ *   3. power p0_v = (a_v + 1)/2, p1_v = (a_{V+v} + 1)/2; phase_m = ((a_{2V+m} + 1)/2) 2 pi -> phase [E,M] (:154-158).
+ *   4. get_next_phase: theta = exp(j phase) -> state.theta, bit for bit what risvec_set_phase stores; the cascade reads
+ *      it on chip.
+ *   5. the cascaded gains and step() of risvec_sarl_step (RISVEC_STEP_OBS implied: state.obs receives the 5-float tail).
+ *   6. obs_full [E, V, M/V + 5]: agent v's slice phase[v tn : (v+1) tn], tn = M / V, then the tail (ddpg_train.py:47-73).
+ *   7. with the ring pointers set (all five, or none): row (mem_cntr + e) % mem_size receives state = obs_full as the
+ *      kernel found it, action = a, reward = metrics[e,0], new_state = the new obs_full, terminal = done (buffer.py:13-21).
+ *      The caller advances its mem_cntr by n_envs.
+ * Shapes: n_veh in {4, 8, 16}, even n_ris with n_veh <= n_ris <= 256 (risvec_sarl_rollout_supported); others return
+ * RISVEC_ERR_UNSUPPORTED: use the staged path (risvec_sarl_step after mapping the action on the host side). */
+typedef struct RisVecSarlRollout {
+    uint32_t struct_bytes;      /* = sizeof(RisVecSarlRollout)                           */
+    int32_t done;               /* terminal flag of this step's transitions              */
+    const float *mu;            /* [E,A]   raw actor output, read in place               */
+    float *ou_x;                /* [E,A]   OU state, updated in place (NULL: no noise)   */
+    const float *z;             /* [E,A]   injected N(0,1) draws (NULL: Philox)          */
+    float ou_theta, ou_mu, ou_sigma, ou_dt;
+    uint64_t ou_seed;           /* Philox key and global id of local env 0 for the noise */
+    int64_t ou_env_offset;
+    float *action;              /* [E,A]                                                 */
+    float *phase;               /* [E,M]   elements_phase_shift_real                     */
+    float *obs_full;            /* [E,V,M/V+5] read (ring `state`) and rewritten         */
+    float *state_memory;        /* [mem_size, V (M/V+5)]                                 */
+    float *action_memory;       /* [mem_size, A]                                         */
+    float *reward_memory;       /* [mem_size]                                            */
+    float *new_state_memory;    /* [mem_size, V (M/V+5)]                                 */
+    uint8_t *terminal_memory;   /* [mem_size] 0/1                                        */
+    int64_t mem_size, mem_cntr;
+} RisVecSarlRollout;
+int risvec_sarl_rollout(const RisVecState *s, const RisVecSarlParams *p, const RisVecSarlRollout *r,
+                        const int32_t *arrivals, uint64_t seed, uint32_t counter, uint32_t flags,
+                        risvec_stream_t stream);
+/* 1 when the one-launch rollout step has a kernel for this shape, else 0 */
+int risvec_sarl_rollout_supported(int32_t n_veh, int32_t n_ris);
+/* sample_buffer (buffer.py:23-34) of the SARL ring whose pointers and mem_size `ring` holds (its other fields are not
+ * read): rows idx[b] (int64, each < max_mem = min(mem_cntr, mem_size)) or, with idx NULL, the Philox draw of
+ * risvec_replay_sample; state rows of state_dims floats, action rows of n_actions; outputs [batch, ...]. */
+int risvec_sarl_replay_sample(const RisVecSarlRollout *ring, int32_t state_dims, int32_t n_actions, int64_t max_mem,
+                              int32_t batch, const int64_t *idx, uint64_t seed, uint32_t counter, float *states,
+                              float *actions, float *rewards, float *states_, uint8_t *dones, int64_t *idx_out,
+                              risvec_stream_t stream);
+
 /* BCD sweep + gains + step in one launch (BASELINE config 5: h_r read once into LDS). */
 int risvec_step_fused_bcd(const RisVecState *s, const RisVecParams *p, const float *action,
                           const int32_t *partner, const int32_t *n_groups,

@@ -9,7 +9,7 @@ importing the package does not need a GPU, computing does.
 from .params import EnvParams, apply_yaml_config, load_yaml, reference_lanes, poisson_cdf_table
 from .vec_env import VecEnviron
 from .compat import Environ, Vehicle, encode_noma_groups
-from .sarl import SarlEnviron, SarlParams, sarl_action_map, sarl_observe
+from .sarl import OUNoise, SarlEnviron, SarlParams, SarlReplayBuffer, sarl_action_map, sarl_observe
 from .noma import NomaConfig, NomaGrouper, anneal_topk
 from .replay import VecReplayBuffer, marshal_actions
 from .policy import BatchedPolicy
@@ -18,5 +18,5 @@ from . import dist
 
 __all__ = ["EnvParams", "apply_yaml_config", "load_yaml", "reference_lanes", "poisson_cdf_table",
            "VecEnviron", "Environ", "Vehicle", "encode_noma_groups", "SarlEnviron", "SarlParams", "sarl_action_map",
-           "sarl_observe", "NomaConfig", "NomaGrouper", "anneal_topk", "VecReplayBuffer",
+           "sarl_observe", "OUNoise", "SarlReplayBuffer", "NomaConfig", "NomaGrouper", "anneal_topk", "VecReplayBuffer",
            "marshal_actions", "BatchedPolicy", "EpisodeMeter", "ScalarSink", "dist"]

@@ -99,6 +99,18 @@ class RisVecSarlParams(C.Structure):
     ]
 
 
+class RisVecSarlRollout(C.Structure):
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("done", C.c_int32),
+        ("mu", _FP), ("ou_x", _FP), ("z", _FP),
+        ("ou_theta", C.c_float), ("ou_mu", C.c_float), ("ou_sigma", C.c_float), ("ou_dt", C.c_float),
+        ("ou_seed", C.c_uint64), ("ou_env_offset", C.c_int64),
+        ("action", _FP), ("phase", _FP), ("obs_full", _FP),
+        ("state_memory", _FP), ("action_memory", _FP), ("reward_memory", _FP), ("new_state_memory", _FP),
+        ("terminal_memory", _FP), ("mem_size", C.c_int64), ("mem_cntr", C.c_int64),
+    ]
+
+
 class RisVecNomaParams(C.Structure):
     _fields_ = [
         ("min_pair_target", C.c_int32), ("mwm_backoff_rounds", C.c_int32), ("mwm_allow_singles", C.c_int32),
@@ -179,6 +191,11 @@ _PROTOS = {
                                     C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RisVecTraj), _FP]),
     "risvec_sarl_step": (C.c_int, [C.POINTER(RisVecState), C.POINTER(RisVecSarlParams), _FP, _FP, _FP,
                                    C.c_uint64, C.c_uint32, C.c_uint32, _FP]),
+    "risvec_sarl_rollout": (C.c_int, [C.POINTER(RisVecState), C.POINTER(RisVecSarlParams), C.POINTER(RisVecSarlRollout), _FP,
+                                      C.c_uint64, C.c_uint32, C.c_uint32, _FP]),
+    "risvec_sarl_rollout_supported": (C.c_int, [C.c_int32, C.c_int32]),
+    "risvec_sarl_replay_sample": (C.c_int, [C.POINTER(RisVecSarlRollout), C.c_int32, C.c_int32, C.c_int64, C.c_int32, _FP,
+                                            C.c_uint64, C.c_uint32, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "risvec_step_fused_bcd": (C.c_int, [C.POINTER(RisVecState), C.POINTER(RisVecParams), _FP, _FP,
                                         _FP, _FP, C.c_uint64, C.c_uint32, C.c_uint32, _FP]),
     "risvec_step_ring": (C.c_int, [C.POINTER(RisVecState), C.POINTER(RisVecParams), C.POINTER(RisVecStepRing), _FP, _FP, _FP,

@@ -12,8 +12,6 @@
 namespace risvec {
 namespace {
 
-constexpr uint32_t kSiteReplay = 8;
-
 struct StoreArgs {
     RisVecReplay rb;
     long long cursor;            // mem_cntr before this call

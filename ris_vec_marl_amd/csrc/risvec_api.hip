@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "risvec_launch.hpp"
+#include "risvec_sarl.hpp"
 #include "risvec_step.hpp"
 
 namespace {
@@ -461,14 +462,29 @@ int risvec_step_multi(const RisVecState* s, const RisVecParams* p, int32_t n_ste
     return finish(fn, risvec::launch_step_multi(*s, *p, a, n_steps, &tj, (hipStream_t)stream));
 }
 
-int risvec_sarl_step(const RisVecState* s, const RisVecSarlParams* p, const float* action_power,
-                     const float* action_phase, const int32_t* arrivals, uint64_t seed, uint32_t counter,
-                     uint32_t flags, risvec_stream_t stream) {
-    const char* fn = "risvec_sarl_step";
+// the SARL parameter block of risvec_sarl_step / risvec_sarl_rollout
+static int check_sarl_params(const char* fn, const RisVecSarlParams* p) {
     if (!p) return fail(RISVEC_ERR_ARG, "%s: params is NULL", fn);
     if (p->abi_version != RISVEC_ABI_VERSION || p->struct_bytes != sizeof(RisVecSarlParams))
         return fail(RISVEC_ERR_ARG, "%s: RisVecSarlParams ABI mismatch (version %u/%u, bytes %u/%zu)", fn,
                     p->abi_version, (unsigned)RISVEC_ABI_VERSION, p->struct_bytes, sizeof(RisVecSarlParams));
+    return RISVEC_OK;
+}
+
+// the five arrays of a SARL ring (buffer.py:7-11), all required
+static int check_sarl_ring(const char* fn, const RisVecSarlRollout* r) {
+    REQ_PTR(r->state_memory, "ring.state_memory"); REQ_PTR(r->action_memory, "ring.action_memory");
+    REQ_PTR(r->reward_memory, "ring.reward_memory"); REQ_PTR(r->new_state_memory, "ring.new_state_memory");
+    REQ_PTR(r->terminal_memory, "ring.terminal_memory");
+    if (r->mem_size < 1) return fail(RISVEC_ERR_SHAPE, "%s: mem_size=%lld must be >= 1", fn, (long long)r->mem_size);
+    return RISVEC_OK;
+}
+
+int risvec_sarl_step(const RisVecState* s, const RisVecSarlParams* p, const float* action_power,
+                     const float* action_phase, const int32_t* arrivals, uint64_t seed, uint32_t counter,
+                     uint32_t flags, risvec_stream_t stream) {
+    const char* fn = "risvec_sarl_step";
+    if (int rc = check_sarl_params(fn, p)) return rc;
     if (int rc = check_common(fn, s, nullptr, false)) return rc;
     REQ_PTR(action_power, "action_power"); OPT_PTR(action_phase, "action_phase"); OPT_PTR(arrivals, "arrivals");
     REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->b, "state.b"); REQ_PTR(s->pl, "state.pl");
@@ -480,6 +496,71 @@ int risvec_sarl_step(const RisVecState* s, const RisVecSarlParams* p, const floa
     if (flags & ~(uint32_t)RISVEC_STEP_OBS) return fail(RISVEC_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags);
     return finish(fn, risvec::launch_sarl_step(*s, *p, action_power, action_phase, arrivals, seed, counter, flags,
                                                (hipStream_t)stream));
+}
+
+int risvec_sarl_rollout_supported(int32_t n_veh, int32_t n_ris) { return risvec::sarl_rollout_covers(n_veh, n_ris) ? 1 : 0; }
+
+int risvec_sarl_rollout(const RisVecState* s, const RisVecSarlParams* p, const RisVecSarlRollout* r, const int32_t* arrivals,
+                        uint64_t seed, uint32_t counter, uint32_t flags, risvec_stream_t stream) {
+    const char* fn = "risvec_sarl_rollout";
+    if (int rc = check_sarl_params(fn, p)) return rc;
+    if (!r) return fail(RISVEC_ERR_ARG, "%s: rollout is NULL", fn);
+    if (r->struct_bytes != sizeof(RisVecSarlRollout))
+        return fail(RISVEC_ERR_ARG, "%s: RisVecSarlRollout ABI mismatch (bytes %u/%zu)", fn, r->struct_bytes, sizeof(RisVecSarlRollout));
+    if (int rc = check_common(fn, s, nullptr, false)) return rc;
+    if (flags & ~(uint32_t)RISVEC_STEP_OBS) return fail(RISVEC_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags);
+    if (!risvec::sarl_rollout_covers(s->n_veh, s->n_ris))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: no one-launch rollout kernel at n_veh=%d, n_ris=%d (n_veh in {4, 8, 16}, even "
+                    "n_ris with n_veh <= n_ris <= 256); use the staged path: map the action on the host side, then "
+                    "risvec_sarl_step", fn, s->n_veh, s->n_ris);
+    REQ_PTR(r->mu, "rollout.mu"); OPT_PTR(r->ou_x, "rollout.ou_x"); OPT_PTR(r->z, "rollout.z");
+    REQ_PTR(r->action, "rollout.action"); REQ_PTR(r->phase, "rollout.phase"); REQ_PTR(r->obs_full, "rollout.obs_full");
+    OPT_PTR(arrivals, "arrivals");
+    if (r->z && !r->ou_x) return fail(RISVEC_ERR_ARG, "%s: rollout.z (injected draws) needs rollout.ou_x", fn);
+    if (r->ou_x) {
+        if (!(r->ou_dt >= 0.0f) || !std::isfinite(r->ou_dt))
+            return fail(RISVEC_ERR_ARG, "%s: ou_dt=%g must be finite and >= 0", fn, (double)r->ou_dt);
+        if (r->ou_env_offset < 0 || r->ou_env_offset + s->n_envs > 0xFFFFFFFFLL)
+            return fail(RISVEC_ERR_SHAPE, "%s: ou_env_offset+n_envs must fit 32 bits", fn);
+    }
+    REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->b, "state.b"); REQ_PTR(s->pl, "state.pl");
+    REQ_PTR(s->gain, "state.gain"); REQ_PTR(s->data_buf, "state.data_buf"); REQ_PTR(s->rate, "state.rate");
+    REQ_PTR(s->data_t, "state.data_t"); REQ_PTR(s->data_p, "state.data_p"); REQ_PTR(s->reward, "state.reward");
+    REQ_PTR(s->over_power, "state.over_power"); REQ_PTR(s->over_data, "state.over_data");
+    REQ_PTR(s->metrics, "state.metrics"); REQ_PTR(s->obs, "state.obs");
+    if (r->state_memory || r->action_memory || r->reward_memory || r->new_state_memory || r->terminal_memory) {
+        if (int rc = check_sarl_ring(fn, r)) return rc;
+        if (r->mem_size < s->n_envs)
+            return fail(RISVEC_ERR_SHAPE, "%s: n_envs=%d transitions do not fit mem_size=%lld", fn, s->n_envs, (long long)r->mem_size);
+        if (r->mem_cntr < 0) return fail(RISVEC_ERR_ARG, "%s: mem_cntr < 0", fn);
+    }
+    const hipError_t err = risvec::launch_sarl_rollout(*s, *p, *r, arrivals, seed, counter, (hipStream_t)stream);
+    if (err == hipErrorNotSupported)
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: no one-launch rollout kernel at n_veh=%d, n_ris=%d; use the staged path "
+                    "(risvec_sarl_step)", fn, s->n_veh, s->n_ris);
+    return finish(fn, err);
+}
+
+int risvec_sarl_replay_sample(const RisVecSarlRollout* ring, int32_t state_dims, int32_t n_actions, int64_t max_mem,
+                              int32_t batch, const int64_t* idx, uint64_t seed, uint32_t counter, float* states,
+                              float* actions, float* rewards, float* states_, uint8_t* dones, int64_t* idx_out,
+                              risvec_stream_t stream) {
+    const char* fn = "risvec_sarl_replay_sample";
+    if (!ring) return fail(RISVEC_ERR_ARG, "%s: ring is NULL", fn);
+    if (ring->struct_bytes != sizeof(RisVecSarlRollout))
+        return fail(RISVEC_ERR_ARG, "%s: RisVecSarlRollout ABI mismatch (bytes %u/%zu)", fn, ring->struct_bytes, sizeof(RisVecSarlRollout));
+    if (int rc = check_sarl_ring(fn, ring)) return rc;
+    if (state_dims < 1 || n_actions < 1)
+        return fail(RISVEC_ERR_SHAPE, "%s: state_dims=%d and n_actions=%d must be >= 1", fn, state_dims, n_actions);
+    if (batch < 1) return fail(RISVEC_ERR_SHAPE, "%s: batch=%d must be >= 1", fn, batch);
+    if (max_mem < 1 || max_mem > ring->mem_size)
+        return fail(RISVEC_ERR_ARG, "%s: max_mem=%lld outside [1, mem_size=%lld] (sampling an empty buffer?)", fn,
+                    (long long)max_mem, (long long)ring->mem_size);
+    OPT_PTR(idx, "idx"); OPT_PTR(idx_out, "idx_out");
+    REQ_PTR(states, "states"); REQ_PTR(actions, "actions"); REQ_PTR(rewards, "rewards"); REQ_PTR(states_, "states_");
+    REQ_PTR(dones, "dones");
+    return finish(fn, risvec::launch_sarl_replay_sample(*ring, state_dims, n_actions, max_mem, batch, idx, seed, counter, states,
+                                                        actions, rewards, states_, dones, idx_out, (hipStream_t)stream));
 }
 
 int risvec_step_fused_bcd(const RisVecState* s, const RisVecParams* p, const float* action,

@@ -32,7 +32,9 @@ struct Dims {
 // ---------------------------------------------------------------------------
 enum Site : uint32_t {
     kSiteArrivals = 0, kSiteTurnA = 1, kSiteTurnB = 2, kSiteSpawn = 3,
-    kSiteBuf0 = 4, kSite3gpp = 5, kSitePhase = 6
+    kSiteBuf0 = 4, kSite3gpp = 5, kSitePhase = 6,
+    kSiteReplay = 8,   // row draw of the replay samplers (7, 9 and 10: the pairing and the policy epilogue)
+    kSiteOU = 11       // OU exploration noise of the SARL rollout: c1 = pair index, .x / .y -> elements 2j / 2j + 1
 };
 
 __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
@@ -125,6 +127,40 @@ __device__ __forceinline__ float2 cfma(float2 a, float2 b, float2 acc) {
     acc.y = fmaf(a.x, b.y, acc.y);
     acc.y = fmaf(a.y, b.x, acc.y);
     return acc;
+}
+
+// exp(j x) in float64 for |x| <= 1e5: Cody-Waite reduction by pi/2 (two-term split, exact product for |k| < 2^17) and the
+// fdlibm kernel polynomials on [-pi/4, pi/4] -- error < 1e-15, i.e. the float32 image is the correctly rounded one except
+// within 1e-8 ulp of a rounding boundary.  ~30 float64 instructions against the ~150 of the general sincos(), whose
+// range reduction for huge arguments and special cases made k_set_phase VALU-bound (9 us for 25 MB at E = 32 768, M = 64:
+// the SARL step's theta = exp(j action_phase), every step).
+__device__ __forceinline__ void sincos_small(double x, double& s, double& c) {
+    const double kd = rint(x * 0.63661977236758138);                        // round(x * 2/pi)
+    double r = fma(-kd, 1.5707963267341256, x);                              // pi/2, high 33 bits
+    r = fma(-kd, 6.0771005065061922e-11, r);                                 // pi/2, next 53 bits
+    const double z = r * r;
+    const double ps = fma(z, fma(z, fma(z, fma(z, fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08),
+                                                  2.75573137070700676789e-06), -1.98412698298579493134e-04),
+                                 8.33333333332248946124e-03), -1.66666666666666324348e-01);
+    const double pc = fma(z, fma(z, fma(z, fma(z, fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09),
+                                                  -2.75573143513906633035e-07), 2.48015872894767294178e-05),
+                                 -1.38888888888741095749e-03), 4.16666666666666019037e-02);
+    const double sr = fma(r * z, ps, r);
+    const double cr = fma(z * z, pc, fma(-0.5, z, 1.0));
+    const int q = (int)kd & 3;
+    const double a = (q & 1) ? cr : sr, b = (q & 1) ? sr : cr;               // sin, cos before the signs
+    s = (q & 2) ? -a : a;
+    c = (q == 1 || q == 2) ? -b : b;
+}
+
+// theta = exp(j angle) as every phase setter stores it (get_next_phase, ENV:233-239): the float32 image of the float64
+// phasor of the float32 angle.  One routine for k_set_phase and the SARL rollout kernel, which must agree bit for bit.
+__device__ __forceinline__ float2 phasor_of_angle(float angle) {
+    const double x = (double)angle;
+    double s, c;
+    if (fabs(x) <= 1.0e5) sincos_small(x, s, c);
+    else sincos(x, &s, &c);                                                  // ENV:239
+    return make_float2((float)c, (float)s);
 }
 
 }  // namespace risvec

@@ -1,5 +1,5 @@
 // SARL step core (Simulation-SARL/Environment.py:321-359) shared by the generic kernel
-// (k_sarl.hip) and the software-pipelined one (k_step_pipe.hip).
+// (k_sarl.hip), the software-pipelined one (k_step_pipe.hip) and the one-launch rollout step (k_sarl_rollout.hip).
 #pragma once
 
 #include "risvec_step.hpp"
@@ -28,10 +28,16 @@ struct SarlArgs {
     uint32_t flags;
 };
 
+// what a lane's step leaves in registers: the observation tail before its scaling (ddpg_train.py:47-73) and the env's
+// mean reward (every lane of the env holds it); the rollout kernel builds obs_full and the replay row from them
+struct SarlOut {
+    float data_buf, data_t, data_p, over_data, rate, reward_mean;
+};
+
 // p0 / p1 = offload / local power of this lane, B = its DataBuf (0 for inactive lanes)
 template <int VP>
-__device__ __forceinline__ void sarl_core(const Dims& d, const RisVecSarlParams& P, const SarlArgs& A, int e,
-                                          int v, bool active, float gain, float p0, float p1, float B) {
+__device__ __forceinline__ SarlOut sarl_core(const Dims& d, const RisVecSarlParams& P, const SarlArgs& A, int e,
+                                             int v, bool active, float gain, float p0, float p1, float B) {
     const int V = d.V;
     const long long idx = (long long)e * V + v;
     const float tf = P.time_fast;
@@ -57,7 +63,7 @@ __device__ __forceinline__ void sarl_core(const Dims& d, const RisVecSarlParams&
         arr = poisson_from_u(u01(r.x), P.poisson_cdf);
     }
     const float Bo = Bn + (float)arr * tf * 1000.0f;
-    const float rew_sum = gsum<VP>(active ? rew : 0.f);
+    const float rew_mean = gsum<VP>(active ? rew : 0.f) * __builtin_amdgcn_rcpf((float)V);    // SENV:358
     if (active) {
         A.data_buf[idx] = Bo;
         A.rate[idx] = rate;
@@ -71,11 +77,21 @@ __device__ __forceinline__ void sarl_core(const Dims& d, const RisVecSarlParams&
             float* o = A.obs + idx * 5;
             o[0] = Bo * 0.1f; o[1] = data_t * 0.1f; o[2] = data_p * 0.1f; o[3] = over_data * 0.1f; o[4] = rate * 0.05f;
         }
-        if (v == 0) A.metrics[(long long)e * RISVEC_METRICS] = rew_sum * __builtin_amdgcn_rcpf((float)V);   // SENV:358
+        if (v == 0) A.metrics[(long long)e * RISVEC_METRICS] = rew_mean;
     }
+    return SarlOut{Bo, data_t, data_p, over_data, rate, rew_mean};
 }
 
 // pipelined fused kernels for compile-time shapes (k_step_pipe.hip); hipErrorNotSupported otherwise
 hipError_t launch_sarl_pipe(const RisVecState& s, const RisVecSarlParams& p, const SarlArgs& a, hipStream_t st);
+
+// the one-launch rollout step (k_sarl_rollout.hip): OU noise, action map, get_next_phase, cascade, step, obs_full, store
+bool sarl_rollout_covers(int V, int M);
+hipError_t launch_sarl_rollout(const RisVecState& s, const RisVecSarlParams& p, const RisVecSarlRollout& r,
+                               const int32_t* arrivals, uint64_t seed, uint32_t counter, hipStream_t st);
+hipError_t launch_sarl_replay_sample(const RisVecSarlRollout& ring, int state_dims, int n_actions, long long max_mem,
+                                     int batch, const int64_t* idx, uint64_t seed, uint32_t counter, float* states,
+                                     float* actions, float* rewards, float* states_, uint8_t* dones, int64_t* idx_out,
+                                     hipStream_t st);
 
 }  // namespace risvec

@@ -86,6 +86,7 @@ class VecEnviron(ParamAttrs):
         self._steps = 0          # step counter    (RNG counter for arrivals)
         self._chan = 0           # 3GPP-gain / random-phase counter
         self._obs_stale = True   # obs[E,V,5] does not reflect the state tensors (no step since the last reset)
+        self._sarl_obs_mark = None   # (_epoch, _steps) at which the SARL observation tensor was current (bind_sarl_rollout)
         self._t: Dict[str, torch.Tensor] = {}
         self._colsum_valid = False     # c_col matches h_r (set by compute_parms / rebuild_colsum)
         self._steer_valid = False      # h_r is the steering vector compute_parms wrote, z_r its base
@@ -712,6 +713,83 @@ class VecEnviron(ParamAttrs):
         launch.inputs = (a, ph, ar, sp)
         return launch
 
+    def sarl_rollout(self, mu, noise=None, replay=None, z=None, arrivals=None, sarl_params=None, done: bool = False
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """One SARL rollout step in one launch (see `bind_sarl_rollout`), inputs converted as needed.  Returns
+        (action [E, 2V+M], phase [E, M], obs_full [E, V, M//V + 5])."""
+        launch = self._bind_sarl_rollout(self._arg, mu, noise, replay, z, arrivals, sarl_params)
+        launch(done)
+        return launch.action, launch.phase, launch.obs
+
+    def bind_sarl_rollout(self, mu: torch.Tensor, noise=None, replay=None, z: Optional[torch.Tensor] = None,
+                          arrivals: Optional[torch.Tensor] = None, sarl_params=None):
+        """Everything `ddpg_train.py:114-185` does between the actor's output and the replay buffer, for every env in ONE
+        launch (`risvec_sarl_rollout`): OU exploration noise on `noise.x` in place (an `OUNoise`; None: the action is
+        `mu`; `z` [E, 2V+M] injects its N(0,1) draws), a = clip(mu + x, +-0.999), the power / phase map, get_next_phase,
+        the cascaded gains and `step()`, every agent's observation with its phase slice, and -- with `replay`, a
+        `SarlReplayBuffer(mem, M//V + 5, 2V+M, V)` -- the transition store (state = the observation the launch found).
+        Returns `launch(done=False)`; `mu` [E, 2V+M] (the raw actor output), `z` and `arrivals` are read in place on every
+        call.  `launch.action`, `launch.phase` and `launch.obs` are the output tensors; `launch.obs` is the env's SARL
+        observation, shared by every launcher of this env and, before the first step or after anything else stepped or
+        reset the env, assembled from the state with a zero phase slice (SENV:105), as `observe()` does for MARL.
+        Shapes: V in {4, 8, 16}, even M with V <= M <= 256; the launch raises `RisVecError` elsewhere (`sarl_step` serves
+        every shape)."""
+        return self._bind_sarl_rollout(self._bound, mu, noise, replay, z, arrivals, sarl_params)
+
+    def _bind_sarl_rollout(self, conv, mu, noise, replay, z, arrivals, sarl_params):
+        from .sarl import SarlParams
+        self._ensure_device()
+        E, V, M = self.n_envs, self.n_veh, self.M
+        A, tn = 2 * V + M, M // V
+        m = conv(mu, torch.float32, (E, A), "mu")
+        zz = conv(z, torch.float32, (E, A), "z")
+        ar = conv(arrivals, torch.int32, (E, V), "arrivals")
+        if zz is not None and noise is None:
+            raise ValueError("z injects the draws of `noise`: give an OUNoise")
+        r = N.RisVecSarlRollout()
+        r.struct_bytes = C.sizeof(N.RisVecSarlRollout)
+        r.mu, r.z = m.data_ptr(), N.ptr(zz)
+        if noise is not None:
+            self._bound(noise.x, torch.float32, (E, A), "noise.x")
+            r.ou_x = noise.x.data_ptr()
+            r.ou_theta, r.ou_mu, r.ou_sigma, r.ou_dt = noise.theta, noise.mu, noise.sigma, noise.dt
+            r.ou_seed, r.ou_env_offset = noise.seed, noise.env_offset
+        if replay is not None:
+            if (replay.device != self.device or replay.n_agents != V or replay.input_shape != tn + 5
+                    or replay.n_actions != A or replay.mem_size < E):
+                raise ValueError("bind_sarl_rollout: the replay buffer must live on %s with n_agents=%d, input_shape=%d, "
+                                 "n_actions=%d and mem_size >= %d" % (self.device, V, tn + 5, A, E))
+            for k in replay._ARRAYS:
+                setattr(r, k, getattr(replay, k).data_ptr())
+            r.mem_size = replay.mem_size
+        action = torch.empty(E, A, dtype=torch.float32, device=self.device)
+        phase = torch.empty(E, M, dtype=torch.float32, device=self.device)
+        obs = self.sarl_observation()
+        r.action, r.phase, r.obs_full = action.data_ptr(), phase.data_ptr(), obs.data_ptr()
+        sp = (sarl_params or SarlParams()).to_c()
+        fn, cs, psp, pr, seed, stream = (N.load().risvec_sarl_rollout, C.byref(self._cstate), C.byref(sp), C.byref(r),
+                                         C.c_uint64(self.seed), N.stream(self.device))
+        par = N.ptr(ar)
+
+        def launch(done: bool = False) -> None:
+            self.sarl_observation()              # the ring's `state` is the observation tensor as the kernel finds it
+            r.done = 1 if done else 0
+            if replay is not None:
+                r.mem_cntr = replay.mem_cntr
+            rc = fn(cs, psp, pr, par, seed, self._steps, N.STEP_OBS, stream)
+            if rc:
+                N.check(rc)
+            if replay is not None:
+                replay.mem_cntr += E
+            self._steps += 1
+            self._theta_changed()
+            self._obs_stale = False
+            self._sarl_obs_mark = (self._epoch, self._steps)
+
+        launch.action, launch.phase, launch.obs = action, phase, obs
+        launch.inputs = (m, zz, ar, noise, replay, sp, r)
+        return launch
+
     def bind_step_store(self, replay, power_raw: torch.Tensor, partner: torch.Tensor, n_groups: torch.Tensor,
                         probs: torch.Tensor, mask: Optional[torch.Tensor] = None, arrivals: Optional[torch.Tensor] = None,
                         fused: bool = True, metrics: bool = True, power_w: bool = False, fading=None):
@@ -789,6 +867,23 @@ class VecEnviron(ParamAttrs):
             self._obs_stale = False
         return t["obs"]
 
+    def sarl_observation(self) -> torch.Tensor:
+        """ddpg_train.py:47-73 for all agents: [E, V, M//V + 5] = each agent's slice of the phase action followed by
+        the 5-float tail.  The rollout launch (`bind_sarl_rollout`) writes it; before the first step, and after
+        anything else stepped or reset the env, it is assembled from the state with a zero phase slice
+        (elements_phase_shift_real starts all zero, SENV:105)."""
+        self._ensure_device()
+        t, tn = self._t, self.M // self.n_veh
+        if "sarl_obs" not in t:
+            t["sarl_obs"] = torch.zeros(self.n_envs, self.n_veh, tn + 5, dtype=torch.float32, device=self.device)
+        o = t["sarl_obs"]
+        if self._sarl_obs_mark != (self._epoch, self._steps):
+            o[..., :tn] = 0
+            for k, (key, div) in enumerate((("data_buf", 10), ("data_t", 10), ("data_p", 10), ("over_data", 10), ("rate", 20))):
+                o[..., tn + k] = t[key] / div
+            self._sarl_obs_mark = (self._epoch, self._steps)
+        return o
+
     def metrics_dict(self) -> Dict[str, torch.Tensor]:
         """The 13 `last_*` scalars + global_reward, each [E] (Environment.py:612-677, 706-711)."""
         m = self.tensors["metrics"]
@@ -841,6 +936,7 @@ class VecEnviron(ParamAttrs):
         self._epoch, self._moves, self._steps, self._chan = c["epoch"], c["moves"], c["steps"], c["chan"]
         self._steer_valid = bool(c.get("steer_valid", False))      # z_r travels with h_r
         self._obs_stale = bool(c.get("obs_stale", self._steps == 0))
+        self._sarl_obs_mark = None
 
 
 # reference attribute name -> tensor key
