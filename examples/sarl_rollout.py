@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """The single-agent driver's rollout loop (Simulation-SARL/ddpg_train.py:114-185, without the learner) for E envs:
 actor -> ONE launch per step (OU exploration noise, clip, power / phase map, get_next_phase, RIS gains + step(), every
-agent's observation, the transition store) -> a sampled training batch.  The actor here is a stand-in MLP with
-ddpg_train.py's hidden sizes: the DDPG networks and `learn()` belong to the learner.
+agent's observation, the transition store) -> a sampled training batch.  The actor is `BatchedActor`: the reference's
+`ActorNetwork.forward` (networks.py:132-141) for every env in one launch, reading the observation the rollout launch
+wrote and writing the `mu` it reads, both in place -- two launches per step.  A trained actor's weights come in with
+`actor.load_state_dict(agent.actor.state_dict())`; `learn()` and the critics belong to the learner.
 
     python examples/sarl_rollout.py [n_envs] [episodes]
 
@@ -14,7 +16,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from ris_vec_marl_amd import OUNoise, SarlReplayBuffer, VecEnviron, reference_lanes  # noqa: E402
+from ris_vec_marl_amd import BatchedActor, OUNoise, SarlReplayBuffer, VecEnviron, reference_lanes  # noqa: E402
 
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 EPISODES = int(sys.argv[2]) if len(sys.argv) > 2 else 2
@@ -26,9 +28,7 @@ L = reference_lanes()
 env = VecEnviron(L["down_lanes"], L["up_lanes"], L["left_lanes"], L["right_lanes"], 400, 400, V, M, 3,
                  n_envs=E, device=dev, seed=0)
 env.make_new_game()                                       # ddpg_train.py:42
-torch.manual_seed(0)
-actor = torch.nn.Sequential(torch.nn.Linear(V * (TN + 5), 512), torch.nn.ReLU(), torch.nn.Linear(512, 256), torch.nn.ReLU(),
-                            torch.nn.Linear(256, A), torch.nn.Tanh()).to(dev)                  # stand-in for ddpg_torch.py's actor
+actor = BatchedActor(V * (TN + 5), A, 512, 256, device=dev, seed=0)                            # ddpg_torch.py:17-19, ddpg_train.py:77-78
 noise = OUNoise(E, A, device=dev, seed=0)                 # ddpg_torch.py:26
 memory = SarlReplayBuffer(4 * N_STEP * E, TN + 5, A, V, device=dev)                            # ddpg_train.py:80 (per env: 400 steps)
 mu = torch.zeros(E, A, device=dev)                        # the launch reads the actor's output in place
@@ -43,8 +43,7 @@ for ep in range(EPISODES):
     obs = env.sarl_observation()                          # state_old_all (:134-137): zero phase slice before the first step
     ep_reward = torch.zeros(E, device=dev)
     for st in range(N_STEP):
-        with torch.no_grad():
-            torch.tanh(actor[:-1](obs.view(E, -1)), out=mu)                                    # choose_action without the noise (:149)
+        actor.forward(obs, out=mu)                        # choose_action without the noise (:149), sigmoid head
         rollout(done=st == N_STEP - 1)                    # :151-179 in one launch; obs is the new observation afterwards
         ep_reward += env.tensors["metrics"][:, 0]
     states, actions, rewards, states_, dones = memory.sample_buffer(BATCH)                     # what learn() would start from

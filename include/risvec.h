@@ -714,6 +714,33 @@ int risvec_policy_mlp(int32_t n_envs, int32_t n_veh, int32_t in_dims, int32_t f1
                       const float *G, const void *W1F, const void *W2f, const float *w_unscale, const float *b2,
                       const float *ln2_w, const float *ln2_b, const void *WhF, const float *wh_unscale, const float *bh,
                       float *heads, risvec_stream_t stream);
+/* The single-agent (DDPG) actor, ActorNetwork.forward (Simulation-SARL/networks.py:132-141): x [n_rows, in_dims] ->
+ * fc1 -> LayerNorm -> ReLU -> fc2 -> LayerNorm -> ReLU -> mu -> sigmoid, in ONE launch with one weight set shared by all
+ * rows, every product on the fp16 matrix cores at float32 accuracy (operands split as for risvec_policy_mlp); neither
+ * hidden layer touches memory.  mu [n_rows, n_actions] = sigmoid(logits); logits [n_rows, n_actions] (optional) receives
+ * the pre-sigmoid values.  x viewed as [E, V (M/V + 5)] is the observation the rollout launch writes, and mu is the
+ * tensor it reads, both in place.  16-byte alignment of x rows is needed only through the base pointer.
+ * Prepared weights (rebuild after an update; S_0 / S_1 = float16 hi / lo of 2^s X, s one power of two per matrix):
+ *   wstream  `items` items of `rows` fragment rows [64 lanes][8 halfs] (1 KiB), with KS = the first of {3, 6, 7, 9} >=
+ *            ceil((in_dims + 1) / 16), MT = fc2 / 32, HT = ceil(n_actions / 32), NG = fc1 / 32,
+ *            rows = 2 KS + 1 + 4 MT rounded up to a multiple of 4, P1 = rows / (2 KS), HS = rows / (2 HT):
+ *     ceil(NG / P1) pass-1 items: group g (32 fc1 features) in item g / P1 at rows 2 KS (g % P1) + 2 s + t, element
+ *            (lane, j) = S_t[32 g + (lane & 31)][16 s + 8 (lane >> 5) + j] of X = the fc1 weight [fc1, 16 KS] with the bias as
+ *            column in_dims, centred over the feature axis (every column sums to zero over fc1), zero beyond;
+ *     NG pass-2 items: rows [0, 2 KS) group g's fc1 fragments again; row 2 KS = LayerNorm-1 weight [32] and bias [32] of the
+ *            group as float32; rows 2 KS + 1 + (2 u + t) MT + m, element (lane, j) =
+ *            S_t[32 g + 16 u + 8 (j >> 2) + 4 (lane >> 5) + (j & 3)][32 m + (lane & 31)] of X = the fc2 weight [fc1, fc2];
+ *     ceil(2 MT / HS) head items: k-step st = 2 m + u in item st / HS at rows 2 HT (st % HS) + 2 ht + t, element (lane, j) =
+ *            S_t[32 m + 16 u + 8 (j >> 2) + 4 (lane >> 5) + (j & 3)][32 ht + (lane & 31)] of X = the mu weight [fc2, 32 HT]
+ *            (zero padded); unused rows are zero;
+ *   wstream_bytes  its size, checked against the shape;
+ *   scales [3]  2^-s of fc1, fc2 and mu.
+ * Built for in_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256}, n_actions <= 96 (risvec_sarl_actor_supported, host
+ * only); other shapes return RISVEC_ERR_SHAPE.  Inputs beyond the float16 range (|x| > 65504) are not supported. */
+int risvec_sarl_actor_supported(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions);
+int risvec_sarl_actor(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions, const float *x,
+                      const void *wstream, int64_t wstream_bytes, const float *scales, const float *b2, const float *ln2_w,
+                      const float *ln2_b, const float *bmu, float *logits, float *mu, risvec_stream_t stream);
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float *g, const float *b2,
                         const float *ln_w, const float *ln_b, const float *Wh, const float *bh, float *heads,
                         risvec_stream_t stream);

@@ -1,0 +1,248 @@
+"""The single-agent (DDPG) driver's `agent.choose_action(state)` without the noise (`Simulation-SARL/ddpg_torch.py:37-45`):
+`ActorNetwork.forward` (`Simulation-SARL/networks.py:132-141`, NET below) for all rows at once, on the GPU.
+
+    fc1 -> LayerNorm -> ReLU -> fc2 -> LayerNorm -> ReLU -> mu -> sigmoid
+
+One weight set, shared by all rows (unlike `BatchedPolicy`, which stacks one network per agent).  The input is the
+rollout launch's observation `[E, V, M//V + 5]` read in place as `[E, V (M//V + 5)]` (`ddpg_train.py:149` flattens it
+agent-major), the output is the `mu [E, 2V + M]` tensor bound to `bind_sarl_rollout`: the driver's rollout step is two
+launches, actor and everything else.  No CPU compute path.
+"""
+from __future__ import annotations
+
+import math
+from typing import Mapping, NamedTuple, Optional, Tuple
+
+import torch
+
+from . import _native as N
+
+_KS_BUILT = (3, 6, 7, 9)          # fc1 k-steps of 16 the kernel is instantiated for (csrc/k_sarl_actor.hip)
+
+
+class ActorGeom(NamedTuple):
+    """Layout of the weight stream of `risvec_sarl_actor` (include/risvec.h): `items` items of `rows` fragment rows."""
+    ks: int
+    mt: int
+    ht: int
+    ng: int
+    rows: int
+    p1: int
+    t1: int
+    hs: int
+    th: int
+    items: int
+
+
+def actor_geom(input_dims: int, fc1_dims: int, fc2_dims: int, n_actions: int) -> ActorGeom:
+    ks = next(k for k in _KS_BUILT if 16 * k >= input_dims + 1)
+    mt, ht, ng = fc2_dims // 32, (n_actions + 31) // 32, fc1_dims // 32
+    rows = (2 * ks + 1 + 4 * mt + 3) // 4 * 4
+    p1, hs = rows // (2 * ks), rows // (2 * ht)
+    t1, th = -(-ng // p1), -(-2 * mt // hs)
+    return ActorGeom(ks, mt, ht, ng, rows, p1, t1, hs, th, t1 + ng + th)
+
+
+def _supported(input_dims: int, fc1_dims: int, fc2_dims: int, n_actions: int) -> bool:
+    """The rule of `risvec_sarl_actor_supported`, restated for the pure packing function (the library is the authority:
+    tests compare the two)."""
+    return (1 <= input_dims <= 128 and fc1_dims >= 32 and fc1_dims % 32 == 0 and fc1_dims <= 1024 and fc2_dims in (128, 256)
+            and 1 <= n_actions <= 96)
+
+
+def centre_fc1(W1: torch.Tensor, b1: torch.Tensor) -> torch.Tensor:
+    """[input_dims + 1, fc1] float64: the fc1 weight (as [in, out]) with the bias as one more input row, every row
+    centred over the feature axis -- the pre-activation it produces has mean 0 over the features for any input."""
+    wb = torch.cat([W1.double().T, b1.double()[None, :]], 0)
+    return wb - wb.mean(-1, keepdim=True)
+
+
+def _split_scaled(w: torch.Tensor, target: float = 64.0):
+    """(hi, lo, 2^-s): w 2^s with its largest entry in [target, 2 target), split into float16 hi + lo (the scaling keeps lo
+    in the float16 normal range; powers of two cancel exactly)."""
+    amax = w.abs().amax().clamp_min(1e-30)
+    shift = torch.floor(torch.log2(target / amax)).clamp(-40, 40)
+    ws = (w.double() * torch.exp2(shift)).float()
+    hi = ws.to(torch.float16)
+    return hi, (ws - hi.float()).to(torch.float16), torch.exp2(-shift).float()
+
+
+def pack_actor_weights(W1, b1, ln1_w, ln1_b, W2, Wmu) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(wstream [items, rows, 64, 8] float16, scales [3] float32) of `risvec_sarl_actor` from the float32 weights
+    (Linear weights [out, in]).  A pure function of its arguments; runs on any device, CPU included."""
+    F1, IN = W1.shape
+    F2, A = W2.shape[0], Wmu.shape[0]
+    if not _supported(IN, F1, F2, A):
+        raise ValueError("no fused actor kernel for input_dims=%d fc1=%d fc2=%d n_actions=%d" % (IN, F1, F2, A))
+    g = actor_geom(IN, F1, F2, A)
+    KS, MT, HT, NG = g.ks, g.mt, g.ht, g.ng
+    dev = W1.device
+    stream = torch.zeros(g.items, g.rows, 64, 8, dtype=torch.float16, device=dev)
+    # fc1 operand [F1, 16 KS]: column k < IN the centred weight, column IN the centred bias
+    x1 = torch.zeros(F1, 16 * KS, dtype=torch.float64, device=dev)
+    x1[:, :IN + 1] = centre_fc1(W1, b1).T
+    h1, l1, u1 = _split_scaled(x1)
+    # (t, g, r, s, h, j) -> (g, s, t, h, r, j): row = 2 s + t, lane = 32 h + r
+    f1 = torch.stack([h1, l1], 0).reshape(2, NG, 32, KS, 2, 8).permute(1, 3, 0, 4, 2, 5).reshape(NG, 2 * KS, 64, 8)
+    # fc2 weight as [F1, F2]; hidden feature f = 32 g + 16 u + 8 jh + 4 h + jl:
+    # (t, g, u, jh, h, jl, m, r) -> (g, u, t, m, h, r, jh, jl): row = (2 u + t) MT + m
+    h2, l2, u2 = _split_scaled(W2.T)
+    f2 = torch.stack([h2, l2], 0).reshape(2, NG, 2, 2, 2, 4, MT, 32).permute(1, 2, 0, 6, 4, 7, 3, 5).reshape(NG, 4 * MT, 64, 8)
+    # mu weight as [F2, 32 HT], zero padded; f = 32 m + 16 u + 8 jh + 4 h + jl:
+    # (t, m, u, jh, h, jl, ht, r) -> (m, u, ht, t, h, r, jh, jl): k-step 2 m + u, row = 2 ht + t
+    wp = torch.zeros(F2, 32 * HT, dtype=Wmu.dtype, device=dev)
+    wp[:, :A] = Wmu.T
+    hh, hl, uh = _split_scaled(wp)
+    fh = torch.stack([hh, hl], 0).reshape(2, MT, 2, 2, 2, 4, HT, 32).permute(1, 2, 6, 0, 4, 7, 3, 5).reshape(2 * MT, 2 * HT, 64, 8)
+    ln = torch.zeros(NG, 256, dtype=torch.float32, device=dev)        # one fragment row as float32
+    ln[:, :32] = ln1_w.float().reshape(NG, 32)
+    ln[:, 32:64] = ln1_b.float().reshape(NG, 32)
+    s32 = stream.view(torch.float32).view(g.items, g.rows, 256)
+    for grp in range(NG):
+        it, at = divmod(grp, g.p1)
+        stream[it, 2 * KS * at:2 * KS * (at + 1)] = f1[grp]
+    p2 = stream[g.t1:g.t1 + NG]
+    p2[:, :2 * KS] = f1
+    s32[g.t1:g.t1 + NG, 2 * KS] = ln
+    p2[:, 2 * KS + 1:2 * KS + 1 + 4 * MT] = f2
+    for st in range(2 * MT):
+        it, at = divmod(st, g.hs)
+        stream[g.t1 + NG + it, 2 * HT * at:2 * HT * (at + 1)] = fh[st]
+    return stream, torch.stack([u1, u2, uh]).float().contiguous()
+
+
+def unpack_actor_weights(stream: torch.Tensor, scales: torch.Tensor, input_dims: int, fc1_dims: int, fc2_dims: int,
+                         n_actions: int) -> dict:
+    """What the kernel multiplies by, as float64: {"fc1" [input_dims + 1, fc1] (centred, the bias last), "fc1_pass1" (the
+    same, read from the pass-1 items), "fc2" [fc1, fc2], "mu" [fc2, n_actions], "ln1_w", "ln1_b" [fc1]} -- hi + lo with
+    the recorded scale undone.  The inverse of `pack_actor_weights` up to the split's rounding."""
+    g = actor_geom(input_dims, fc1_dims, fc2_dims, n_actions)
+    KS, MT, HT, NG = g.ks, g.mt, g.ht, g.ng
+    s = stream.cpu()
+    sc = scales.cpu().double()
+    p2 = s[g.t1:g.t1 + NG]
+
+    def fc1_of(frag):                                                 # [NG, 2 KS, 64, 8] -> [IN + 1, F1]
+        f = frag.double().reshape(NG, KS, 2, 2, 32, 8)                # (g, s, t, h, r, j)
+        x = (f[:, :, 0] + f[:, :, 1]).permute(0, 3, 1, 2, 4).reshape(32 * NG, 16 * KS)    # (g, r, s, h, j)
+        return (x * sc[0]).T[:input_dims + 1].contiguous()
+    p1 = torch.stack([s[grp // g.p1, 2 * KS * (grp % g.p1):2 * KS * (grp % g.p1 + 1)] for grp in range(NG)])
+    f2 = p2[:, 2 * KS + 1:2 * KS + 1 + 4 * MT].double().reshape(NG, 2, 2, MT, 2, 32, 2, 4)     # (g, u, t, m, h, r, jh, jl)
+    w2 = (f2[:, :, 0] + f2[:, :, 1]).permute(0, 1, 5, 3, 6, 2, 4).reshape(32 * NG, 32 * MT) * sc[1]   # (g, u, jh, h, jl, m, r)
+    fh = torch.stack([s[g.t1 + NG + st // g.hs, 2 * HT * (st % g.hs):2 * HT * (st % g.hs + 1)] for st in range(2 * MT)])
+    fh = fh.double().reshape(MT, 2, HT, 2, 2, 32, 2, 4)               # (m, u, ht, t, h, r, jh, jl)
+    wm = (fh[:, :, :, 0] + fh[:, :, :, 1]).permute(0, 1, 5, 3, 6, 2, 4).reshape(32 * MT, 32 * HT) * sc[2]  # (m, u, jh, h, jl, ht, r)
+    ln = s.view(torch.float32).view(g.items, g.rows, 256)[g.t1:g.t1 + NG, 2 * KS]
+    return {"fc1": fc1_of(p2[:, :2 * KS]), "fc1_pass1": fc1_of(p1), "fc2": w2, "mu": wm[:, :n_actions].contiguous(),
+            "ln1_w": ln[:, :32].reshape(-1).double(), "ln1_b": ln[:, 32:64].reshape(-1).double()}
+
+
+class BatchedActor:
+    """`ActorNetwork` (NET:95-141) for n rows at once: input_dims -> fc1 -> LayerNorm -> ReLU -> fc2 -> LayerNorm -> ReLU
+    -> mu[n_actions] -> sigmoid.  `input_dims` is the flattened width, n_agents x per-agent width (NET:99)."""
+
+    GEMM_MODES = ("fused", "library")
+    _WEIGHTS = ("W1", "b1", "ln1_w", "ln1_b", "W2", "b2", "ln2_w", "ln2_b", "Wmu", "bmu")
+    _SD = {"fc1.weight": "W1", "fc1.bias": "b1", "bn1.weight": "ln1_w", "bn1.bias": "ln1_b", "fc2.weight": "W2",
+           "fc2.bias": "b2", "bn2.weight": "ln2_w", "bn2.bias": "ln2_b", "mu.weight": "Wmu", "mu.bias": "bmu"}
+
+    def __init__(self, input_dims: int, n_actions: int, fc1_dims: int = 512, fc2_dims: int = 256, device="cuda", seed: int = 0,
+                 gemm: Optional[str] = None):
+        """gemm: how `forward` runs.  "fused": the whole forward in one hand-written MFMA launch (`risvec_sarl_actor`:
+        float16 hi + lo split products at float32 accuracy, the hidden layers never leaving the chip); built for
+        input_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256}, n_actions <= 96.  "library": `forward_torch`,
+        the same forward with library kernels only -- the fallback for every other shape and the comparator.
+        Default: fused where supported."""
+        lib = N.load()
+        self.device = N.resolve_device(device)
+        N.require_hip(self.device)
+        self.input_dims, self.n_actions, self.fc1_dims, self.fc2_dims = int(input_dims), int(n_actions), int(fc1_dims), int(fc2_dims)
+        if min(self.input_dims, self.n_actions, self.fc1_dims, self.fc2_dims) < 1:
+            raise ValueError("BatchedActor: every dimension must be >= 1")
+        fused_ok = bool(lib.risvec_sarl_actor_supported(self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions))
+        self.gemm = gemm if gemm is not None else ("fused" if fused_ok else "library")
+        if self.gemm not in self.GEMM_MODES or (self.gemm == "fused" and not fused_ok):
+            raise ValueError("gemm=%r is not available for input_dims=%d fc1=%d fc2=%d n_actions=%d (modes: %s; fused: "
+                             "input_dims <= 128, fc1 %% 32 == 0 <= 1024, fc2 in {128, 256}, n_actions <= 96)"
+                             % (gemm, self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions, ", ".join(self.GEMM_MODES)))
+        self._packed = (None, None)                           # (key, (wstream, scales))
+        dev = self.device
+        g = torch.Generator(device="cpu").manual_seed(seed)
+
+        def uni(*shape, r):
+            return ((torch.rand(*shape, generator=g) * 2 - 1) * r).to(dev)
+        f1, f2, f3 = 1.0 / math.sqrt(self.fc1_dims), 1.0 / math.sqrt(self.fc2_dims), 0.003      # NET:115-125
+        self.W1, self.b1 = uni(self.fc1_dims, self.input_dims, r=f1), uni(self.fc1_dims, r=f1)
+        self.W2, self.b2 = uni(self.fc2_dims, self.fc1_dims, r=f2), uni(self.fc2_dims, r=f2)
+        self.Wmu, self.bmu = uni(self.n_actions, self.fc2_dims, r=f3), uni(self.n_actions, r=f3)
+        self.ln1_w, self.ln1_b = torch.ones(self.fc1_dims, device=dev), torch.zeros(self.fc1_dims, device=dev)
+        self.ln2_w, self.ln2_b = torch.ones(self.fc2_dims, device=dev), torch.zeros(self.fc2_dims, device=dev)
+
+    # ------------------------------------------------------------------ weights
+    def state_dict(self) -> dict:
+        """The reference's `ActorNetwork.state_dict()` keys (fc1.* fc2.* bn1.* bn2.* mu.*), CPU copies."""
+        return {k: getattr(self, a).detach().cpu().clone() for k, a in self._SD.items()}
+
+    def load_state_dict(self, sd: Mapping[str, object]) -> None:
+        """Take the weights of a reference `ActorNetwork.state_dict()` as it is (tensors or arrays; `actor` and
+        `target_actor` checkpoints alike).  Load checkpoints with `torch.load(..., weights_only=True)`."""
+        new = {}
+        for k, a in self._SD.items():
+            if k not in sd:
+                raise KeyError("load_state_dict: %r is missing" % k)
+            t = torch.as_tensor(sd[k], dtype=torch.float32)
+            if tuple(t.shape) != tuple(getattr(self, a).shape):
+                raise ValueError("load_state_dict: %s has shape %s, this actor's is %s"
+                                 % (k, tuple(t.shape), tuple(getattr(self, a).shape)))
+            new[a] = t
+        for a, t in new.items():
+            getattr(self, a).copy_(t.to(self.device))
+
+    def _fused_weights(self):
+        """(wstream, scales) of `risvec_sarl_actor`, rebuilt when a weight tensor is replaced or updated in place."""
+        key = tuple((t.data_ptr(), t._version) for t in (self.W1, self.b1, self.ln1_w, self.ln1_b, self.W2, self.Wmu))
+        if self._packed[0] != key:
+            self._packed = (key, pack_actor_weights(self.W1, self.b1, self.ln1_w, self.ln1_b, self.W2, self.Wmu))
+        return self._packed[1]
+
+    # ------------------------------------------------------------------ forward
+    def _rows(self, obs) -> int:
+        dev = self.device
+        if (not isinstance(obs, torch.Tensor) or obs.dtype != torch.float32 or obs.device != dev or not obs.is_contiguous()
+                or obs.dim() not in (2, 3) or obs.shape[0] < 1 or obs.numel() != obs.shape[0] * self.input_dims):
+            raise ValueError("obs must be a contiguous float32 tensor [n, %d] or [n, V, %d / V] on %s"
+                             % (self.input_dims, self.input_dims, dev))
+        return int(obs.shape[0])
+
+    def forward(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None, logits: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """NET:132-141 for every row: obs [n, input_dims] or [n, V, input_dims / V] (the rollout launch's observation, read in
+        place) -> mu [n, n_actions] = sigmoid(logits).  `out`: a caller-owned [n, n_actions] tensor written in place
+        (the one bound to `bind_sarl_rollout`); `logits`: receives the pre-sigmoid values."""
+        n, dev = self._rows(obs), self.device
+        if out is None:
+            out = torch.empty(n, self.n_actions, device=dev)
+        N.in_place(out, torch.float32, (n, self.n_actions), "forward: out", dev)
+        N.in_place(logits, torch.float32, (n, self.n_actions), "forward: logits", dev)
+        if self.gemm == "library":
+            lg = self.logits_torch(obs.view(n, self.input_dims))
+            if logits is not None:
+                logits.copy_(lg)
+            return torch.sigmoid(lg, out=out)
+        ws, scales = self._fused_weights()
+        N.check(N.load().risvec_sarl_actor(n, self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions, obs.data_ptr(),
+                                           ws.data_ptr(), ws.numel() * ws.element_size(), scales.data_ptr(), self.b2.data_ptr(),
+                                           self.ln2_w.data_ptr(), self.ln2_b.data_ptr(), self.bmu.data_ptr(), N.ptr(logits),
+                                           out.data_ptr(), N.stream(dev)))
+        return out
+
+    __call__ = forward
+
+    def logits_torch(self, x: torch.Tensor) -> torch.Tensor:
+        F = torch.nn.functional
+        h = torch.relu(F.layer_norm(F.linear(x, self.W1, self.b1), (self.fc1_dims,), self.ln1_w, self.ln1_b, 1e-5))
+        h = torch.relu(F.layer_norm(F.linear(h, self.W2, self.b2), (self.fc2_dims,), self.ln2_w, self.ln2_b, 1e-5))
+        return F.linear(h, self.Wmu, self.bmu)
+
+    def forward_torch(self, obs: torch.Tensor) -> torch.Tensor:
+        """The same forward with library kernels only (torch.nn.functional.linear / layer_norm): what gemm="library" runs."""
+        return torch.sigmoid(self.logits_torch(obs.reshape(obs.shape[0], self.input_dims)))

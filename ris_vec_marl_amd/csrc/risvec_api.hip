@@ -915,6 +915,29 @@ int risvec_policy_mlp(int32_t n_envs, int32_t n_veh, int32_t in_dims, int32_t f1
                                                 ln2_b, WhF, wh_unscale, bh, heads, (hipStream_t)stream));
 }
 
+int risvec_sarl_actor_supported(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions) {
+    return risvec::sarl_actor_supported(in_dims, fc1, fc2, n_actions) ? 1 : 0;
+}
+
+int risvec_sarl_actor(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions, const float* x,
+                      const void* wstream, int64_t wstream_bytes, const float* scales, const float* b2, const float* ln2_w,
+                      const float* ln2_b, const float* bmu, float* logits, float* mu, risvec_stream_t stream) {
+    const char* fn = "risvec_sarl_actor";
+    if (n_rows < 1) return fail(RISVEC_ERR_SHAPE, "%s: n_rows=%d must be >= 1", fn, n_rows);
+    if (!risvec::sarl_actor_supported(in_dims, fc1, fc2, n_actions))
+        return fail(RISVEC_ERR_SHAPE, "%s: in_dims=%d fc1=%d fc2=%d n_actions=%d (built for in_dims <= 128, fc1 a multiple of 32 "
+                    "and <= 1024, fc2 = 128 or 256, n_actions <= 96; use library kernels elsewhere)", fn, in_dims, fc1, fc2,
+                    n_actions);
+    const risvec::SarlActorGeom g = risvec::sarl_actor_geom(in_dims, fc1, fc2, n_actions);
+    if (wstream_bytes != g.stream_bytes)
+        return fail(RISVEC_ERR_ARG, "%s: wstream_bytes=%lld, this shape's weight stream has %lld", fn, (long long)wstream_bytes,
+                    g.stream_bytes);
+    REQ_PTR(x, "x"); REQ_PTR(wstream, "wstream"); REQ_PTR(scales, "scales"); REQ_PTR(b2, "b2"); REQ_PTR(ln2_w, "ln2_w");
+    REQ_PTR(ln2_b, "ln2_b"); REQ_PTR(bmu, "bmu"); OPT_PTR(logits, "logits"); REQ_PTR(mu, "mu");
+    return finish(fn, risvec::launch_sarl_actor(n_rows, in_dims, fc1, fc2, n_actions, x, wstream, scales, b2, ln2_w, ln2_b, bmu,
+                                                logits, mu, (hipStream_t)stream));
+}
+
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float* g, const float* b2,
                         const float* ln_w, const float* ln_b, const float* Wh, const float* bh, float* heads,
                         risvec_stream_t stream) {

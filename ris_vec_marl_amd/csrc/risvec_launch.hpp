@@ -80,6 +80,16 @@ hipError_t launch_policy_mlp(int E, int V, int IN, int F1, int F2, int H, const 
 hipError_t launch_policy_heads(int E, int V, int F, int H, const float* g, const float* b2, const float* lw,
                                const float* lb, const float* Wh, const float* bh, float* heads, hipStream_t st);
 
+// The DDPG actor forward in one launch (k_sarl_actor.hip).  sarl_actor_geom(): the layout of its weight stream for a
+// supported shape (items == 0 otherwise): `items` items of `rows` fragment rows of 1 KiB -- t1 pass-1 items, ng pass-2
+// items, th head items; ks = fc1 k-steps of 16 the kernel is built with, mt / ht = fc2 / head output tiles of 32.
+struct SarlActorGeom { int ks, mt, ht, ng, rows, t1, th, items; long long stream_bytes; };
+bool sarl_actor_supported(int IN, int F1, int F2, int A);
+SarlActorGeom sarl_actor_geom(int IN, int F1, int F2, int A);
+hipError_t launch_sarl_actor(long long n_rows, int IN, int F1, int F2, int A, const float* x, const void* wstream,
+                             const float* scales, const float* b2, const float* ln2w, const float* ln2b, const float* bmu,
+                             float* logits, float* mu, hipStream_t st);
+
 int episode_partial_rows(int E);
 hipError_t launch_episode_clear(int E, int V, double* acc, hipStream_t st);
 hipError_t launch_episode_accumulate(int E, int V, const float* metrics, const float* reward, const float* power_w,
