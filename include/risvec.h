@@ -23,6 +23,7 @@
 #ifndef RISVEC_H
 #define RISVEC_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -741,6 +742,24 @@ int risvec_sarl_actor_supported(int32_t in_dims, int32_t fc1, int32_t fc2, int32
 int risvec_sarl_actor(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions, const float *x,
                       const void *wstream, int64_t wstream_bytes, const float *scales, const float *b2, const float *ln2_w,
                       const float *ln2_b, const float *bmu, float *logits, float *mu, risvec_stream_t stream);
+/* The prepared weights of risvec_sarl_actor, built on the device from the float32 weights as the learner holds them
+ * (Linear weights [out, in]: W1 [fc1, in_dims], b1 [fc1], W2 [fc2, fc1], Wmu [n_actions, fc2]; LayerNorm-1 ln1_w, ln1_b
+ * [fc1]), read in place: call it after every optimiser step.  Two launches on `stream`, no allocation, no
+ * synchronisation: one workgroup takes the float64 mean over the features of every row of [W1^T ; b1], the largest
+ * magnitude of the centred fc1 operand, of W2 and of Wmu, and from them s = floor(log2(64 / max(amax, 1e-30))) clamped to
+ * [-40, 40] per matrix; the second launch writes every 16-byte fragment of the layout above exactly once, padding
+ * included (the buffer may hold anything before the call): centre in float64, scale by 2^s, round to float32,
+ * S_0 = half(x), S_1 = half(x - float(S_0)).  Sums run in a fixed order: the same bits on every call.
+ *   wstream, wstream_bytes  the stream to write and its size, checked against the shape;
+ *   scales [3]              receives 2^-s of fc1, fc2 and mu;
+ *   workspace               risvec_sarl_actor_pack_workspace bytes (0: a shape risvec_sarl_actor is not built for), of
+ *                           any content; holds the means and 2^s between the launches.
+ * Shapes outside risvec_sarl_actor_supported return RISVEC_ERR_UNSUPPORTED. */
+size_t risvec_sarl_actor_pack_workspace(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions);
+int risvec_sarl_actor_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions, const float *W1, const float *b1,
+                           const float *ln1_w, const float *ln1_b, const float *W2, const float *Wmu, void *wstream,
+                           size_t wstream_bytes, float *scales, void *workspace, size_t workspace_bytes,
+                           risvec_stream_t stream);
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float *g, const float *b2,
                         const float *ln_w, const float *ln_b, const float *Wh, const float *bh, float *heads,
                         risvec_stream_t stream);

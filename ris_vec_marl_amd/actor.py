@@ -111,6 +111,45 @@ def pack_actor_weights(W1, b1, ln1_w, ln1_b, W2, Wmu) -> Tuple[torch.Tensor, tor
     return stream, torch.stack([u1, u2, uh]).float().contiguous()
 
 
+def pack_actor_weights_device(W1, b1, ln1_w, ln1_b, W2, Wmu, out=None, workspace=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`pack_actor_weights` computed on the device by `risvec_sarl_actor_pack` (csrc/k_sarl_actor_pack.hip): two launches
+    on the current stream, the float32 weights read in place, no copy and no synchronisation.  out: (wstream, scales)
+    to write into, every byte of them (default: new tensors); workspace: a uint8 tensor of
+    `risvec_sarl_actor_pack_workspace` bytes (default: a new one).  The same function of its arguments as the host
+    one, except that the float64 row means of the centred fc1 weight are summed in another order."""
+    lib = N.load()
+    ws = (W1, b1, ln1_w, ln1_b, W2, Wmu)
+    if not all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.device == W1.device for t in ws):
+        raise ValueError("pack_actor_weights_device: the weights must be contiguous float32 tensors on one device")
+    dev = W1.device
+    N.require_hip(dev)
+    if W1.dim() != 2 or W2.dim() != 2 or Wmu.dim() != 2:
+        raise ValueError("pack_actor_weights_device: W1, W2 and Wmu are Linear weights [out, in]")
+    (F1, IN), F2, A = W1.shape, W2.shape[0], Wmu.shape[0]
+    want = dict(b1=(F1,), ln1_w=(F1,), ln1_b=(F1,), W2=(F2, F1), Wmu=(A, F2))
+    for name, t in zip(("b1", "ln1_w", "ln1_b", "W2", "Wmu"), ws[1:]):
+        if tuple(t.shape) != want[name]:
+            raise ValueError("pack_actor_weights_device: %s has shape %s, W1 %s asks for %s" % (name, tuple(t.shape), tuple(W1.shape), want[name]))
+    need = int(lib.risvec_sarl_actor_pack_workspace(IN, F1, F2, A))
+    if need == 0:
+        raise ValueError("no fused actor kernel for input_dims=%d fc1=%d fc2=%d n_actions=%d" % (IN, F1, F2, A))
+    g = actor_geom(IN, F1, F2, A)
+    if out is None:
+        out = (torch.empty(g.items, g.rows, 64, 8, dtype=torch.float16, device=dev), torch.empty(3, device=dev))
+    stream, scales = out
+    N.in_place(stream, torch.float16, (g.items, g.rows, 64, 8), "pack_actor_weights_device: out[0]", dev)
+    N.in_place(scales, torch.float32, (3,), "pack_actor_weights_device: out[1]", dev)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
+            or not workspace.is_contiguous()):
+        raise ValueError("pack_actor_weights_device: workspace must be a contiguous uint8 tensor on %s" % dev)
+    N.check(lib.risvec_sarl_actor_pack(IN, F1, F2, A, *(t.data_ptr() for t in ws), stream.data_ptr(),
+                                       stream.numel() * stream.element_size(), scales.data_ptr(), workspace.data_ptr(),
+                                       workspace.numel(), N.stream(dev)))
+    return stream, scales
+
+
 def unpack_actor_weights(stream: torch.Tensor, scales: torch.Tensor, input_dims: int, fc1_dims: int, fc2_dims: int,
                          n_actions: int) -> dict:
     """What the kernel multiplies by, as float64: {"fc1" [input_dims + 1, fc1] (centred, the bias last), "fc1_pass1" (the
@@ -142,17 +181,22 @@ class BatchedActor:
     -> mu[n_actions] -> sigmoid.  `input_dims` is the flattened width, n_agents x per-agent width (NET:99)."""
 
     GEMM_MODES = ("fused", "library")
+    PACK_MODES = ("host", "device")
     _WEIGHTS = ("W1", "b1", "ln1_w", "ln1_b", "W2", "b2", "ln2_w", "ln2_b", "Wmu", "bmu")
     _SD = {"fc1.weight": "W1", "fc1.bias": "b1", "bn1.weight": "ln1_w", "bn1.bias": "ln1_b", "fc2.weight": "W2",
            "fc2.bias": "b2", "bn2.weight": "ln2_w", "bn2.bias": "ln2_b", "mu.weight": "Wmu", "mu.bias": "bmu"}
 
     def __init__(self, input_dims: int, n_actions: int, fc1_dims: int = 512, fc2_dims: int = 256, device="cuda", seed: int = 0,
-                 gemm: Optional[str] = None):
+                 gemm: Optional[str] = None, pack: Optional[str] = None):
         """gemm: how `forward` runs.  "fused": the whole forward in one hand-written MFMA launch (`risvec_sarl_actor`:
         float16 hi + lo split products at float32 accuracy, the hidden layers never leaving the chip); built for
         input_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256}, n_actions <= 96.  "library": `forward_torch`,
         the same forward with library kernels only -- the fallback for every other shape and the comparator.
-        Default: fused where supported."""
+        Default: fused where supported.
+        pack: how the fused kernel's weight stream is rebuilt after a weight update.  "host": `pack_actor_weights`,
+        library kernels into new tensors (the default).  "device": `pack_actor_weights_device`, two launches into
+        buffers allocated once -- for a learner that updates the weights every step (see `share_state_dict`); only where
+        the fused kernel covers the shape."""
         lib = N.load()
         self.device = N.resolve_device(device)
         N.require_hip(self.device)
@@ -165,7 +209,13 @@ class BatchedActor:
             raise ValueError("gemm=%r is not available for input_dims=%d fc1=%d fc2=%d n_actions=%d (modes: %s; fused: "
                              "input_dims <= 128, fc1 %% 32 == 0 <= 1024, fc2 in {128, 256}, n_actions <= 96)"
                              % (gemm, self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions, ", ".join(self.GEMM_MODES)))
+        self.pack = pack if pack is not None else "host"
+        if self.pack not in self.PACK_MODES or (self.pack == "device" and not fused_ok):
+            raise ValueError("pack=%r is not available for input_dims=%d fc1=%d fc2=%d n_actions=%d (modes: %s; device: "
+                             "where the fused kernel is built, see gemm)"
+                             % (pack, self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions, ", ".join(self.PACK_MODES)))
         self._packed = (None, None)                           # (key, (wstream, scales))
+        self._pack_buffers = None                             # pack="device": ((wstream, scales), workspace), at first use
         dev = self.device
         g = torch.Generator(device="cpu").manual_seed(seed)
 
@@ -198,11 +248,40 @@ class BatchedActor:
         for a, t in new.items():
             getattr(self, a).copy_(t.to(self.device))
 
+    def share_state_dict(self, sd: Mapping[str, torch.Tensor]) -> None:
+        """Use the learner's own tensors as this actor's weights, by reference (reference key names; typically
+        `agent.actor.state_dict()`): nothing is copied, now or later.  An in-place optimiser step on them is seen through
+        their version counters, and the next `forward` rebuilds the weight stream first -- with pack="device" in two
+        launches.  Tensors must be float32, contiguous, on this actor's device and of this actor's shapes."""
+        new = {}
+        for k, a in self._SD.items():
+            if k not in sd:
+                raise KeyError("share_state_dict: %r is missing" % k)
+            t, shape = sd[k], tuple(getattr(self, a).shape)
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device
+                    or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise ValueError("share_state_dict: %s must be a contiguous float32 tensor of shape %s on %s (it is used in "
+                                 "place; load_state_dict copies and converts)" % (k, shape, self.device))
+            new[a] = t.detach()                               # the same storage and version counter
+        for a, t in new.items():
+            setattr(self, a, t)
+
     def _fused_weights(self):
         """(wstream, scales) of `risvec_sarl_actor`, rebuilt when a weight tensor is replaced or updated in place."""
-        key = tuple((t.data_ptr(), t._version) for t in (self.W1, self.b1, self.ln1_w, self.ln1_b, self.W2, self.Wmu))
+        ws = (self.W1, self.b1, self.ln1_w, self.ln1_b, self.W2, self.Wmu)
+        key = tuple((t.data_ptr(), t._version) for t in ws)
         if self._packed[0] != key:
-            self._packed = (key, pack_actor_weights(self.W1, self.b1, self.ln1_w, self.ln1_b, self.W2, self.Wmu))
+            if self.pack == "device":
+                if self._pack_buffers is None:
+                    g = actor_geom(self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions)
+                    need = int(N.load().risvec_sarl_actor_pack_workspace(self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions))
+                    self._pack_buffers = ((torch.zeros(g.items, g.rows, 64, 8, dtype=torch.float16, device=self.device),
+                                           torch.zeros(3, device=self.device)),
+                                          torch.zeros(need, dtype=torch.uint8, device=self.device))
+                out, workspace = self._pack_buffers
+                self._packed = (key, pack_actor_weights_device(*ws, out=out, workspace=workspace))
+            else:
+                self._packed = (key, pack_actor_weights(*ws))
         return self._packed[1]
 
     # ------------------------------------------------------------------ forward

@@ -938,6 +938,33 @@ int risvec_sarl_actor(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2,
                                                 logits, mu, (hipStream_t)stream));
 }
 
+size_t risvec_sarl_actor_pack_workspace(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions) {
+    return (size_t)risvec::sarl_actor_pack_workspace(in_dims, fc1, fc2, n_actions);
+}
+
+int risvec_sarl_actor_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_actions, const float* W1, const float* b1,
+                           const float* ln1_w, const float* ln1_b, const float* W2, const float* Wmu, void* wstream,
+                           size_t wstream_bytes, float* scales, void* workspace, size_t workspace_bytes,
+                           risvec_stream_t stream) {
+    const char* fn = "risvec_sarl_actor_pack";
+    if (!risvec::sarl_actor_supported(in_dims, fc1, fc2, n_actions))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: in_dims=%d fc1=%d fc2=%d n_actions=%d (risvec_sarl_actor is built for in_dims "
+                    "<= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128 or 256, n_actions <= 96)", fn, in_dims, fc1, fc2,
+                    n_actions);
+    REQ_PTR(W1, "W1"); REQ_PTR(b1, "b1"); REQ_PTR(ln1_w, "ln1_w"); REQ_PTR(ln1_b, "ln1_b"); REQ_PTR(W2, "W2");
+    REQ_PTR(Wmu, "Wmu"); REQ_PTR(wstream, "wstream"); REQ_PTR(scales, "scales"); REQ_PTR(workspace, "workspace");
+    const risvec::SarlActorGeom g = risvec::sarl_actor_geom(in_dims, fc1, fc2, n_actions);
+    if (wstream_bytes != (size_t)g.stream_bytes)
+        return fail(RISVEC_ERR_ARG, "%s: wstream_bytes=%zu, this shape's weight stream has %lld", fn, wstream_bytes,
+                    g.stream_bytes);
+    const size_t need = (size_t)risvec::sarl_actor_pack_workspace(in_dims, fc1, fc2, n_actions);
+    if (workspace_bytes < need)
+        return fail(RISVEC_ERR_ARG, "%s: workspace_bytes=%zu, this shape needs %zu (risvec_sarl_actor_pack_workspace)", fn,
+                    workspace_bytes, need);
+    return finish(fn, risvec::launch_sarl_actor_pack(in_dims, fc1, fc2, n_actions, W1, b1, ln1_w, ln1_b, W2, Wmu, wstream,
+                                                     scales, workspace, (hipStream_t)stream));
+}
+
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float* g, const float* b2,
                         const float* ln_w, const float* ln_b, const float* Wh, const float* bh, float* heads,
                         risvec_stream_t stream) {

@@ -89,6 +89,12 @@ SarlActorGeom sarl_actor_geom(int IN, int F1, int F2, int A);
 hipError_t launch_sarl_actor(long long n_rows, int IN, int F1, int F2, int A, const float* x, const void* wstream,
                              const float* scales, const float* b2, const float* ln2w, const float* ln2b, const float* bmu,
                              float* logits, float* mu, hipStream_t st);
+// That weight stream and its scales from the float32 weights, in two launches (k_sarl_actor_pack.hip); the workspace
+// holds sarl_actor_pack_workspace() bytes (0: no such shape) and needs no initialisation.
+long long sarl_actor_pack_workspace(int IN, int F1, int F2, int A);
+hipError_t launch_sarl_actor_pack(int IN, int F1, int F2, int A, const float* W1, const float* b1, const float* ln1w,
+                                  const float* ln1b, const float* W2, const float* Wmu, void* wstream, float* scales,
+                                  void* workspace, hipStream_t st);
 
 int episode_partial_rows(int E);
 hipError_t launch_episode_clear(int E, int V, double* acc, hipStream_t st);
