@@ -760,6 +760,41 @@ int risvec_sarl_actor_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_
                            const float *ln1_w, const float *ln1_b, const float *W2, const float *Wmu, void *wstream,
                            size_t wstream_bytes, float *scales, void *workspace, size_t workspace_bytes,
                            risvec_stream_t stream);
+/* The single-agent (DDPG) critic, CriticNetwork.forward (Simulation-SARL/networks.py:66-79), and the TD target of learn()
+ * (ddpg_torch.py:84-88), in ONE launch with one weight set shared by all rows:
+ *     s = relu(LN1(fc1 x));  s = LN2(fc2 s);  h = relu(s + action_value(a));  h = relu(LN3(fc3 h));  q = q_w . h + q_b
+ *     y[row] = done[row] ? reward[row] : reward[row] + gamma q[row]      (a select; one fused multiply-add)
+ * x [n_rows, in_dims], a [n_rows, n_actions] float32, read in place (no alignment beyond float's).  The four matrix products
+ * run on the fp16 matrix cores at float32 accuracy (operands split as for risvec_sarl_actor), the 1-wide q layer is a dot
+ * product in registers; no hidden layer touches memory.  q_out [n_rows] and y_out [n_rows] are each optional, at least one
+ * must be given; y_out needs reward [n_rows] float32 and done [n_rows] uint8 (0 / 1).
+ * Prepared weights (rebuild after an update; S_0 / S_1 = float16 hi / lo of 2^s X, s one power of two per matrix):
+ *   wstream  fragment rows [64 lanes][8 halfs] (1 KiB) in four blocks, with KS = ceil((in_dims + 1) / 16), KSA =
+ *            ceil(n_actions / 16), NG = fc1 / 32, MT2 = fc2 / 128, MT3 = fc3 / 128; w < 4 is the wavefront that owns
+ *            output tiles [w MT, (w + 1) MT) of a layer, t = hi / lo:
+ *     action_value  row ((w KSA + s) MT2 + m) 2 + t: element (lane, j) = S_t[16 s + 8 (lane >> 5) + j][32 (w MT2 + m) + (lane & 31)]
+ *            of X = the action_value weight as [16 KSA, fc2], zero beyond n_actions;
+ *     fc1    row (g KS + s) 2 + t, g < NG: element (lane, j) = S_t[32 g + (lane & 31)][16 s + 8 (lane >> 5) + j] of X = the fc1
+ *            weight [fc1, 16 KS] with the bias as column in_dims, centred over the feature axis (every column sums to
+ *            zero over fc1), zero beyond;
+ *     fc2    row ((w 2 NG + k) MT2 + m) 2 + t, k < 2 NG: element (lane, j) =
+ *            S_t[16 k + 8 (j >> 2) + 4 (lane >> 5) + (j & 3)][32 (w MT2 + m) + (lane & 31)] of X = the fc2 weight [fc1, fc2];
+ *     fc3    row ((w fc2 / 16 + k) MT3 + m) 2 + t, k < fc2 / 16: the same element rule for X = the fc3 weight [fc2, fc3];
+ *   wstream_bytes  its size = risvec_sarl_critic_stream_bytes(...), checked against the shape;
+ *   scales [4]  2^-s of fc1, fc2, action_value and fc3;
+ *   ln1_w, ln1_b [fc1]; b2, ln2_w, ln2_b, bav (the action_value bias) [fc2]; b3, ln3_w, ln3_b, q_w [fc3]; q_b [1]: float32,
+ *            16-byte aligned, read in place.
+ * Built for in_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}, n_actions <= 96
+ * (risvec_sarl_critic_supported, host only); other shapes return RISVEC_ERR_SHAPE (stream_bytes: 0).  Inputs beyond the
+ * float16 range (|x| > 65504) are not supported. */
+int risvec_sarl_critic_supported(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions);
+int64_t risvec_sarl_critic_stream_bytes(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions);
+int risvec_sarl_critic(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions, const float *x,
+                       const float *a, const void *wstream, int64_t wstream_bytes, const float *scales, const float *ln1_w,
+                       const float *ln1_b, const float *b2, const float *ln2_w, const float *ln2_b, const float *bav,
+                       const float *b3, const float *ln3_w, const float *ln3_b, const float *q_w, const float *q_b,
+                       const float *reward, const uint8_t *done, float gamma, float *q_out, float *y_out,
+                       risvec_stream_t stream);
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float *g, const float *b2,
                         const float *ln_w, const float *ln_b, const float *Wh, const float *bh, float *heads,
                         risvec_stream_t stream);

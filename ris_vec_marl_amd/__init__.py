@@ -14,10 +14,12 @@ from .noma import NomaConfig, NomaGrouper, anneal_topk
 from .replay import VecReplayBuffer, marshal_actions
 from .policy import BatchedPolicy
 from .actor import BatchedActor, pack_actor_weights_device
+from .critic import BatchedCritic, ddpg_td_target, pack_critic_weights, unpack_critic_weights
 from .metrics import EpisodeMeter, ScalarSink
 from . import dist
 
 __all__ = ["EnvParams", "apply_yaml_config", "load_yaml", "reference_lanes", "poisson_cdf_table",
            "VecEnviron", "Environ", "Vehicle", "encode_noma_groups", "SarlEnviron", "SarlParams", "sarl_action_map",
            "sarl_observe", "OUNoise", "SarlReplayBuffer", "NomaConfig", "NomaGrouper", "anneal_topk", "VecReplayBuffer",
-           "marshal_actions", "BatchedPolicy", "BatchedActor", "pack_actor_weights_device", "EpisodeMeter", "ScalarSink", "dist"]
+           "marshal_actions", "BatchedPolicy", "BatchedActor", "pack_actor_weights_device", "BatchedCritic",
+           "ddpg_td_target", "pack_critic_weights", "unpack_critic_weights", "EpisodeMeter", "ScalarSink", "dist"]

@@ -1,0 +1,326 @@
+"""The single-agent (DDPG) learner's first step on a sampled batch (`Simulation-SARL/ddpg_torch.py:80-88`): the target
+critic's forward, `CriticNetwork.forward` (`Simulation-SARL/networks.py:66-79`, NET below), and the TD target, for all
+rows at once on the GPU.
+
+    s = relu(LN1(fc1 x));  s = LN2(fc2 s);  h = relu(s + action_value(a));  h = relu(LN3(fc3 h));  q = q_w . h + q_b
+    y = done ? reward : reward + gamma q
+
+One weight set shared by all rows.  `BatchedCritic.forward` / `td_target` are one launch (`risvec_sarl_critic`);
+`ddpg_td_target` is `target_actor.forward` + `target_critic.td_target`, two launches, the sampled tensors read in
+place.  Nothing here differentiates: the gradient half of `learn()` stays with the learner.  No CPU compute path.
+"""
+from __future__ import annotations
+
+import math
+from typing import Mapping, NamedTuple, Optional, Tuple
+
+import torch
+
+from . import _native as N
+from .actor import _split_scaled, centre_fc1
+
+_WAVES = 4                        # wavefronts of a workgroup: each owns a quarter of every layer's output features
+
+
+class CriticGeom(NamedTuple):
+    """Layout of the weight stream of `risvec_sarl_critic` (include/risvec.h): fragment rows of 1 KiB in four blocks that
+    start at rows `av`, `fc1`, `fc2`, `fc3`; `rows` in all."""
+    ks: int
+    ksa: int
+    ng: int
+    mt2: int
+    mt3: int
+    av: int
+    fc1: int
+    fc2: int
+    fc3: int
+    rows: int
+
+
+def critic_geom(input_dims: int, fc1_dims: int, fc2_dims: int, fc3_dims: int, n_actions: int) -> CriticGeom:
+    ks, ksa, ng = (input_dims + 1 + 15) // 16, (n_actions + 15) // 16, fc1_dims // 32
+    mt2, mt3 = fc2_dims // (32 * _WAVES), fc3_dims // (32 * _WAVES)
+    av = 0
+    fc1 = av + _WAVES * ksa * mt2 * 2
+    fc2 = fc1 + ng * ks * 2
+    fc3 = fc2 + _WAVES * 2 * ng * mt2 * 2
+    rows = fc3 + _WAVES * 8 * mt2 * mt3 * 2
+    return CriticGeom(ks, ksa, ng, mt2, mt3, av, fc1, fc2, fc3, rows)
+
+
+def _supported(input_dims: int, fc1_dims: int, fc2_dims: int, fc3_dims: int, n_actions: int) -> bool:
+    """The rule of `risvec_sarl_critic_supported`, restated for the pure packing function (the library is the authority:
+    tests compare the two)."""
+    return (1 <= input_dims <= 128 and fc1_dims >= 32 and fc1_dims % 32 == 0 and fc1_dims <= 1024
+            and fc2_dims in (128, 256, 512) and fc3_dims in (128, 256) and 1 <= n_actions <= 96)
+
+
+# A fragments [tiles, k-steps, 2 (hi | lo), 64 lanes, 8] of X [K, N] (input-major), N = 32 tiles; lane = 32 h + r holds
+# output feature 32 tile + r.  "nat": k = 16 s + 8 h + j (the operand comes from memory); "cd": k = 16 s + 8 (j >> 2) +
+# 4 h + (j & 3) (the operand is the previous MFMA's accumulator, registers 8u .. 8u+7 = k-step u).
+def _frags(hi: torch.Tensor, lo: torch.Tensor, order: str) -> torch.Tensor:
+    K, Nn = hi.shape
+    s = torch.stack([hi, lo], 0)
+    if order == "nat":                                                # (t, s, h, j, tile, r) -> (tile, s, t, h, r, j)
+        return s.reshape(2, K // 16, 2, 8, Nn // 32, 32).permute(4, 1, 0, 2, 5, 3).reshape(Nn // 32, K // 16, 2, 64, 8)
+    # (t, s, jh, h, jl, tile, r) -> (tile, s, t, h, r, jh, jl)
+    return s.reshape(2, K // 16, 2, 2, 4, Nn // 32, 32).permute(5, 1, 0, 3, 6, 2, 4).reshape(Nn // 32, K // 16, 2, 64, 8)
+
+
+def _unfrags(f: torch.Tensor, order: str) -> torch.Tensor:
+    """hi + lo of `_frags` back as float64 X [K, N]."""
+    tiles, ks = f.shape[0], f.shape[1]
+    f = f.double()
+    f = f[:, :, 0] + f[:, :, 1]                                       # (tile, s, lane, j)
+    if order == "nat":                                                # (tile, s, h, r, j) -> (s, h, j, tile, r)
+        return f.reshape(tiles, ks, 2, 32, 8).permute(1, 2, 4, 0, 3).reshape(16 * ks, 32 * tiles)
+    # (tile, s, h, r, jh, jl) -> (s, jh, h, jl, tile, r)
+    return f.reshape(tiles, ks, 2, 32, 2, 4).permute(1, 4, 2, 5, 0, 3).reshape(16 * ks, 32 * tiles)
+
+
+def _by_wave(f: torch.Tensor, mt: int) -> torch.Tensor:
+    """[4 mt tiles, ks, 2, 64, 8] -> rows in stream order (w, s, m, t)."""
+    ks = f.shape[1]
+    return f.reshape(_WAVES, mt, ks, 2, 64, 8).permute(0, 2, 1, 3, 4, 5).reshape(-1, 64, 8)
+
+
+def _from_wave(rows: torch.Tensor, mt: int, ks: int) -> torch.Tensor:
+    return rows.reshape(_WAVES, ks, mt, 2, 64, 8).permute(0, 2, 1, 3, 4, 5).reshape(_WAVES * mt, ks, 2, 64, 8)
+
+
+def pack_critic_weights(W1, b1, W2, Wav, W3) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(wstream [rows, 64, 8] float16, scales [4] float32) of `risvec_sarl_critic` from the float32 Linear weights
+    ([out, in]: fc1 and its bias, fc2, action_value, fc3).  A pure function of its arguments; runs on any device, CPU
+    included.  The LayerNorm parameters, the other biases and the q layer are read by the kernel as they are."""
+    F1, IN = W1.shape
+    F2, A, F3 = W2.shape[0], Wav.shape[1], W3.shape[0]
+    if not _supported(IN, F1, F2, F3, A):
+        raise ValueError("no fused critic kernel for input_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d" % (IN, F1, F2, F3, A))
+    if tuple(b1.shape) != (F1,) or tuple(W2.shape) != (F2, F1) or tuple(Wav.shape) != (F2, A) or tuple(W3.shape) != (F3, F2):
+        raise ValueError("pack_critic_weights: the weights' shapes do not chain")
+    g = critic_geom(IN, F1, F2, F3, A)
+    dev = W1.device
+    # fc1 operand [F1, 16 KS]: column k < IN the centred weight, column IN the centred bias
+    x1 = torch.zeros(F1, 16 * g.ks, dtype=torch.float64, device=dev)
+    x1[:, :IN + 1] = centre_fc1(W1, b1).T
+    h1, l1, u1 = _split_scaled(x1)
+    # (t, g, r, s, h, j) -> (g, s, t, h, r, j): row (g KS + s) 2 + t, lane = 32 h + r
+    f1 = torch.stack([h1, l1], 0).reshape(2, g.ng, 32, g.ks, 2, 8).permute(1, 3, 0, 4, 2, 5).reshape(-1, 64, 8)
+    wa = torch.zeros(16 * g.ksa, F2, dtype=torch.float32, device=dev)
+    wa[:A] = Wav.T
+    ha, la, ua = _split_scaled(wa)
+    h2, l2, u2 = _split_scaled(W2.T)
+    h3, l3, u3 = _split_scaled(W3.T)
+    stream = torch.cat([_by_wave(_frags(ha, la, "nat"), g.mt2), f1, _by_wave(_frags(h2, l2, "cd"), g.mt2),
+                        _by_wave(_frags(h3, l3, "cd"), g.mt3)], 0).contiguous()
+    assert stream.shape[0] == g.rows
+    return stream, torch.stack([u1, u2, ua, u3]).float().contiguous()
+
+
+def unpack_critic_weights(stream: torch.Tensor, scales: torch.Tensor, input_dims: int, fc1_dims: int, fc2_dims: int,
+                          fc3_dims: int, n_actions: int) -> dict:
+    """What the kernel multiplies by, as float64: {"fc1" [input_dims + 1, fc1] (centred, the bias last), "fc2" [fc1, fc2],
+    "action_value" [n_actions, fc2], "fc3" [fc2, fc3]} -- hi + lo with the recorded scale undone.  The inverse of
+    `pack_critic_weights` up to the split's rounding."""
+    g = critic_geom(input_dims, fc1_dims, fc2_dims, fc3_dims, n_actions)
+    s, sc = stream.cpu(), scales.cpu().double()
+    f = s[g.fc1:g.fc2].double().reshape(g.ng, g.ks, 2, 2, 32, 8)      # (g, s, t, h, r, j)
+    x1 = (f[:, :, 0] + f[:, :, 1]).permute(0, 3, 1, 2, 4).reshape(32 * g.ng, 16 * g.ks)   # (g, r, s, h, j)
+    return {"fc1": (x1 * sc[0]).T[:input_dims + 1].contiguous(),
+            "fc2": _unfrags(_from_wave(s[g.fc2:g.fc3], g.mt2, 2 * g.ng), "cd") * sc[1],
+            "action_value": (_unfrags(_from_wave(s[g.av:g.fc1], g.mt2, g.ksa), "nat") * sc[2])[:n_actions].contiguous(),
+            "fc3": _unfrags(_from_wave(s[g.fc3:g.rows], g.mt3, 8 * g.mt2), "cd") * sc[3]}
+
+
+class BatchedCritic:
+    """`CriticNetwork` (NET:9-79) for n rows at once.  `input_dims` is the flattened state width, n_agents x per-agent
+    width (NET:19); the output is q [n, 1]."""
+
+    GEMM_MODES = ("fused", "library")
+    #: with gemm=None, batches of fewer rows than this run the library path even where the fused kernel is built
+    #: (the measured crossover, profiles/sarl_critic.json; 1 = fused at every row count)
+    AUTO_MIN_ROWS = 1
+    _WEIGHTS = ("W1", "b1", "ln1_w", "ln1_b", "W2", "b2", "ln2_w", "ln2_b", "W3", "b3", "ln3_w", "ln3_b", "Wav", "bav", "Wq", "bq")
+    _SD = {"fc1.weight": "W1", "fc1.bias": "b1", "fc2.weight": "W2", "fc2.bias": "b2", "fc3.weight": "W3", "fc3.bias": "b3",
+           "bn1.weight": "ln1_w", "bn1.bias": "ln1_b", "bn2.weight": "ln2_w", "bn2.bias": "ln2_b", "bn3.weight": "ln3_w",
+           "bn3.bias": "ln3_b", "action_value.weight": "Wav", "action_value.bias": "bav", "q.weight": "Wq", "q.bias": "bq"}
+    _PACKED = ("W1", "b1", "W2", "Wav", "W3")                 # what the weight stream is built from
+
+    def __init__(self, input_dims: int, n_actions: int, fc1_dims: int = 1024, fc2_dims: int = 512, fc3_dims: int = 256,
+                 device="cuda", seed: int = 0, gemm: Optional[str] = None):
+        """gemm: how `forward` / `td_target` run.  "fused": one hand-written MFMA launch (`risvec_sarl_critic`: float16
+        hi + lo split products at float32 accuracy, the hidden layers never leaving the chip); built for input_dims <=
+        128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}, n_actions <= 96.  "library": `q_torch`,
+        the same forward with library kernels only -- the fallback for every other shape and the comparator.
+        Default (None): fused where built, for batches of at least `AUTO_MIN_ROWS` rows; library otherwise."""
+        lib = N.load()
+        self.device = N.resolve_device(device)
+        N.require_hip(self.device)
+        self.input_dims, self.n_actions = int(input_dims), int(n_actions)
+        self.fc1_dims, self.fc2_dims, self.fc3_dims = int(fc1_dims), int(fc2_dims), int(fc3_dims)
+        dims = (self.input_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims, self.n_actions)
+        if min(dims) < 1:
+            raise ValueError("BatchedCritic: every dimension must be >= 1")
+        fused_ok = bool(lib.risvec_sarl_critic_supported(*dims))
+        self.gemm = gemm if gemm is not None else ("fused" if fused_ok else "library")
+        if self.gemm not in self.GEMM_MODES or (self.gemm == "fused" and not fused_ok):
+            raise ValueError("gemm=%r is not available for input_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d (modes: %s; fused: "
+                             "input_dims <= 128, fc1 %% 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}, "
+                             "n_actions <= 96)" % ((gemm,) + dims + (", ".join(self.GEMM_MODES),)))
+        self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
+        self._packed = (None, None)                           # (key, (wstream, scales))
+        self.packs = 0                                        # how often the weight stream was rebuilt
+        dev = self.device
+        g = torch.Generator(device="cpu").manual_seed(seed)
+
+        def uni(*shape, r):
+            return ((torch.rand(*shape, generator=g) * 2 - 1) * r).to(dev)
+        f1, f2, f3 = 1.0 / math.sqrt(self.fc1_dims), 1.0 / math.sqrt(self.fc2_dims), 1.0 / math.sqrt(self.fc3_dims)   # NET:40-58
+        self.W1, self.b1 = uni(self.fc1_dims, self.input_dims, r=f1), uni(self.fc1_dims, r=f1)
+        self.W2, self.b2 = uni(self.fc2_dims, self.fc1_dims, r=f2), uni(self.fc2_dims, r=f2)
+        self.W3, self.b3 = uni(self.fc3_dims, self.fc2_dims, r=f3), uni(self.fc3_dims, r=f3)
+        self.Wq, self.bq = uni(1, self.fc3_dims, r=0.003), uni(1, r=0.003)
+        self.Wav, self.bav = uni(self.fc2_dims, self.n_actions, r=f2), uni(self.fc2_dims, r=f2)
+        for i, f in ((1, self.fc1_dims), (2, self.fc2_dims), (3, self.fc3_dims)):
+            setattr(self, "ln%d_w" % i, torch.ones(f, device=dev))
+            setattr(self, "ln%d_b" % i, torch.zeros(f, device=dev))
+
+    # ------------------------------------------------------------------ weights
+    def state_dict(self) -> dict:
+        """The reference's `CriticNetwork.state_dict()` keys (fc1.* fc2.* fc3.* bn1.* bn2.* bn3.* action_value.* q.*), CPU
+        copies."""
+        return {k: getattr(self, a).detach().cpu().clone() for k, a in self._SD.items()}
+
+    def load_state_dict(self, sd: Mapping[str, object]) -> None:
+        """Take the weights of a reference `CriticNetwork.state_dict()` as it is (tensors or arrays; `critic` and
+        `target_critic` checkpoints alike).  Load checkpoints with `torch.load(..., weights_only=True)`."""
+        new = {}
+        for k, a in self._SD.items():
+            if k not in sd:
+                raise KeyError("load_state_dict: %r is missing" % k)
+            t = torch.as_tensor(sd[k], dtype=torch.float32)
+            if tuple(t.shape) != tuple(getattr(self, a).shape):
+                raise ValueError("load_state_dict: %s has shape %s, this critic's is %s"
+                                 % (k, tuple(t.shape), tuple(getattr(self, a).shape)))
+            new[a] = t
+        for a, t in new.items():
+            getattr(self, a).copy_(t.to(self.device))
+
+    def share_state_dict(self, sd: Mapping[str, torch.Tensor]) -> None:
+        """Use the learner's own tensors as this critic's weights, by reference (reference key names; typically
+        `agent.target_critic.state_dict()`): nothing is copied, now or later.  An in-place update of them is seen through
+        their version counters, and the next call rebuilds the weight stream first.  Tensors must be float32, contiguous,
+        on this critic's device and of this critic's shapes."""
+        new = {}
+        for k, a in self._SD.items():
+            if k not in sd:
+                raise KeyError("share_state_dict: %r is missing" % k)
+            t, shape = sd[k], tuple(getattr(self, a).shape)
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device
+                    or not t.is_contiguous() or tuple(t.shape) != shape):
+                raise ValueError("share_state_dict: %s must be a contiguous float32 tensor of shape %s on %s (it is used in "
+                                 "place; load_state_dict copies and converts)" % (k, shape, self.device))
+            new[a] = t.detach()                               # the same storage and version counter
+        for a, t in new.items():
+            setattr(self, a, t)
+
+    def _fused_weights(self):
+        """(wstream, scales) of `risvec_sarl_critic`, rebuilt when a packed weight tensor is replaced or updated in place
+        (host packing: library kernels into new tensors)."""
+        ws = tuple(getattr(self, a) for a in self._PACKED)
+        key = tuple((t.data_ptr(), t._version) for t in ws)
+        if self._packed[0] != key:
+            self._packed = (key, pack_critic_weights(*ws))
+            self.packs += 1
+        return self._packed[1]
+
+    # ------------------------------------------------------------------ forward
+    def _rows(self, state, action) -> int:
+        dev = self.device
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float32 or state.device != dev
+                or not state.is_contiguous() or state.dim() not in (2, 3) or state.shape[0] < 1
+                or state.numel() != state.shape[0] * self.input_dims):
+            raise ValueError("state must be a contiguous float32 tensor [n, %d] or [n, V, %d / V] on %s"
+                             % (self.input_dims, self.input_dims, dev))
+        n = int(state.shape[0])
+        if action is None:
+            raise ValueError("action must be a contiguous float32 tensor [n, %d] on %s" % (self.n_actions, dev))
+        N.in_place(action, torch.float32, (n, self.n_actions), "action", dev)
+        return n
+
+    def _fused(self, n: int) -> bool:
+        return self.gemm == "fused" and n >= self.fused_min_rows
+
+    def _launch(self, n, state, action, reward, done, gamma, q, y) -> None:
+        ws, scales = self._fused_weights()
+        p = lambda t: t.data_ptr()   # noqa: E731
+        N.check(N.load().risvec_sarl_critic(
+            n, self.input_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims, self.n_actions, p(state), p(action), p(ws),
+            ws.numel() * ws.element_size(), p(scales), p(self.ln1_w), p(self.ln1_b), p(self.b2), p(self.ln2_w), p(self.ln2_b),
+            p(self.bav), p(self.b3), p(self.ln3_w), p(self.ln3_b), p(self.Wq), p(self.bq), N.ptr(reward), N.ptr(done),
+            float(gamma), N.ptr(q), N.ptr(y), N.stream(self.device)))
+
+    def forward(self, state: torch.Tensor, action: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """NET:66-79 for every row: state [n, input_dims] or [n, V, input_dims / V], action [n, n_actions], both read in
+        place -> q [n, 1].  `out`: a caller-owned [n, 1] tensor written in place."""
+        n, dev = self._rows(state, action), self.device
+        if out is None:
+            out = torch.empty(n, 1, device=dev)
+        N.in_place(out, torch.float32, (n, 1), "forward: out", dev)
+        if not self._fused(n):
+            return out.copy_(self.q_torch(state.view(n, self.input_dims), action))
+        self._launch(n, state, action, None, None, 0.0, out, None)
+        return out
+
+    __call__ = forward
+
+    def td_target(self, reward: torch.Tensor, state_: torch.Tensor, action_: torch.Tensor, done: torch.Tensor,
+                  gamma: float = 0.99, out: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ddpg_torch.py:81, 84-87 in the same launch as the forward: y [n] = reward where done, reward + gamma Q(state_,
+        action_) elsewhere (a select, as `critic_value_[done] = 0.0` is).  reward [n] float32, done [n] bool or uint8 (0 / 1),
+        all read in place; `out`: a caller-owned [n] tensor for y; `q`: a caller-owned [n, 1] tensor that receives
+        Q(state_, action_)."""
+        n, dev = self._rows(state_, action_), self.device
+        if reward is None:
+            raise ValueError("td_target: reward must be a contiguous float32 tensor of shape (%d,) on %s" % (n, dev))
+        N.in_place(reward, torch.float32, (n,), "td_target: reward", dev)
+        if (not isinstance(done, torch.Tensor) or done.dtype not in (torch.bool, torch.uint8) or done.device != dev
+                or not done.is_contiguous() or tuple(done.shape) != (n,)):
+            raise ValueError("td_target: done must be a contiguous bool or uint8 tensor of shape (%d,) on %s" % (n, dev))
+        if not math.isfinite(float(gamma)):
+            raise ValueError("td_target: gamma must be finite")
+        if out is None:
+            out = torch.empty(n, device=dev)
+        N.in_place(out, torch.float32, (n,), "td_target: out", dev)
+        N.in_place(q, torch.float32, (n, 1), "td_target: q", dev)
+        if not self._fused(n):
+            qv = self.q_torch(state_.view(n, self.input_dims), action_)
+            if q is not None:
+                q.copy_(qv)
+            return out.copy_(torch.where(done.view(torch.bool) if done.dtype == torch.uint8 else done, reward,
+                                         reward + float(gamma) * qv.view(n)))
+        d8 = done.view(torch.uint8) if done.dtype == torch.bool else done
+        self._launch(n, state_, action_, reward, d8, gamma, q, out)
+        return out
+
+    def q_torch(self, x: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+        F = torch.nn.functional
+        s = torch.relu(F.layer_norm(F.linear(x, self.W1, self.b1), (self.fc1_dims,), self.ln1_w, self.ln1_b, 1e-5))
+        s = F.layer_norm(F.linear(s, self.W2, self.b2), (self.fc2_dims,), self.ln2_w, self.ln2_b, 1e-5)
+        h = torch.relu(torch.add(s, F.linear(a, self.Wav, self.bav)))
+        h = torch.relu(F.layer_norm(F.linear(h, self.W3, self.b3), (self.fc3_dims,), self.ln3_w, self.ln3_b, 1e-5))
+        return F.linear(h, self.Wq, self.bq)
+
+    def forward_torch(self, state: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+        """The same forward with library kernels only (torch.nn.functional.linear / layer_norm): what gemm="library" runs."""
+        return self.q_torch(state.reshape(state.shape[0], self.input_dims), action)
+
+
+def ddpg_td_target(target_actor, target_critic: BatchedCritic, states_: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor,
+                   gamma: float, out: Optional[torch.Tensor] = None, actions_: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ddpg_torch.py:80-81, 84-87 as two launches: `target_actor.forward(states_, out=actions_)` (a `BatchedActor`), then
+    `target_critic.td_target(rewards, states_, target_actions, dones, gamma, out=out)`.  The tensors
+    `SarlReplayBuffer.sample_buffer` returned are read in place; `actions_` [n, n_actions] and `out` [n] are optional
+    caller-owned buffers.  Returns y [n]; `target.view(batch, 1)` (:88) is a view of it."""
+    target_actions = target_actor.forward(states_, out=actions_)
+    return target_critic.td_target(rewards, states_, target_actions, dones, gamma, out=out)

@@ -965,6 +965,42 @@ int risvec_sarl_actor_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_
                                                      scales, workspace, (hipStream_t)stream));
 }
 
+int risvec_sarl_critic_supported(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions) {
+    return risvec::sarl_critic_supported(in_dims, fc1, fc2, fc3, n_actions) ? 1 : 0;
+}
+
+int64_t risvec_sarl_critic_stream_bytes(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions) {
+    return risvec::sarl_critic_stream_bytes(in_dims, fc1, fc2, fc3, n_actions);
+}
+
+int risvec_sarl_critic(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions, const float* x,
+                       const float* a, const void* wstream, int64_t wstream_bytes, const float* scales, const float* ln1_w,
+                       const float* ln1_b, const float* b2, const float* ln2_w, const float* ln2_b, const float* bav,
+                       const float* b3, const float* ln3_w, const float* ln3_b, const float* q_w, const float* q_b,
+                       const float* reward, const uint8_t* done, float gamma, float* q_out, float* y_out,
+                       risvec_stream_t stream) {
+    const char* fn = "risvec_sarl_critic";
+    if (n_rows < 1) return fail(RISVEC_ERR_SHAPE, "%s: n_rows=%d must be >= 1", fn, n_rows);
+    if (!risvec::sarl_critic_supported(in_dims, fc1, fc2, fc3, n_actions))
+        return fail(RISVEC_ERR_SHAPE, "%s: in_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d (built for in_dims <= 128, fc1 a multiple "
+                    "of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256, n_actions <= 96; use library kernels elsewhere)",
+                    fn, in_dims, fc1, fc2, fc3, n_actions);
+    const long long need = risvec::sarl_critic_stream_bytes(in_dims, fc1, fc2, fc3, n_actions);
+    if (wstream_bytes != need)
+        return fail(RISVEC_ERR_ARG, "%s: wstream_bytes=%lld, this shape's weight stream has %lld", fn, (long long)wstream_bytes, need);
+    if (!x || !a) return fail(RISVEC_ERR_ARG, "%s: x or a is NULL", fn);
+    REQ_PTR(wstream, "wstream"); REQ_PTR(scales, "scales"); REQ_PTR(ln1_w, "ln1_w"); REQ_PTR(ln1_b, "ln1_b"); REQ_PTR(b2, "b2");
+    REQ_PTR(ln2_w, "ln2_w"); REQ_PTR(ln2_b, "ln2_b"); REQ_PTR(bav, "bav"); REQ_PTR(b3, "b3"); REQ_PTR(ln3_w, "ln3_w");
+    REQ_PTR(ln3_b, "ln3_b"); REQ_PTR(q_w, "q_w");
+    if (!q_b) return fail(RISVEC_ERR_ARG, "%s: q_b is NULL", fn);
+    if (!q_out && !y_out) return fail(RISVEC_ERR_ARG, "%s: q_out and y_out are both NULL", fn);
+    if (y_out && (!reward || !done)) return fail(RISVEC_ERR_ARG, "%s: y_out needs reward and done", fn);
+    if (y_out && !std::isfinite(gamma)) return fail(RISVEC_ERR_ARG, "%s: gamma=%g must be finite", fn, (double)gamma);
+    return finish(fn, risvec::launch_sarl_critic(n_rows, in_dims, fc1, fc2, fc3, n_actions, x, a, wstream, scales, ln1_w, ln1_b, b2,
+                                                 ln2_w, ln2_b, bav, b3, ln3_w, ln3_b, q_w, q_b, reward, done, gamma, q_out, y_out,
+                                                 (hipStream_t)stream));
+}
+
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float* g, const float* b2,
                         const float* ln_w, const float* ln_b, const float* Wh, const float* bh, float* heads,
                         risvec_stream_t stream) {

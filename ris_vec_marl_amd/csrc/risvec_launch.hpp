@@ -96,6 +96,16 @@ hipError_t launch_sarl_actor_pack(int IN, int F1, int F2, int A, const float* W1
                                   const float* ln1b, const float* W2, const float* Wmu, void* wstream, float* scales,
                                   void* workspace, hipStream_t st);
 
+// The DDPG critic forward and TD target in one launch (k_sarl_critic.hip).  sarl_critic_stream_bytes(): the size of its
+// weight stream for a supported shape (0 otherwise).  reward / done are read only when y is given; q and y are optional.
+bool sarl_critic_supported(int IN, int F1, int F2, int F3, int A);
+long long sarl_critic_stream_bytes(int IN, int F1, int F2, int F3, int A);
+hipError_t launch_sarl_critic(long long n_rows, int IN, int F1, int F2, int F3, int A, const float* x, const float* a,
+                              const void* wstream, const float* scales, const float* ln1w, const float* ln1b, const float* b2,
+                              const float* ln2w, const float* ln2b, const float* bav, const float* b3, const float* ln3w,
+                              const float* ln3b, const float* qw, const float* qb, const float* reward, const uint8_t* done,
+                              float gamma, float* q, float* y, hipStream_t st);
+
 int episode_partial_rows(int E);
 hipError_t launch_episode_clear(int E, int V, double* acc, hipStream_t st);
 hipError_t launch_episode_accumulate(int E, int V, const float* metrics, const float* reward, const float* power_w,

@@ -1,0 +1,192 @@
+"""CPU-side tests of the DDPG critic forward (`BatchedCritic`, `risvec_sarl_critic`): the shape rule, the argument checks
+of the C entry point (which must answer before touching a device), the weight packing -- a pure function that runs on
+CPU tensors -- and the float64 restatement the GPU tests measure against, checked here against the vectors captured
+from the reference's own network."""
+import ctypes as C
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from ris_vec_marl_amd import _native as N
+from ris_vec_marl_amd import critic as CR
+from tests import sarl_critic_ref as R
+
+# (in, fc1, fc2, fc3, n_actions): the driver's two, the fixtures' two, the corners of the rule
+SHAPES = [(80, 1024, 512, 256, 56), (104, 1024, 512, 256, 80), (80, 96, 128, 128, 56), (36, 64, 128, 128, 24),
+          (128, 1024, 512, 256, 96), (5, 32, 128, 128, 1), (79, 160, 256, 128, 33)]
+SMALL = [s for s in SHAPES if s[1] <= 160]
+
+
+def test_supported_rule_agrees_with_the_library_over_a_grid():
+    lib = N.load()
+    grid = itertools.product((0, 1, 80, 128, 129), (0, 32, 48, 96, 1024, 1056), (64, 128, 256, 384, 512, 1024),
+                             (64, 128, 192, 256, 512), (0, 1, 56, 96, 97))
+    n_ok = 0
+    for dims in grid:
+        ok = bool(lib.risvec_sarl_critic_supported(*dims))
+        assert ok == CR._supported(*dims), dims
+        assert (lib.risvec_sarl_critic_stream_bytes(*dims) != 0) == ok, dims
+        n_ok += ok
+    assert n_ok == 3 * 3 * 3 * 2 * 3
+    for dims in SHAPES:
+        assert lib.risvec_sarl_critic_supported(*dims) == 1 and CR._supported(*dims)
+
+
+def test_library_declares_and_exports_the_critic():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "risvec.h")).read()
+    lib = N.load()
+    for name in ("risvec_sarl_critic_supported", "risvec_sarl_critic_stream_bytes", "risvec_sarl_critic"):
+        assert name in N.EXPORTS and hasattr(lib, name)
+        assert re.search(r"\b%s\(" % name, header)
+
+
+def test_entry_point_rejects_bad_arguments_without_a_device():
+    lib = N.load()
+    buf = (C.c_float * 64)()                                  # host memory: never dereferenced, only checked
+    p = C.addressof(buf) + (-C.addressof(buf)) % 16
+    dims = (80, 1024, 512, 256, 56)
+    nbytes = lib.risvec_sarl_critic_stream_bytes(*dims)
+    names = ("x", "a", "ws", "sc", "l1w", "l1b", "b2", "l2w", "l2b", "bav", "b3", "l3w", "l3b", "qw", "qb")
+
+    def call(n=4, dims=dims, wb=nbytes, rw=p, dn=p, gamma=0.99, q=p, y=p, **kw):
+        a = {k: kw.get(k, p) for k in names}
+        return lib.risvec_sarl_critic(n, *dims, a["x"], a["a"], a["ws"], wb, a["sc"], a["l1w"], a["l1b"], a["b2"], a["l2w"],
+                                      a["l2b"], a["bav"], a["b3"], a["l3w"], a["l3b"], a["qw"], a["qb"], rw, dn, gamma, q, y, None)
+    assert call(n=0) == N.ERR_SHAPE
+    for bad in ((144, 1024, 512, 256, 56), (80, 1000, 512, 256, 56), (80, 1024, 384, 256, 56), (80, 1024, 512, 512, 56),
+                (80, 1024, 512, 256, 97)):
+        assert call(dims=bad) == N.ERR_SHAPE
+        assert b"risvec_sarl_critic" in lib.risvec_last_error()
+    assert call(wb=nbytes - 1024) == N.ERR_ARG                # a stream packed for another shape
+    for name in names:
+        assert call(**{name: None}) == N.ERR_ARG, name
+    assert call(l2w=p + 4) == N.ERR_ARG                       # not 16-byte aligned
+    assert call(q=None, y=None) == N.ERR_ARG                  # at least one output
+    assert call(rw=None) == N.ERR_ARG and call(dn=None) == N.ERR_ARG          # y needs reward and done
+    assert call(gamma=float("nan")) == N.ERR_ARG
+
+
+def torch_weights(dims, seed, scale=1.0):
+    w = R.random_critic(dims, seed)
+    t = lambda k: torch.from_numpy(w[k])                      # noqa: E731
+    return w, dict(W1=t("fc1.weight") * scale, b1=t("fc1.bias") * scale, W2=t("fc2.weight"), Wav=t("action_value.weight"),
+                   W3=t("fc3.weight"))
+
+
+@pytest.mark.parametrize("dims", SHAPES)
+@pytest.mark.parametrize("scale", [1.0, 1e-3])
+def test_packing_round_trip_and_stream_size(dims, scale):
+    """hi + lo with the recorded scale reproduce every float32 weight to 2^-21 of the matrix's largest entry (the split
+    keeps 22 bits below the largest entry's exponent); the stream has the byte size the header states."""
+    _, tw = torch_weights(dims, 3, scale)
+    stream, scales = CR.pack_critic_weights(**tw)
+    g = CR.critic_geom(*dims)
+    IN, F1, F2, F3, A = dims
+    assert g.rows == 4 * g.ksa * g.mt2 * 2 + g.ng * g.ks * 2 + 4 * 2 * g.ng * g.mt2 * 2 + 4 * (F2 // 16) * g.mt3 * 2
+    assert (g.ks, g.ksa, g.ng, g.mt2, g.mt3) == (-(-(IN + 1) // 16), -(-A // 16), F1 // 32, F2 // 128, F3 // 128)
+    assert stream.dtype == torch.float16 and tuple(stream.shape) == (g.rows, 64, 8) and stream.is_contiguous()
+    assert stream.numel() * 2 == N.load().risvec_sarl_critic_stream_bytes(*dims) == g.rows * 1024
+    # the kernel's LDS: input fragments + the widest activation + the reduction slots, within the 160 KiB of a CU
+    assert (g.ks + max(g.ksa, 2 * g.ng, F2 // 16)) * 2048 + 6 * 4 * 32 * 4 <= 160 * 1024
+    assert tuple(scales.shape) == (4,) and scales.dtype == torch.float32
+    assert all(float(torch.log2(s)) == round(float(torch.log2(s))) for s in scales)       # powers of two
+    un = CR.unpack_critic_weights(stream, scales, *dims)
+    want = {"fc1": CR.centre_fc1(tw["W1"], tw["b1"]), "fc2": tw["W2"].double().T, "action_value": tw["Wav"].double().T,
+            "fc3": tw["W3"].double().T}
+    assert set(un) == set(want)
+    for k in want:
+        assert un[k].shape == want[k].shape, k
+        assert float((un[k] - want[k]).abs().max()) <= 2.0 ** -21 * float(want[k].abs().max()), k
+
+
+@pytest.mark.parametrize("dims", SHAPES)
+def test_fc1_operand_columns_sum_to_zero(dims):
+    _, tw = torch_weights(dims, 5)
+    c = CR.centre_fc1(tw["W1"], tw["b1"])
+    assert float(c.sum(-1).abs().max()) <= dims[1] * 2.0 ** -52 * float(c.abs().max())
+    # what the kernel multiplies by: the split's rounding, at most 2^-22 of the largest entry per term
+    un = CR.unpack_critic_weights(*CR.pack_critic_weights(**tw), *dims)
+    assert float(un["fc1"].sum(-1).abs().max()) <= dims[1] * 2.0 ** -22 * float(c.abs().max())
+
+
+def test_packing_refuses_unsupported_shapes():
+    _, tw = torch_weights((80, 96, 128, 128, 56), 1)
+    bad = dict(tw, W2=torch.zeros(64, 96), Wav=torch.zeros(64, 56), W3=torch.zeros(128, 64))       # fc2 = 64
+    with pytest.raises(ValueError):
+        CR.pack_critic_weights(**bad)
+    with pytest.raises(ValueError):
+        CR.pack_critic_weights(**dict(tw, W3=torch.zeros(128, 256)))                               # does not chain
+
+
+@pytest.mark.parametrize("name", ["sarl_critic_8_40", "sarl_critic_4_16"])
+def test_float64_restatement_is_the_references_network(name):
+    """q and target of the fixtures (the reference's own float32 forward and its own target statements) against the
+    float64 restatement: err < 2e-5, done rows equal the reward bit for bit; the fixture is shaped as the issue asks."""
+    fx = R.fixture(name)
+    w, aw = R.weights_of(fx), R.weights_of(fx, "aw.")
+    assert set(w) == set(CR.BatchedCritic._SD)
+    done = fx["done"]
+    assert done.dtype == np.bool_ and done.sum() >= 5 and (~done).sum() >= 5
+    assert not fx["state"][0].any() and fx["state"][1].any()
+    B = int(fx["B"])
+    assert (np.abs(fx["action"][:B // 2]).max() <= 0.999 and fx["action"][:B // 2].min() < 0) and fx["action"][B // 2:].min() >= 0
+    e_q = R.err(fx["q"], R.critic_q64(w, fx["state"], fx["action"]))
+    mu64 = R.actor_mu64(aw, fx["state_"])
+    e_mu = float(np.abs(fx["target_action"] - mu64).max())
+    q_next64 = R.critic_q64(w, fx["state_"], mu64)
+    e_qn = R.err(fx["q_next"], q_next64)
+    y64 = R.td_target64(fx["reward"], q_next64, done, float(fx["gamma"]))
+    e_y = R.err(fx["target"], y64)
+    print("%s: the reference's float32 against float64: q %.3g, target action %.3g, Q(s', a') %.3g, target %.3g" % (name, e_q, e_mu, e_qn, e_y))
+    assert e_q < R.BAR and e_qn < R.BAR and e_y < R.BAR and e_mu < R.BAR
+    assert np.array_equal(fx["target"].reshape(-1)[done], fx["reward"][done])
+    assert float(np.abs(fx["q"]).max()) > 0.3
+
+
+@pytest.mark.parametrize("dims", SMALL)
+def test_numpy_walk_of_the_packed_stream(dims):
+    """The packed stream walked through the kernel's data flow in NumPy (fragment addressing, the C/D -> B hand-over
+    through LDS, the four-way feature split, split activations, three partial products) against float64.  What is left
+    is the split's rounding: 2^-22 per product, far inside the bar."""
+    w, tw = torch_weights(dims, 11)
+    stream, scales = CR.pack_critic_weights(**tw)
+    state, action = R.random_batch(dims, 37, 12)
+    got = R.walk_stream(stream.numpy(), scales.numpy(), w, state, action, dims, CR.critic_geom(*dims))
+    e = R.err(got, R.critic_q64(w, state, action))
+    print("walk %s: err %.3g" % (dims, e))
+    assert e < 1e-6
+
+
+def test_batched_critic_is_exported_and_needs_a_device():
+    import ris_vec_marl_amd as rv
+    for name in ("BatchedCritic", "ddpg_td_target", "pack_critic_weights", "unpack_critic_weights"):
+        assert getattr(rv, name) is getattr(CR, name) and name in rv.__all__
+    assert set(CR.BatchedCritic._SD) == {p + s for p in ("fc1.", "fc2.", "fc3.", "bn1.", "bn2.", "bn3.", "action_value.", "q.")
+                                         for s in ("weight", "bias")}
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError):
+            rv.BatchedCritic(80, 56, device="cpu")
+
+
+def test_load_state_dict_takes_the_fixture_and_rejects_a_wrong_shape():
+    """Built without a device: the checks of load_state_dict come before any copy."""
+    fx = R.fixture("sarl_critic_4_16")
+    sd = R.weights_of(fx)
+    c = CR.BatchedCritic.__new__(CR.BatchedCritic)
+    c.device = torch.device("cpu")
+    for k, a in CR.BatchedCritic._SD.items():
+        setattr(c, a, torch.zeros(*sd[k].shape))
+    c.load_state_dict(sd)
+    assert all(np.array_equal(v.numpy(), sd[k]) for k, v in c.state_dict().items())
+    bad = dict(sd)
+    bad["fc2.weight"] = sd["fc2.weight"].T.copy()             # [in, out] instead of the reference's [out, in]
+    with pytest.raises(ValueError):
+        c.load_state_dict(bad)
+    del bad["fc2.weight"]
+    with pytest.raises(KeyError):
+        c.load_state_dict(bad)
