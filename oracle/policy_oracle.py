@@ -50,16 +50,13 @@ def mask_logits(logits: np.ndarray, mask: Optional[np.ndarray]) -> np.ndarray:
     return np.where(m <= 0, FP32_MIN_HALF, logits)
 
 
-def choose_action(wts: Dict[str, np.ndarray], state: np.ndarray, mask: Optional[np.ndarray], tau: float,
-                  eps: np.ndarray, expo: np.ndarray, hard: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """SAC:187-225 -> (power_action [B,2], intent_probs [B,N], intent_onehot [B,N]).  `hard`: the
-    straight-through form `y_hard - y_soft + y_soft` of F.gumbel_softmax(hard=True) (SAC:110-113 with
-    `gumbel_hard`, switched on by the driver at TRAIN:1816-1818), evaluated in float32 like the reference
-    because its value IS the float32 rounding of that expression."""
-    mu, log_std, logits = forward(wts, state)
-    x_t = mu + np.exp(log_std) * np.asarray(eps, dtype=np.float64)        # Normal(mu, std).sample()
+def sample_heads(mu: np.ndarray, log_std: np.ndarray, logits: np.ndarray, mask: Optional[np.ndarray], tau: float,
+                 eps: np.ndarray, expo: np.ndarray, hard: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Everything of `choose_action` after the forward, on given head outputs (SAC:72, 83-86, 91-113, 215-216)."""
+    log_std = np.clip(np.asarray(log_std, dtype=np.float64), -20.0, 2.0)                      # SAC:72 (idempotent)
+    x_t = np.asarray(mu, dtype=np.float64) + np.exp(log_std) * np.asarray(eps, dtype=np.float64)   # Normal(mu, std).sample()
     power = np.tanh(x_t)
-    ml = mask_logits(logits, mask)
+    ml = mask_logits(np.asarray(logits, dtype=np.float64), mask)
     g = (ml + -np.log(np.asarray(expo, dtype=np.float64))) / float(tau)  # gumbel_softmax, soft (SAC:110-113)
     g = g - g.max(-1, keepdims=True)
     y = np.exp(g)
@@ -70,6 +67,41 @@ def choose_action(wts: Dict[str, np.ndarray], state: np.ndarray, mask: Optional[
         y32 = y.astype(np.float32)
         y = ((onehot.astype(np.float32) - y32) + y32).astype(np.float64)
     return power, y, onehot
+
+
+def choose_action(wts: Dict[str, np.ndarray], state: np.ndarray, mask: Optional[np.ndarray], tau: float,
+                  eps: np.ndarray, expo: np.ndarray, hard: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """SAC:187-225 -> (power_action [B,2], intent_probs [B,N], intent_onehot [B,N]).  `hard`: the
+    straight-through form `y_hard - y_soft + y_soft` of F.gumbel_softmax(hard=True) (SAC:110-113 with
+    `gumbel_hard`, switched on by the driver at TRAIN:1816-1818), evaluated in float32 like the reference
+    because its value IS the float32 rounding of that expression."""
+    mu, log_std, logits = forward(wts, state)
+    return sample_heads(mu, log_std, logits, mask, tau, eps, expo, hard)
+
+
+SITE_POLICY_EPS, SITE_POLICY_GUMBEL = 9, 10
+EXPO_FLOOR = 2.0 ** -24
+
+
+def philox_draws(env_ids: np.ndarray, V: int, call: int, seed: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(eps [E,V,2], expo [E,V,V]) float64 exactly as `k_policy_sample` (csrc/k_policy.hip) draws them on call
+    number `call`: eps = normal2(.x, .y) of the block at (global env id, agent, call, site 9); expo[..., k] from word
+    k & 3 of the block at site 10 + 0x100 (k >> 2): -ln(u), u = ((x >> 8) + 1) 2^-24 in (0, 1].  u == 1 would give
+    Exp(1) = 0 and a Gumbel of +inf; as torch's device sampler does for `exponential_()` (what F.gumbel_softmax draws
+    with), that one case yields 2^-24 instead (ATen/core/TransformationHelper.h: "exponential excludes 0")."""
+    from .risvec_oracle import exp1_from_u32, normal2, philox4x32
+    e = np.asarray(env_ids, dtype=np.uint64)[:, None]
+    v = np.arange(V, dtype=np.uint64)[None, :]
+    c = np.uint64(call & 0xFFFFFFFF)
+    x = philox4x32(e, v, c, np.uint64(SITE_POLICY_EPS), seed)
+    eps = np.stack(normal2(x[0], x[1]), axis=-1)
+    expo = np.empty((e.shape[0], V, V))
+    for sub in range((V + 3) // 4):
+        blk = philox4x32(e, v, c, np.uint64(SITE_POLICY_GUMBEL + 0x100 * sub), seed)
+        for w in range(min(4, V - 4 * sub)):
+            expo[:, :, 4 * sub + w] = exp1_from_u32(blk[w])
+    expo[expo == 0.0] = EXPO_FLOOR
+    return eps, expo
 
 
 def top2_gap(y: np.ndarray) -> np.ndarray:

@@ -626,6 +626,22 @@ def u01(x: np.ndarray) -> np.ndarray:
     return ((x >> np.uint32(8)).astype(np.float32)) * np.float32(2.0 ** -24)
 
 
+def normal2(a: np.ndarray, b: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Box-Muller of two Philox words exactly as risvec_dev.hpp::normal2 feeds it: u1 = ((a >> 8) + 1) 2^-24 in
+    (0, 1], u2 = (b >> 8) 2^-24 in [0, 1) (both exact in float32), evaluated in float64:
+    (sqrt(-2 ln u1) cos(2 pi u2), sqrt(-2 ln u1) sin(2 pi u2))."""
+    u1 = ((np.asarray(a, np.uint32) >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    u2 = (np.asarray(b, np.uint32) >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+    rad = np.sqrt(-2.0 * np.log(u1))
+    return rad * np.cos(2.0 * np.pi * u2), rad * np.sin(2.0 * np.pi * u2)
+
+
+def exp1_from_u32(x: np.ndarray) -> np.ndarray:
+    """Exp(1) from the top 24 bits of a Philox word: -ln(((x >> 8) + 1) 2^-24), u in (0, 1] -- so 0 is possible
+    (all-ones top bits).  The 3GPP small-scale power uses it as it stands (a gain of 0)."""
+    return -np.log(((np.asarray(x, np.uint32) >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24)
+
+
 POISSON_TABLE = 64
 
 
@@ -692,6 +708,26 @@ def philox_turn_draws(env_ids: np.ndarray, V: int, counter: int, seed: int) -> n
     a = philox4x32(e, v, np.uint64(counter), np.uint64(SITE_TURN_A), seed)
     b = philox4x32(e, v, np.uint64(counter), np.uint64(SITE_TURN_B), seed)
     return np.stack([u01(x) for x in a + b], axis=-1)
+
+
+def philox_fading(env_ids: np.ndarray, V: int, counter: int, seed: int, rician_K_dB: float
+                  ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(u_los, z_shadow, small) [E,V] float64 exactly as `draws_3gpp` (csrc/risvec_3gpp.hpp) draws them at channel
+    counter `counter`: the block at (global env id, vehicle, counter, SITE_3GPP) gives u = .x (top 24 bits),
+    z = normal2(.y, .z)[0] and, for Rayleigh (rician_K_dB <= 1e-6, compared as the float32 the kernel receives),
+    the Exp(1) power from .w; for Rice the power is rice_power(normal2(.x, .y)) of a second block at SITE_3GPP + 0x100."""
+    e = np.asarray(env_ids, dtype=np.uint64)[:, None]
+    v = np.arange(V, dtype=np.uint64)[None, :]
+    c = np.uint64(counter & 0xFFFFFFFF)
+    x0, x1, x2, x3 = philox4x32(e, v, c, np.uint64(SITE_3GPP), seed)
+    u = u01(x0).astype(np.float64)
+    z = normal2(x1, x2)[0]
+    if np.float32(rician_K_dB) <= np.float32(1e-6):
+        small = exp1_from_u32(x3)
+    else:
+        y0, y1, _, _ = philox4x32(e, v, c, np.uint64(SITE_3GPP + 0x100), seed)
+        small = rice_power(*normal2(y0, y1), float(np.float32(rician_K_dB)))
+    return u, z, small
 
 
 def philox_phase_idx(env_ids: np.ndarray, M: int, counter: int, seed: int, control_bit: int) -> np.ndarray:

@@ -66,7 +66,10 @@ k_policy_sample(PolicyArgs A) {
         else {
             const uint4 r = philox4x32_10(genv, (uint32_t)v, A.counter, kSitePolicyGumbel + 0x100u * (k >> 2), A.seed);
             const uint32_t x = (k & 3) == 0 ? r.x : (k & 3) == 1 ? r.y : (k & 3) == 2 ? r.z : r.w;
-            ex = -logf(((float)(x >> 8) + 1.0f) * 0x1p-24f);          // Exp(1), u in (0, 1]
+            // Exp(1), u in (0, 1].  u == 1 would be 0, its Gumbel +inf and the row inf - inf: as torch's device
+            // exponential_() does (what F.gumbel_softmax draws with, SAC:110-113), that one draw is 2^-24 instead
+            const uint32_t m = x >> 8;
+            ex = m == 0xFFFFFFu ? 0x1p-24f : -logf(((float)m + 1.0f) * 0x1p-24f);
         }
         const float ml = blocked ? -FLT_MAX / 2.0f : h[4 + k];        // torch.finfo(float32).min / 2  (SAC:103)
         z = (ml + -logf(ex)) / A.tau[v];                              // (logits + gumbel) / tau

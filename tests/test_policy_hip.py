@@ -107,7 +107,8 @@ def test_reference_sized_networks_vs_oracle(shape):
 
 def test_full_size_properties_and_philox():
     """E = 32 768 x 8 agents, production draws: probabilities sum to 1, blocked partners get none, the
-    one-hot marks the arg-max, tanh range; the Philox draws are the documented ones (site 9 / 10)."""
+    one-hot marks the arg-max, tanh range; the Philox draws are the documented ones (site 9 / 10); the rows whose
+    Gumbel word gives u == 1 are finite."""
     from ris_vec_marl_amd import BatchedPolicy
     V, E = 8, 32768
     rng = np.random.default_rng(5)
@@ -137,6 +138,21 @@ def test_full_size_properties_and_philox():
         ls = np.clip(heads[a][:, 2:4], -20, 2)
         np.testing.assert_allclose(p[:, a, 0], np.tanh(n0 * np.exp(ls[:, 0]) + heads[a][:, 0]), atol=2e-4)
         np.testing.assert_allclose(p[:, a, 1], np.tanh(n1 * np.exp(ls[:, 1]) + heads[a][:, 1]), atol=2e-4)
+    # the Gumbel words with all-ones top 24 bits at this seed's first call (tests/test_draws_oracle.py): u == 1 draws
+    # Exp(1) = 2^-24 as torch's exponential_() does, not 0 -- a Gumbel of 16.6 instead of +inf and a NaN row
+    for env_id, agent, k in ((192560, 0, 0), (976975, 5, 0), (805036, 5, 2)):
+        edge = BatchedPolicy(V, 5, 512, 256, device=DEV, seed=77, env_offset=env_id - 2)
+        _, y5, oh5 = edge.choose_action(obs[:5])
+        y5 = y5.cpu().numpy()
+        assert np.isfinite(y5).all()
+        np.testing.assert_allclose(y5.sum(-1), 1.0, atol=1e-5)
+        h5 = edge.forward_heads(obs[:5]).cpu().numpy().astype(np.float64)
+        expo = PO.philox_draws(np.arange(env_id - 2, env_id + 3), V, 1, 77)[1]
+        assert expo[2, agent, k] == 2.0 ** -24
+        want = PO.sample_heads(h5[agent][:, 0:2], h5[agent][:, 2:4], h5[agent][:, 4:], None, 2.0, np.zeros((5, 2)),
+                               expo[:, agent])[1]
+        np.testing.assert_allclose(y5[:, agent], want, atol=2e-5)
+        assert oh5.cpu().numpy()[2, agent, k] == 1.0 and want[2, k] > 0.9
 
 
 @pytest.mark.parametrize("gemm", ["fused", "fp16x3", "fp32"])

@@ -130,16 +130,12 @@ def test_ou_noise_injected_draws(E, V, M):
 
 def philox_normals(env_ids, A, counter, seed):
     """z [E, A] as the kernel draws it: Philox4x32-10 at (env id, pair j, counter, site 11; seed); Box-Muller of the
-    block's words (.x, .y) gives elements 2j and 2j + 1.  Evaluated in float64 from the float32 uniforms."""
+    block's words (.x, .y) gives elements 2j and 2j + 1 (`orc.normal2`: float64 from the float32 uniforms)."""
     e = np.asarray(env_ids, dtype=np.uint64)[:, None]
     j = np.arange(A // 2, dtype=np.uint64)[None, :]
     r0, r1, _, _ = orc.philox4x32(e, j, np.uint64(counter), np.uint64(11), seed)
-    u1 = (((r0 >> np.uint32(8)).astype(np.float32) + np.float32(1)) * np.float32(2.0 ** -24)).astype(np.float64)
-    u2 = orc.u01(r1).astype(np.float64)
-    rad = np.sqrt(-2.0 * np.log(u1))
     z = np.empty((e.shape[0], A))
-    z[:, 0::2] = rad * np.cos(2 * np.pi * u2)
-    z[:, 1::2] = rad * np.sin(2 * np.pi * u2)
+    z[:, 0::2], z[:, 1::2] = orc.normal2(r0, r1)
     return z
 
 
