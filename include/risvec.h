@@ -795,6 +795,39 @@ int risvec_sarl_critic(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2
                        const float *b3, const float *ln3_w, const float *ln3_b, const float *q_w, const float *q_b,
                        const float *reward, const uint8_t *done, float gamma, float *q_out, float *y_out,
                        risvec_stream_t stream);
+/* The prepared weights of risvec_sarl_critic, built on the device from the float32 weights as the learner holds them
+ * (Linear weights [out, in]: W1 [fc1, in_dims], b1 [fc1], W2 [fc2, fc1], Wav [fc2, n_actions], W3 [fc3, fc2]), read in
+ * place: call it after every update of the target critic.  Two launches on `stream`, no allocation, no synchronisation.
+ * The first takes, in one workgroup, the float64 mean over the features of every row of [W1^T ; b1] and the largest
+ * magnitude of the centred fc1 operand, and in further workgroups the largest magnitudes of slices of W2, Wav and W3,
+ * one workspace slot per slice (no atomics, nothing to initialise).  The second combines the slots into
+ * s = floor(log2(64 / max(amax, 1e-30))) clamped to [-40, 40] per matrix (quotient and logarithm in float64 for fc1, in
+ * float32 for the others) and writes every 16-byte fragment of the layout above exactly once, padding included (the
+ * buffer may hold anything before the call): centre in float64 (fc1), scale by 2^s, round to float32, S_0 = half(x),
+ * S_1 = half(x - float(S_0)).  Sums run in a fixed order: the same bits on every call.
+ *   W1, b1, W2, Wav, W3     float-aligned (16-byte alignment of W2 and W3 lets their fragments be read as float4);
+ *   wstream, wstream_bytes  the stream to write, 16-byte aligned, and its size = risvec_sarl_critic_stream_bytes(...);
+ *   scales [4]              receives 2^-s of fc1, fc2, action_value and fc3;
+ *   workspace               risvec_sarl_critic_pack_workspace bytes (0: a shape risvec_sarl_critic is not built for),
+ *                           16-byte aligned, of any content; holds the means and the maxima between the launches.
+ * Shapes outside risvec_sarl_critic_supported return RISVEC_ERR_UNSUPPORTED. */
+size_t risvec_sarl_critic_pack_workspace(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions);
+int risvec_sarl_critic_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions, const float *W1,
+                            const float *b1, const float *W2, const float *Wav, const float *W3, void *wstream,
+                            size_t wstream_bytes, float *scales, void *workspace, size_t workspace_bytes,
+                            risvec_stream_t stream);
+/* The Polyak blend of update_network_parameters (Simulation-SARL/ddpg_torch.py:104-130) for n_tensors tensors in ONE
+ * launch, in place:
+ *     target[i][e] = fl32( fl32(tau * online[i][e]) + fl32(one_minus_tau * target[i][e]) )
+ * two rounded products and one rounded sum, never a fused multiply-add: the bits of `tau * a + (1 - tau) * b` on
+ * float32 tensors.  The caller passes one_minus_tau = (float)(1.0 - (double)tau), as that expression computes it.
+ *   online, target, numel   HOST arrays of n_tensors entries (1 <= n_tensors <= 32), copied into the kernel's argument
+ *                           block: device pointers to float32 data, float-aligned, and element counts >= 1.  A pair
+ *                           whose pointers share their offset from a 16-byte boundary is blended 16 bytes at a time.
+ * online[i] == target[i], a NULL entry, a misaligned pointer and a non-finite factor return RISVEC_ERR_ARG; n_tensors
+ * or a numel out of range RISVEC_ERR_SHAPE -- all before any device is touched. */
+int risvec_soft_update(int32_t n_tensors, const float *const *online, float *const *target, const int64_t *numel,
+                       float tau, float one_minus_tau, risvec_stream_t stream);
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float *g, const float *b2,
                         const float *ln_w, const float *ln_b, const float *Wh, const float *bh, float *heads,
                         risvec_stream_t stream);

@@ -235,6 +235,9 @@ _PROTOS = {
     "risvec_sarl_critic_supported": (C.c_int, [C.c_int32] * 5),
     "risvec_sarl_critic_stream_bytes": (C.c_int64, [C.c_int32] * 5),
     "risvec_sarl_critic": (C.c_int, [C.c_int32] * 6 + [_FP, _FP, _FP, C.c_int64] + [_FP] * 14 + [C.c_float, _FP, _FP, _FP]),
+    "risvec_sarl_critic_pack_workspace": (C.c_size_t, [C.c_int32] * 5),
+    "risvec_sarl_critic_pack": (C.c_int, [C.c_int32] * 5 + [_FP] * 6 + [C.c_size_t, _FP, _FP, C.c_size_t, _FP]),
+    "risvec_soft_update": (C.c_int, [C.c_int32, _FP, _FP, _FP, C.c_float, C.c_float, _FP]),
     "risvec_policy_heads": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "risvec_policy_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64, C.c_uint32,
                                        C.c_float, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),

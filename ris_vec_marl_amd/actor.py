@@ -10,8 +10,9 @@ launches, actor and everything else.  No CPU compute path.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
-from typing import Mapping, NamedTuple, Optional, Tuple
+from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -176,6 +177,54 @@ def unpack_actor_weights(stream: torch.Tensor, scales: torch.Tensor, input_dims:
             "ln1_w": ln[:, :32].reshape(-1).double(), "ln1_b": ln[:, 32:64].reshape(-1).double()}
 
 
+def polyak_pairs(target, online, what: str):
+    """[(online tensor, target tensor)] in the order of `target._WEIGHTS` for `target.soft_update_from(online, tau)`:
+    `online` is an object of `target`'s class and shape or a mapping under the reference's key names.  Refuses what
+    `share_state_dict` refuses (KeyError for a missing key, ValueError for a tensor that is not contiguous float32 of
+    the right shape on the target's device) before anything is touched."""
+    names = {a: k for k, a in target._SD.items()}
+    if isinstance(online, Mapping):
+        for k in target._SD:
+            if k not in online:
+                raise KeyError("%s: %r is missing" % (what, k))
+        src = {a: online[names[a]] for a in target._WEIGHTS}
+    elif isinstance(online, type(target)):
+        src = {a: getattr(online, a) for a in target._WEIGHTS}
+    else:
+        raise ValueError("%s: online must be a %s of the same shape or a mapping of its weights under the reference's key names"
+                         % (what, type(target).__name__))
+    pairs = []
+    for a in target._WEIGHTS:
+        t, mine = src[a], getattr(target, a)
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != target.device
+                or not t.is_contiguous() or tuple(t.shape) != tuple(mine.shape)):
+            raise ValueError("%s: %s must be a contiguous float32 tensor of shape %s on %s (it is read in place)"
+                             % (what, names[a], tuple(mine.shape), target.device))
+        if t.data_ptr() == mine.data_ptr():
+            raise ValueError("%s: %s is the target's own tensor" % (what, names[a]))
+        pairs.append((t, mine))
+    return pairs
+
+
+def polyak_tau(tau, what: str) -> float:
+    tau = float(tau)
+    if not math.isfinite(tau) or not 0.0 <= tau <= 1.0:
+        raise ValueError("%s: tau must be finite and in [0, 1]" % what)
+    return tau
+
+
+def soft_update_tensors(pairs: Sequence[Tuple[torch.Tensor, torch.Tensor]], tau: float, device) -> None:
+    """target = tau * online + (1 - tau) * target for up to 32 (online, target) pairs of contiguous float32 device tensors in
+    ONE launch on the current stream (`risvec_soft_update`, csrc/k_soft_update.hip), in place, with the bits of that
+    expression on float32 tensors (`ddpg_torch.py:122-127`).  The targets' version counters are not advanced."""
+    N.require_hip(device)
+    n = len(pairs)
+    on = (C.c_void_p * n)(*(o.data_ptr() for o, _ in pairs))
+    tg = (C.c_void_p * n)(*(t.data_ptr() for _, t in pairs))
+    ne = (C.c_int64 * n)(*(t.numel() for _, t in pairs))
+    N.check(N.load().risvec_soft_update(n, on, tg, ne, tau, 1.0 - tau, N.stream(device)))
+
+
 class BatchedActor:
     """`ActorNetwork` (NET:95-141) for n rows at once: input_dims -> fc1 -> LayerNorm -> ReLU -> fc2 -> LayerNorm -> ReLU
     -> mu[n_actions] -> sigmoid.  `input_dims` is the flattened width, n_agents x per-agent width (NET:99)."""
@@ -265,6 +314,24 @@ class BatchedActor:
             new[a] = t.detach()                               # the same storage and version counter
         for a, t in new.items():
             setattr(self, a, t)
+
+    def soft_update_from(self, online, tau: float) -> None:
+        """`update_network_parameters` (`ddpg_torch.py:104-130`) for this (target) actor: every weight tensor becomes
+        tau * online + (1 - tau) * own, in place, in one launch, bit for bit what that expression gives on float32
+        tensors.  online: another `BatchedActor` of the same shape, or a mapping under the reference's key names (the
+        learner's `actor.state_dict()`; contiguous float32 tensors of this actor's shapes on this actor's device, read in
+        place).  tau in [0, 1]; tau = 1 is the constructor's hard copy (:35).  The write goes through raw pointers, so the
+        tensors' version counters are NOT advanced: the weight stream is marked stale here and the next `forward`
+        rebuilds it.  A refused argument changes nothing."""
+        tau = polyak_tau(tau, "soft_update_from")
+        pairs = polyak_pairs(self, online, "soft_update_from")
+        soft_update_tensors(pairs, tau, self.device)
+        self.mark_stale()
+
+    def mark_stale(self) -> None:
+        """Have the next `forward` rebuild the weight stream: for writers that do not advance the weights' version
+        counters."""
+        self._packed = (None, self._packed[1])
 
     def _fused_weights(self):
         """(wstream, scales) of `risvec_sarl_actor`, rebuilt when a weight tensor is replaced or updated in place."""

@@ -7,7 +7,9 @@ rows at once on the GPU.
 
 One weight set shared by all rows.  `BatchedCritic.forward` / `td_target` are one launch (`risvec_sarl_critic`);
 `ddpg_td_target` is `target_actor.forward` + `target_critic.td_target`, two launches, the sampled tensors read in
-place.  Nothing here differentiates: the gradient half of `learn()` stays with the learner.  No CPU compute path.
+place.  `ddpg_soft_update` is the learner's last step, `update_network_parameters` (`ddpg_torch.py:104-130`), for both
+target networks in one launch; with pack="device" the next `ddpg_td_target` rebuilds both weight streams in two
+launches each.  Nothing here differentiates: the gradient half of `learn()` stays with the learner.  No CPU compute path.
 """
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ from typing import Mapping, NamedTuple, Optional, Tuple
 import torch
 
 from . import _native as N
-from .actor import _split_scaled, centre_fc1
+from .actor import _split_scaled, centre_fc1, polyak_pairs, polyak_tau, soft_update_tensors
 
 _WAVES = 4                        # wavefronts of a workgroup: each owns a quarter of every layer's output features
 
@@ -117,6 +119,46 @@ def pack_critic_weights(W1, b1, W2, Wav, W3) -> Tuple[torch.Tensor, torch.Tensor
     return stream, torch.stack([u1, u2, ua, u3]).float().contiguous()
 
 
+def pack_critic_weights_device(W1, b1, W2, Wav, W3, out=None, workspace=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`pack_critic_weights` computed on the device by `risvec_sarl_critic_pack` (csrc/k_sarl_critic_pack.hip): two launches
+    on the current stream, the float32 weights read in place, no copy and no synchronisation.  out: (wstream, scales)
+    to write into, every byte of them (default: new tensors); workspace: a uint8 tensor of
+    `risvec_sarl_critic_pack_workspace` bytes (default: a new one).  The same function of its arguments as the host
+    one, except that the float64 row means of the centred fc1 weight are summed in another order."""
+    lib = N.load()
+    ws = (W1, b1, W2, Wav, W3)
+    if not all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.device == W1.device for t in ws):
+        raise ValueError("pack_critic_weights_device: the weights must be contiguous float32 tensors on one device")
+    dev = W1.device
+    N.require_hip(dev)
+    if W1.dim() != 2 or W2.dim() != 2 or Wav.dim() != 2 or W3.dim() != 2:
+        raise ValueError("pack_critic_weights_device: W1, W2, Wav and W3 are Linear weights [out, in]")
+    (F1, IN), F2, A, F3 = W1.shape, W2.shape[0], Wav.shape[1], W3.shape[0]
+    want = dict(b1=(F1,), W2=(F2, F1), Wav=(F2, A), W3=(F3, F2))
+    for name, t in zip(("b1", "W2", "Wav", "W3"), ws[1:]):
+        if tuple(t.shape) != want[name]:
+            raise ValueError("pack_critic_weights_device: %s has shape %s, W1 %s and W2 %s ask for %s"
+                             % (name, tuple(t.shape), tuple(W1.shape), tuple(W2.shape), want[name]))
+    need = int(lib.risvec_sarl_critic_pack_workspace(IN, F1, F2, F3, A))
+    if need == 0:
+        raise ValueError("no fused critic kernel for input_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d" % (IN, F1, F2, F3, A))
+    g = critic_geom(IN, F1, F2, F3, A)
+    if out is None:
+        out = (torch.empty(g.rows, 64, 8, dtype=torch.float16, device=dev), torch.empty(4, device=dev))
+    stream, scales = out
+    N.in_place(stream, torch.float16, (g.rows, 64, 8), "pack_critic_weights_device: out[0]", dev)
+    N.in_place(scales, torch.float32, (4,), "pack_critic_weights_device: out[1]", dev)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
+            or not workspace.is_contiguous()):
+        raise ValueError("pack_critic_weights_device: workspace must be a contiguous uint8 tensor on %s" % dev)
+    N.check(lib.risvec_sarl_critic_pack(IN, F1, F2, F3, A, *(t.data_ptr() for t in ws), stream.data_ptr(),
+                                        stream.numel() * stream.element_size(), scales.data_ptr(), workspace.data_ptr(),
+                                        workspace.numel(), N.stream(dev)))
+    return stream, scales
+
+
 def unpack_critic_weights(stream: torch.Tensor, scales: torch.Tensor, input_dims: int, fc1_dims: int, fc2_dims: int,
                           fc3_dims: int, n_actions: int) -> dict:
     """What the kernel multiplies by, as float64: {"fc1" [input_dims + 1, fc1] (centred, the bias last), "fc2" [fc1, fc2],
@@ -137,6 +179,7 @@ class BatchedCritic:
     width (NET:19); the output is q [n, 1]."""
 
     GEMM_MODES = ("fused", "library")
+    PACK_MODES = ("host", "device")
     #: with gemm=None, batches of fewer rows than this run the library path even where the fused kernel is built
     #: (the measured crossover, profiles/sarl_critic.json; 1 = fused at every row count)
     AUTO_MIN_ROWS = 1
@@ -147,12 +190,16 @@ class BatchedCritic:
     _PACKED = ("W1", "b1", "W2", "Wav", "W3")                 # what the weight stream is built from
 
     def __init__(self, input_dims: int, n_actions: int, fc1_dims: int = 1024, fc2_dims: int = 512, fc3_dims: int = 256,
-                 device="cuda", seed: int = 0, gemm: Optional[str] = None):
+                 device="cuda", seed: int = 0, gemm: Optional[str] = None, pack: Optional[str] = None):
         """gemm: how `forward` / `td_target` run.  "fused": one hand-written MFMA launch (`risvec_sarl_critic`: float16
         hi + lo split products at float32 accuracy, the hidden layers never leaving the chip); built for input_dims <=
         128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}, n_actions <= 96.  "library": `q_torch`,
         the same forward with library kernels only -- the fallback for every other shape and the comparator.
-        Default (None): fused where built, for batches of at least `AUTO_MIN_ROWS` rows; library otherwise."""
+        Default (None): fused where built, for batches of at least `AUTO_MIN_ROWS` rows; library otherwise.
+        pack: how the fused kernel's weight stream is rebuilt after a weight update.  "host": `pack_critic_weights`,
+        library kernels into new tensors (the default).  "device": `pack_critic_weights_device`, two launches into
+        buffers allocated once -- for a target critic that is blended every step (see `soft_update_from`); only where
+        the fused kernel covers the shape."""
         lib = N.load()
         self.device = N.resolve_device(device)
         N.require_hip(self.device)
@@ -168,7 +215,12 @@ class BatchedCritic:
                              "input_dims <= 128, fc1 %% 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}, "
                              "n_actions <= 96)" % ((gemm,) + dims + (", ".join(self.GEMM_MODES),)))
         self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
+        self.pack = pack if pack is not None else "host"
+        if self.pack not in self.PACK_MODES or (self.pack == "device" and not fused_ok):
+            raise ValueError("pack=%r is not available for input_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d (modes: %s; device: "
+                             "where the fused kernel is built, see gemm)" % ((pack,) + dims + (", ".join(self.PACK_MODES),)))
         self._packed = (None, None)                           # (key, (wstream, scales))
+        self._pack_buffers = None                             # pack="device": ((wstream, scales), workspace), at first use
         self.packs = 0                                        # how often the weight stream was rebuilt
         dev = self.device
         g = torch.Generator(device="cpu").manual_seed(seed)
@@ -224,13 +276,43 @@ class BatchedCritic:
         for a, t in new.items():
             setattr(self, a, t)
 
+    def soft_update_from(self, online, tau: float) -> None:
+        """`update_network_parameters` (`ddpg_torch.py:104-130`) for this (target) critic: every weight tensor becomes
+        tau * online + (1 - tau) * own, in place, in one launch, bit for bit what that expression gives on float32
+        tensors.  online: another `BatchedCritic` of the same shape, or a mapping under the reference's key names (the
+        learner's `critic.state_dict()`; contiguous float32 tensors of this critic's shapes on this critic's device, read
+        in place).  tau in [0, 1]; tau = 1 is the constructor's hard copy (:35).  The write goes through raw pointers, so
+        the tensors' version counters are NOT advanced: the weight stream is marked stale here and the next `forward` /
+        `td_target` rebuilds it.  A refused argument changes nothing."""
+        tau = polyak_tau(tau, "soft_update_from")
+        pairs = polyak_pairs(self, online, "soft_update_from")
+        soft_update_tensors(pairs, tau, self.device)
+        self.mark_stale()
+
+    def mark_stale(self) -> None:
+        """Have the next `forward` / `td_target` rebuild the weight stream: for writers that do not advance the weights'
+        version counters."""
+        self._packed = (None, self._packed[1])
+
     def _fused_weights(self):
-        """(wstream, scales) of `risvec_sarl_critic`, rebuilt when a packed weight tensor is replaced or updated in place
-        (host packing: library kernels into new tensors)."""
+        """(wstream, scales) of `risvec_sarl_critic`, rebuilt when a packed weight tensor is replaced or updated in place,
+        or after `mark_stale` (pack="host": library kernels into new tensors; pack="device": two launches into the
+        buffers of the first rebuild)."""
         ws = tuple(getattr(self, a) for a in self._PACKED)
         key = tuple((t.data_ptr(), t._version) for t in ws)
         if self._packed[0] != key:
-            self._packed = (key, pack_critic_weights(*ws))
+            if self.pack == "device":
+                if self._pack_buffers is None:
+                    dims = (self.input_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims, self.n_actions)
+                    g = critic_geom(*dims)
+                    need = int(N.load().risvec_sarl_critic_pack_workspace(*dims))
+                    self._pack_buffers = ((torch.zeros(g.rows, 64, 8, dtype=torch.float16, device=self.device),
+                                           torch.zeros(4, device=self.device)),
+                                          torch.zeros(need, dtype=torch.uint8, device=self.device))
+                out, workspace = self._pack_buffers
+                self._packed = (key, pack_critic_weights_device(*ws, out=out, workspace=workspace))
+            else:
+                self._packed = (key, pack_critic_weights(*ws))
             self.packs += 1
         return self._packed[1]
 
@@ -324,3 +406,20 @@ def ddpg_td_target(target_actor, target_critic: BatchedCritic, states_: torch.Te
     caller-owned buffers.  Returns y [n]; `target.view(batch, 1)` (:88) is a view of it."""
     target_actions = target_actor.forward(states_, out=actions_)
     return target_critic.td_target(rewards, states_, target_actions, dones, gamma, out=out)
+
+
+def ddpg_soft_update(actor, target_actor, critic, target_critic: BatchedCritic, tau: float) -> None:
+    """`update_network_parameters` (`ddpg_torch.py:104-130`) for both target networks in ONE launch: all 10 actor and all
+    16 critic tensors become tau * online + (1 - tau) * target, in place, bit for bit what the reference's statements
+    give on float32 tensors.  `actor` / `critic`: the online networks, each a `BatchedActor` / `BatchedCritic` of the
+    target's shape or a mapping under the reference's key names (the learner's `state_dict()`, read in place);
+    `target_actor` / `target_critic`: the `Batched*` objects `ddpg_td_target` runs.  tau in [0, 1].  The targets'
+    version counters are not advanced; both weight streams are marked stale, so the next `ddpg_td_target` rebuilds them first
+    (pack="device": two launches each, into the same buffers).  A refused argument changes nothing."""
+    tau = polyak_tau(tau, "ddpg_soft_update")
+    if target_actor.device != target_critic.device:
+        raise ValueError("ddpg_soft_update: the two target networks must be on one device")
+    pairs = polyak_pairs(target_actor, actor, "ddpg_soft_update: actor") + polyak_pairs(target_critic, critic, "ddpg_soft_update: critic")
+    soft_update_tensors(pairs, tau, target_critic.device)
+    target_actor.mark_stale()
+    target_critic.mark_stale()

@@ -1001,6 +1001,61 @@ int risvec_sarl_critic(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2
                                                  (hipStream_t)stream));
 }
 
+size_t risvec_sarl_critic_pack_workspace(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions) {
+    return (size_t)risvec::sarl_critic_pack_workspace(in_dims, fc1, fc2, fc3, n_actions);
+}
+
+int risvec_sarl_critic_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_actions, const float* W1,
+                            const float* b1, const float* W2, const float* Wav, const float* W3, void* wstream,
+                            size_t wstream_bytes, float* scales, void* workspace, size_t workspace_bytes,
+                            risvec_stream_t stream) {
+    const char* fn = "risvec_sarl_critic_pack";
+    if (!risvec::sarl_critic_supported(in_dims, fc1, fc2, fc3, n_actions))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: in_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d (risvec_sarl_critic is built for "
+                    "in_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256, n_actions <= 96)",
+                    fn, in_dims, fc1, fc2, fc3, n_actions);
+    // the weights are read float by float wherever they do not start on 16 bytes: float alignment is all they need
+    const struct { const float* p; const char* name; } weights[] = {{W1, "W1"}, {b1, "b1"}, {W2, "W2"}, {Wav, "Wav"}, {W3, "W3"},
+                                                                    {scales, "scales"}};
+    for (const auto& w : weights) {
+        if (!w.p) return fail(RISVEC_ERR_ARG, "%s: %s is NULL", fn, w.name);
+        if (reinterpret_cast<uintptr_t>(w.p) & 3u) return fail(RISVEC_ERR_ARG, "%s: %s is not 4-byte aligned", fn, w.name);
+    }
+    REQ_PTR(wstream, "wstream"); REQ_PTR(workspace, "workspace");
+    const long long bytes = risvec::sarl_critic_stream_bytes(in_dims, fc1, fc2, fc3, n_actions);
+    if (wstream_bytes != (size_t)bytes)
+        return fail(RISVEC_ERR_ARG, "%s: wstream_bytes=%zu, this shape's weight stream has %lld", fn, wstream_bytes, bytes);
+    const size_t need = (size_t)risvec::sarl_critic_pack_workspace(in_dims, fc1, fc2, fc3, n_actions);
+    if (workspace_bytes < need)
+        return fail(RISVEC_ERR_ARG, "%s: workspace_bytes=%zu, this shape needs %zu (risvec_sarl_critic_pack_workspace)", fn,
+                    workspace_bytes, need);
+    return finish(fn, risvec::launch_sarl_critic_pack(in_dims, fc1, fc2, fc3, n_actions, W1, b1, W2, Wav, W3, wstream, scales,
+                                                      workspace, (hipStream_t)stream));
+}
+
+int risvec_soft_update(int32_t n_tensors, const float* const* online, float* const* target, const int64_t* numel, float tau,
+                       float one_minus_tau, risvec_stream_t stream) {
+    const char* fn = "risvec_soft_update";
+    if (n_tensors < 1 || n_tensors > risvec::kSoftUpdateMax)
+        return fail(RISVEC_ERR_SHAPE, "%s: n_tensors=%d outside [1, %d]", fn, n_tensors, risvec::kSoftUpdateMax);
+    if (!online || !target || !numel) return fail(RISVEC_ERR_ARG, "%s: online, target or numel is NULL", fn);
+    if (!std::isfinite(tau) || !std::isfinite(one_minus_tau))
+        return fail(RISVEC_ERR_ARG, "%s: tau=%g and one_minus_tau=%g must be finite", fn, (double)tau, (double)one_minus_tau);
+    long long total = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (numel[i] < 1 || numel[i] > (1LL << 40))
+            return fail(RISVEC_ERR_SHAPE, "%s: numel[%d]=%lld outside [1, 2^40]", fn, i, (long long)numel[i]);
+        if (!online[i] || !target[i]) return fail(RISVEC_ERR_ARG, "%s: online[%d] or target[%d] is NULL", fn, i, i);
+        if ((reinterpret_cast<uintptr_t>(online[i]) | reinterpret_cast<uintptr_t>(target[i])) & 3u)
+            return fail(RISVEC_ERR_ARG, "%s: online[%d] or target[%d] is not 4-byte aligned", fn, i, i);
+        if (online[i] == target[i])
+            return fail(RISVEC_ERR_ARG, "%s: online[%d] and target[%d] are the same tensor", fn, i, i);
+        total += numel[i];
+    }
+    if (total > (1LL << 40)) return fail(RISVEC_ERR_SHAPE, "%s: %lld elements in all, more than 2^40", fn, total);
+    return finish(fn, risvec::launch_soft_update(n_tensors, online, target, numel, tau, one_minus_tau, (hipStream_t)stream));
+}
+
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float* g, const float* b2,
                         const float* ln_w, const float* ln_b, const float* Wh, const float* bh, float* heads,
                         risvec_stream_t stream) {

@@ -105,6 +105,18 @@ hipError_t launch_sarl_critic(long long n_rows, int IN, int F1, int F2, int F3, 
                               const float* ln2w, const float* ln2b, const float* bav, const float* b3, const float* ln3w,
                               const float* ln3b, const float* qw, const float* qb, const float* reward, const uint8_t* done,
                               float gamma, float* q, float* y, hipStream_t st);
+// That weight stream and its scales from the float32 weights, in two launches (k_sarl_critic_pack.hip); the workspace
+// holds sarl_critic_pack_workspace() bytes (0: no such shape) and needs no initialisation.
+long long sarl_critic_pack_workspace(int IN, int F1, int F2, int F3, int A);
+hipError_t launch_sarl_critic_pack(int IN, int F1, int F2, int F3, int A, const float* W1, const float* b1, const float* W2,
+                                   const float* Wav, const float* W3, void* wstream, float* scales, void* workspace,
+                                   hipStream_t st);
+
+// target = tau online + one_minus_tau target for n_tensors <= kSoftUpdateMax tensors in one launch (k_soft_update.hip);
+// the three arrays are host arrays, copied into the kernel's argument block.
+constexpr int kSoftUpdateMax = 32;
+hipError_t launch_soft_update(int n_tensors, const float* const* online, float* const* target, const int64_t* numel,
+                              float tau, float one_minus_tau, hipStream_t st);
 
 int episode_partial_rows(int E);
 hipError_t launch_episode_clear(int E, int V, double* acc, hipStream_t st);

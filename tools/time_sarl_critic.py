@@ -3,7 +3,8 @@
 target critic with the epilogue): the hand-written MFMA launches (`gemm="fused"`) against the same computation with
 library kernels (`gemm="library"`: torch.nn.functional, what the reference's networks run as), interleaved in one
 process, HIP events, median of rounds.  FROZEN weights: the host pack of the weight stream is timed separately
-(`pack_us`, wall clock with a synchronisation) -- a learner that soft-updates the target critic every step pays it per step.
+(`pack_us`, wall clock with a synchronisation) -- a learner that soft-updates the target critic every step pays it per step
+unless the critic packs on the device (`pack="device"`): tools/time_critic_refresh.py times that step, blend included.
 
     python tools/time_sarl_critic.py [--out profiles/sarl_critic.json] [--rounds 7] [--steps 50] [--warmup 20]
 
