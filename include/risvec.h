@@ -72,8 +72,15 @@ enum {
                                        read it; evaluate sum_m theta_m b_m z^m by Horner in float64 from
                                        state.z_r (16 bytes per vehicle instead of 8M).  Only valid while h_r is
                                        what the geometry kernel produced -- not for arbitrary channel draws. */
-    RISVEC_STEP_3GPP = 512          /* risvec_step_kernel() only: the 3GPP member of the form (risvec_step_fused_3gpp*
+    RISVEC_STEP_3GPP = 512,         /* risvec_step_kernel() only: the 3GPP member of the form (risvec_step_fused_3gpp*
                                        set it internally; every other step entry point rejects it) */
+    RISVEC_STEP_THETA_IDX_CURRENT = 1024 /* risvec_step_fused and the fused form of risvec_step_ring (control_bit = 3,
+                                       state.theta_idx given): state.theta_idx holds the candidate index of EVERY element
+                                       of state.theta (risvec_random_phase and every sweep that writes the tensor leave
+                                       it so), so a kernel may read either.  Never changes which kernel is launched; the
+                                       software pipeline without the non-temporal hint then reads the indices (1 byte per
+                                       element instead of 8, same outputs bit for bit), every other kernel ignores the
+                                       bit.  Unlike RISVEC_STEP_THETA_BY_INDEX the tensor is not stale. */
 };
 
 /* risvec_bcd flags */
@@ -225,6 +232,9 @@ uint32_t risvec_abi_version(void);
  * member of the fused-step family a shape / batch size takes is a dispatch decision; tests assert it.
  * risvec_colsum and risvec_geometry (when it refreshes c_col) name the column-sum member they launched. */
 const char *risvec_last_kernel(void);
+/* 1 when the calling thread's last step launch read theta as candidate indices (RISVEC_STEP_THETA_BY_INDEX, or
+ * RISVEC_STEP_THETA_IDX_CURRENT where the kernel has that reader), 0 when it read the complex64 state.theta or none. */
+int risvec_last_theta_by_index(void);
 const char *risvec_last_error(void);
 
 /* Forms of a step call, for risvec_step_kernel(): risvec_step, risvec_step_fused, risvec_step_ring (cached / fused),
@@ -312,7 +322,8 @@ int risvec_theta_by_index_supported(int32_t n_veh, int32_t n_ris);
 int risvec_set_phase(const RisVecState *s, const float *angle, risvec_stream_t stream);
 
 /* Random_phase (ENV:203-206): theta = exp(j*possible_angles[idx]); idx [E,M] int32 or
- * NULL -> Philox. */
+ * NULL -> Philox.  With control_bit = 3 and state.theta_idx given, the candidate index of every element is written
+ * there too. */
 int risvec_random_phase(const RisVecState *s, const int32_t *idx, uint64_t seed,
                         uint32_t counter, risvec_stream_t stream);
 

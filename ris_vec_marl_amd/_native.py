@@ -28,6 +28,7 @@ STEP_REUSE_SSUM = 32
 STEP_STEER = 64
 STEP_REUSE_IDX = 128
 STEP_THETA_BY_INDEX = 256
+STEP_THETA_IDX_CURRENT = 1024     # state.theta_idx matches state.theta: a kernel may read either (fused forms)
 STEP_3GPP = 512          # risvec_step_kernel(): the 3GPP member of the form (the 3GPP entry points set it themselves)
 BCD_REUSE_COLSUM, BCD_REUSE_SSUM, BCD_REUSE_IDX, BCD_NO_THETA = 1, 2, 4, 8
 FORM_CACHED, FORM_FUSED, FORM_CACHED_RING, FORM_FUSED_RING, FORM_FUSED_MULTI = range(5)
@@ -163,6 +164,7 @@ _PROTOS = {
     "risvec_abi_version": (C.c_uint32, []),
     "risvec_last_error": (C.c_char_p, []),
     "risvec_last_kernel": (C.c_char_p, []),
+    "risvec_last_theta_by_index": (C.c_int, []),
     "risvec_step_kernel": (C.c_char_p, [C.POINTER(RisVecState), C.c_uint32, C.c_int32]),
     "risvec_force_forms": (C.c_int, [C.POINTER(RisVecForce)]),
     "risvec_default_params": (None, [C.POINTER(RisVecParams)]),
@@ -341,6 +343,11 @@ def last_kernel() -> str:
     """Name of the kernel the calling thread's last step / BCD / column-sum call dispatched (risvec_last_kernel)."""
     k = load().risvec_last_kernel()
     return k.decode() if k else ""
+
+
+def last_theta_by_index() -> int:
+    """1 if the calling thread's last step launch read theta as candidate indices, else 0 (risvec_last_theta_by_index)."""
+    return int(load().risvec_last_theta_by_index())
 
 
 def step_kernel(state, flags: int = 0, form: int = FORM_FUSED):

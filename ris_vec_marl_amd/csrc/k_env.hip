@@ -295,15 +295,19 @@ k_set_phase(long long n, const float* __restrict__ angle, float* __restrict__ th
     *reinterpret_cast<float2*>(theta + 2 * i) = phasor_of_angle(angle[i]);
 }
 
+// theta_idx (control_bit = 3 only, else nullptr): each element's candidate index goes to state.theta_idx as well, so what
+// reads theta by index (RISVEC_STEP_THETA_IDX_CURRENT) can do so from the first step of an episode.  The eight phasors
+// are then theta_candidate()'s -- the values the by-index readers expand an index to, bit for bit (sincospi's exact
+// zeros carry signs that depend on the quadrant; theta_candidate's are all +0, as the BCD sweep stores them).
 __global__ void __launch_bounds__(kBlock)
-k_random_phase(Dims d, const int32_t* __restrict__ idx, float* __restrict__ theta, uint64_t seed,
-               uint32_t counter) {
+k_random_phase(Dims d, const int32_t* __restrict__ idx, float* __restrict__ theta, uint8_t* __restrict__ theta_idx,
+               uint64_t seed, uint32_t counter) {
     __shared__ float2 s_cand[64];                                           // exp(j possible_angles[k]), ENV:169
     const int nc = 1 << d.cbit;
     if ((int)threadIdx.x < nc) {
         double s, c;
         sincospi(2.0 * (double)threadIdx.x / (double)nc, &s, &c);
-        s_cand[threadIdx.x] = make_float2((float)c, (float)s);
+        s_cand[threadIdx.x] = d.cbit == 3 ? theta_candidate((int)threadIdx.x) : make_float2((float)c, (float)s);
     }
     __syncthreads();
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -317,6 +321,7 @@ k_random_phase(Dims d, const int32_t* __restrict__ idx, float* __restrict__ thet
         k = randint_u32(r.x, 0, nc);                                        // ENV:204
     }
     *reinterpret_cast<float2*>(theta + 2 * i) = s_cand[k];                  // ENV:206
+    if (theta_idx) theta_idx[(long long)e * theta_idx_stride(d.M) + m] = (uint8_t)k;
 }
 
 // ---------------------------------------------------------------------------
@@ -368,7 +373,7 @@ hipError_t launch_random_phase(const RisVecState& s, const int32_t* idx, uint64_
                                uint32_t counter, hipStream_t st) {
     const long long n = (long long)s.n_envs * s.n_ris;
     hipLaunchKernelGGL(k_random_phase, dim3(blocks_for(n)), dim3(kBlock), 0, st, dims_of(s), idx,
-                       s.theta, seed, counter);
+                       s.theta, s.control_bit == 3 ? s.theta_idx : nullptr, seed, counter);
     return hipGetLastError();
 }
 

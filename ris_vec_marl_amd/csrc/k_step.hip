@@ -315,6 +315,9 @@ static hipError_t launch_step_vp(const RisVecState& s, const RisVecParams& p, co
 //                                     envs) per CU and 16x64 at most 8 (16x64: never NT); 8x36, 8x40, 16x256 and the
 //                                     run-time-M members at every size
 //     4. the compile-time shapes      k_step_fused_pipe<V,M,D,MarlCore> (NT beyond 1.055 IC)
+//                                     (RISVEC_STEP_THETA_IDX_CURRENT selects nothing: where the plan is this kernel -- or its
+//                                     ring form -- without NT, launch_step hands it state.theta_idx and it reads theta by
+//                                     index; everywhere else the bit is ignored)
 //     5. anything else                k_step_fused<VP,G,VEC>
 //
 // Why (us per step; profiles/):
@@ -515,9 +518,12 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
     const StepPlan pl = plan_step(s, flags, form);
     if (pl.family == StepPlan::NONE) return hipErrorNotSupported;
     StepArgs a = make_step_args(s, action, partner, n_groups, arrivals, seed, counter,
-                                flags & ~(uint32_t)(RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX));
+                                flags & ~(uint32_t)(RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX | RISVEC_STEP_THETA_IDX_CURRENT));
     if (ring) a.ring = *ring;                                  // the transition store rides in the step kernel
-    if (pl.tk) {                                               // theta is kept by index (the API checked the shape)
+    // theta is kept by index (the API checked the shape), or the indices are known to match the tensor and the plan is
+    // the kernel that can read either: the software pipeline without the non-temporal hint
+    const bool idx_current = (flags & RISVEC_STEP_THETA_IDX_CURRENT) && pl.family == StepPlan::PIPE && pl.pol == 0;
+    if (pl.tk || idx_current) {
         a.theta_k = s.theta_idx;
         a.theta_k_stride = theta_idx_stride(s.n_ris);
     }
@@ -526,6 +532,7 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
     else if (pl.family == StepPlan::PIPE) err = launch_step_fused_pipe(s, p, a, pl, st);
     else err = with_vp(s.n_veh, [&](auto vp) { return launch_step_vp<vp>(s, p, a, pl, st); });
     note_kernel("%s", pl.name);
+    note_theta_by_index(a.theta_k != nullptr);
     return err;
 }
 

@@ -100,18 +100,8 @@ k_step_fused_lat(Dims d, RisVecParams P, StepArgs A, int n_steps, RisVecTraj TJ)
     const int e_last = d.E - 1;
     const int NP = S::np(d);                                   // complex pairs per row: a constant for compile-time shapes
 
-    if constexpr (TK) {
-        // candidate k of the BCD sweep: exp(j 2 pi k / 8) as the float32 values the sweep stores (ENV:169, 213); 8 = 0
-        if (lane < 16) {
-            const float r = 0.70710677f;
-            const int k = lane & 7;
-            float c = (k & 3) == 2 ? 0.f : ((k & 1) ? r : 1.f);
-            float sn = (k & 3) == 0 ? 0.f : ((k & 1) ? r : 1.f);
-            if (k >= 3 && k <= 5) c = -c;
-            if (k >= 5) sn = -sn;
-            s_ph[wave][lane] = lane < 8 ? make_float2(c, sn) : make_float2(0.f, 0.f);
-        }
-    }
+    // candidate k of the BCD sweep: exp(j 2 pi k / 8) as the float32 values the sweep stores (ENV:169, 213); 8 = 0
+    if constexpr (TK) theta_table_fill(s_ph[wave], lane);
 
     float4 bq[NIT];
 #pragma unroll

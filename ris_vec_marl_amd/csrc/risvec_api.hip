@@ -14,6 +14,7 @@ namespace {
 
 thread_local char g_err[512] = "";
 thread_local char g_kernel[160] = "";
+thread_local int g_theta_by_index = 0;
 RisVecForce g_force{};                  // risvec_force_forms(): all RISVEC_BY_RULE
 
 int fail(int code, const char* fmt, ...) {
@@ -107,6 +108,19 @@ int check_step(const char* fn, const RisVecState* s, const float* action, const 
     return RISVEC_OK;
 }
 
+// RISVEC_STEP_THETA_IDX_CURRENT, accepted by risvec_step_fused and the fused form of risvec_step_ring only (check_step
+// refuses it as an unknown bit everywhere else): checks what it needs and returns the flags check_step sees
+int check_idx_current(const char* fn, const RisVecState* s, bool fused, uint32_t* flags) {
+    if (!(*flags & RISVEC_STEP_THETA_IDX_CURRENT)) return RISVEC_OK;
+    if (!fused) return fail(RISVEC_ERR_ARG, "%s: RISVEC_STEP_THETA_IDX_CURRENT is a hint to the fused forms (this one reads no theta)", fn);
+    REQ_PTR(s->theta_idx, "state.theta_idx");
+    if (s->control_bit != 3)
+        return fail(RISVEC_ERR_ARG, "%s: RISVEC_STEP_THETA_IDX_CURRENT needs control_bit = 3 (candidate indices exist for 2^b = 8 "
+                    "only), got %d", fn, s->control_bit);
+    *flags &= ~(uint32_t)RISVEC_STEP_THETA_IDX_CURRENT;
+    return RISVEC_OK;
+}
+
 // the transition-store arguments of risvec_step_ring / risvec_step_fused_3gpp, checked and translated
 int check_ring(const char* fn, const RisVecState* s, const RisVecStepRing* ring, uint32_t flags, risvec::StepRing* out) {
     const uint32_t need = RISVEC_STEP_POLICY_ACTION | RISVEC_STEP_OBS;
@@ -181,7 +195,10 @@ void note_kernel(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_kernel, sizeof(g_kernel), fmt, ap);
     va_end(ap);
+    g_theta_by_index = 0;
 }
+
+void note_theta_by_index(bool by_index) { g_theta_by_index = by_index ? 1 : 0; }
 
 const RisVecForce& forced_forms() { return g_force; }
 }  // namespace risvec
@@ -191,6 +208,8 @@ extern "C" {
 uint32_t risvec_abi_version(void) { return RISVEC_ABI_VERSION; }
 
 const char* risvec_last_kernel(void) { return g_kernel; }
+
+int risvec_last_theta_by_index(void) { return g_theta_by_index; }
 
 const char* risvec_last_error(void) { return g_err; }
 
@@ -377,7 +396,7 @@ int risvec_random_phase(const RisVecState* s, const int32_t* idx, uint64_t seed,
                         risvec_stream_t stream) {
     const char* fn = "risvec_random_phase";
     if (int rc = check_common(fn, s, nullptr, false)) return rc;
-    OPT_PTR(idx, "idx"); REQ_PTR(s->theta, "state.theta");
+    OPT_PTR(idx, "idx"); REQ_PTR(s->theta, "state.theta"); OPT_PTR(s->theta_idx, "state.theta_idx");
     return finish(fn, risvec::launch_random_phase(*s, idx, seed, counter, (hipStream_t)stream));
 }
 
@@ -407,7 +426,9 @@ int risvec_step_fused(const RisVecState* s, const RisVecParams* p, const float* 
                       uint64_t seed, uint32_t counter, uint32_t flags, risvec_stream_t stream) {
     const char* fn = "risvec_step_fused";
     if (int rc = check_common(fn, s, p)) return rc;
-    if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, true)) return rc;
+    uint32_t known = flags;
+    if (int rc = check_idx_current(fn, s, true, &known)) return rc;
+    if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, known, true)) return rc;
     if (flags & RISVEC_STEP_THETA_BY_INDEX) {                  // theta as the last sweep's candidate indices (no sweep here)
         REQ_PTR(s->theta_idx, "state.theta_idx");
         if (s->control_bit != 3 || !risvec::theta_by_index_supported(s->n_veh, s->n_ris) || (flags & RISVEC_STEP_STEER))
@@ -592,9 +613,11 @@ int risvec_step_ring(const RisVecState* s, const RisVecParams* p, const RisVecSt
     const char* fn = "risvec_step_ring";
     if (int rc = check_common(fn, s, p)) return rc;
     if (!ring) return fail(RISVEC_ERR_ARG, "%s: ring is NULL", fn);
-    if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, flags, fused != 0)) return rc;
+    uint32_t known = flags;
+    if (int rc = check_idx_current(fn, s, fused != 0, &known)) return rc;
+    if (int rc = check_step(fn, s, action, partner, n_groups, arrivals, known, fused != 0)) return rc;
     risvec::StepRing r;
-    if (int rc = check_ring(fn, s, ring, flags, &r)) return rc;
+    if (int rc = check_ring(fn, s, ring, known, &r)) return rc;
     const int V = s->n_veh;
     const hipError_t err = risvec::launch_step(*s, *p, action, partner, n_groups, arrivals, seed, counter, flags, fused != 0,
                                                (hipStream_t)stream, &r);

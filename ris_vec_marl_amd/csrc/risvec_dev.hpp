@@ -129,6 +129,18 @@ __device__ __forceinline__ float2 cfma(float2 a, float2 b, float2 acc) {
     return acc;
 }
 
+// The float32 phasor of candidate index k of a control_bit = 3 RIS: exp(j 2 pi k / 8) as the BCD sweep stores it
+// (ENV:169, 213; +-1, +-0.70710677f and +0 -- every zero is +0), and 0 for k = 8, the integer 0 of ENV:211, 220.
+// The one definition behind the by-index readers' table (theta_table_fill, risvec_pipe.hpp) and k_random_phase.
+__device__ __forceinline__ float2 theta_candidate(int k) {
+    const float r = 0.70710677f;
+    float c = (k & 3) == 2 ? 0.f : ((k & 1) ? r : 1.f);
+    float sn = (k & 3) == 0 ? 0.f : ((k & 1) ? r : 1.f);
+    if (k >= 3 && k <= 5) c = -c;
+    if (k >= 5) sn = -sn;
+    return k < 8 ? make_float2(c, sn) : make_float2(0.f, 0.f);
+}
+
 // exp(j x) in float64 for |x| <= 1e5: Cody-Waite reduction by pi/2 (two-term split, exact product for |k| < 2^17) and the
 // fdlibm kernel polynomials on [-pi/4, pi/4] -- error < 1e-15, i.e. the float32 image is the correctly rounded one except
 // within 1e-8 ulp of a rounding boundary.  ~30 float64 instructions against the ~150 of the general sincos(), whose

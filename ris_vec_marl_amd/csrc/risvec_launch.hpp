@@ -132,6 +132,8 @@ hipError_t launch_theta_from_index(const RisVecState& s, hipStream_t st);
 
 // risvec_last_kernel(): the launchers of the step path and the BCD sweep name the kernel they dispatched (per thread)
 void note_kernel(const char* fmt, ...);
+// risvec_last_theta_by_index(): note_kernel() clears it, the step launcher sets it after naming its kernel
+void note_theta_by_index(bool by_index);
 
 // risvec_force_forms(): the test / A/B override of the dispatch rules.  Read by the step selector (plan_step) and
 // launch_colsum only.

@@ -50,11 +50,25 @@ struct PipeShape : FusedShape<V, fused_g(V, M), fused_nit(V, M), M> {
     static constexpr int NP = M / 2;                           // complex pairs per row
 };
 
-template <int PC, int NIT>
+// TK ("theta by index"): the unit carries the two candidate indices of each theta pair (one 16-bit load) instead of
+// the complex64 pair (one 16-byte load)
+template <int PC, int NIT, bool TK = false>
 struct Unit {
     float4 h[PC][NIT];
     float4 t[NIT];
 };
+template <int PC, int NIT>
+struct Unit<PC, NIT, true> {
+    float4 h[PC][NIT];
+    unsigned k[NIT];
+};
+
+// A wavefront's 16-entry LDS table of theta_candidate() (risvec_dev.hpp; entries 8 ... 15 are 0), written by its first
+// 16 lanes.  The reader puts __builtin_amdgcn_wave_barrier() between this and its lookups: same-wave LDS accesses
+// execute in order.
+__device__ __forceinline__ void theta_table_fill(float2 (&row)[16], int lane) {
+    if (lane < 16) row[lane] = theta_candidate(lane);
+}
 
 // ---------------------------------------------------------------------------
 // What runs on the reduced cascade sums: the pipeline is the same for the MARL step, the SARL

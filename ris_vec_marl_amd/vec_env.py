@@ -100,6 +100,11 @@ class VecEnviron(ParamAttrs):
         self._theta_stale = False      # tensors["theta"] lags behind theta_idx (only ever True with lazy_theta)
         self._stale_version = -1       # tensors["theta"]._version when it went stale: a later write through torch moves it
         self._tk_ok = None             # does the fused step have a theta-by-index form at this shape? (asked lazily)
+        # theta_idx holds the candidate index of every element of tensors["theta"] AS IT IS NOW (Random_phase with
+        # control_bit = 3, or a sweep that wrote both): the fused step may then read either, and is told so
+        # (RISVEC_STEP_THETA_IDX_CURRENT).  Its own field, not `_idx_valid`: that one steers which BCD sweep runs.
+        self._idx_current = False
+        self._idx_current_version = -1  # tensors["theta"]._version when it was set: a write through torch moves it
         self._cstate: Optional[N.RisVecState] = None
         self._cparams: Optional[N.RisVecParams] = None
         self._cparams_version = -1
@@ -355,12 +360,27 @@ class VecEnviron(ParamAttrs):
         self._theta_stale = stale
         if stale:
             self._stale_version = self._t["theta"]._version     # kernels write through raw pointers: no bump
+        self._set_idx_current(not stale and self.control_bit == 3)  # a 2^b = 8 sweep that wrote the tensor wrote both
 
     def _theta_changed(self) -> None:
         """theta was written by something other than a BCD sweep: its cached sum and candidate indices are stale."""
         self._ssum_sweeps = 0
         self._idx_valid = False
         self._theta_stale = False      # whoever wrote theta made the tensor the truth again
+        self._idx_current = False
+
+    def _set_idx_current(self, current: bool) -> None:
+        """A kernel just wrote theta; `current`: it wrote the matching candidate indices too."""
+        self._idx_current = current
+        if current:
+            self._idx_current_version = self._t["theta"]._version   # kernels write through raw pointers: no bump
+
+    def _idx_current_flag(self) -> int:
+        """RISVEC_STEP_THETA_IDX_CURRENT while the indices are known to match the tensor: set by a kernel that wrote both,
+        and nothing has written the tensor through torch since (an unannounced write moves its `_version`)."""
+        if self._idx_current and self._t["theta"]._version == self._idx_current_version:
+            return N.STEP_THETA_IDX_CURRENT
+        return 0
 
     def _bcd_flags(self, reuse_colsum: Optional[bool], step: bool) -> int:
         reuse_c = self._colsum_valid if reuse_colsum is None else bool(reuse_colsum)
@@ -430,6 +450,7 @@ class VecEnviron(ParamAttrs):
         N.check(N.load().risvec_random_phase(C.byref(self._cstate), N.ptr(i), self.seed, self._chan,
                                              N.stream(self.device)))
         self._theta_changed()
+        self._set_idx_current(self.control_bit == 3)   # with 2^b = 8 the kernel writes each element's index as well
 
     def data_rate(self, p_off, partner, n_groups) -> torch.Tensor:
         """Environment.py:331-372 on the cached gains: p_off [E,V] offload power in W -> rate [E,V]."""
@@ -552,6 +573,7 @@ class VecEnviron(ParamAttrs):
         cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), N.stream(self.device)
         pa, pp, pn, par = N.ptr(a), N.ptr(pt), N.ptr(ng), N.ptr(ar)
         pfd = C.byref(fd) if fd is not None else None
+        either = fused and not bcd and not steer       # a launch that may be told "theta_idx matches theta"
 
         def launch() -> None:
             model = self._model(fused, steer, fd) if fused else None
@@ -567,6 +589,8 @@ class VecEnviron(ParamAttrs):
                 flags = base_flags | (self._bcd_flags(None, step=True) if bcd else 0)
                 if self.lazy_theta or self._theta_stale:       # otherwise theta is the tensor, and current
                     flags = self._theta_mode(flags, fused, bcd, steer)
+                elif either:
+                    flags |= self._idx_current_flag()
                 rc = fn(cs, C.byref(self._p()), pa, pp, pn, par, seed, self._steps, flags, stream)
                 if rc:
                     N.check(rc)
@@ -838,9 +862,12 @@ class VecEnviron(ParamAttrs):
                 rc = fn3(cs, C.byref(self._p()), model, pa, pp, pn, par, pfd, seed, self._steps, self._chan, flags,
                          C.byref(ring), stream)
             else:
+                fl = flags
                 if fused:
                     self._sync_theta()
-                rc = fn(cs, C.byref(self._p()), C.byref(ring), pa, pp, pn, par, seed, self._steps, flags, fz, stream)
+                    if not self.lazy_theta:
+                        fl |= self._idx_current_flag()
+                rc = fn(cs, C.byref(self._p()), C.byref(ring), pa, pp, pn, par, seed, self._steps, fl, fz, stream)
             if rc:
                 N.check(rc)
             replay.mem_cntr += E
