@@ -77,10 +77,13 @@ enum {
     RISVEC_STEP_THETA_IDX_CURRENT = 1024 /* risvec_step_fused and the fused form of risvec_step_ring (control_bit = 3,
                                        state.theta_idx given): state.theta_idx holds the candidate index of EVERY element
                                        of state.theta (risvec_random_phase and every sweep that writes the tensor leave
-                                       it so), so a kernel may read either.  Never changes which kernel is launched; the
-                                       software pipeline without the non-temporal hint then reads the indices (1 byte per
-                                       element instead of 8, same outputs bit for bit), every other kernel ignores the
-                                       bit.  Unlike RISVEC_STEP_THETA_BY_INDEX the tensor is not stale. */
+                                       it so), so a kernel may read either.  Never changes the plan or the kernel name
+                                       risvec_last_kernel() reports; the byte-bound members then run their by-index
+                                       instantiation (1 byte per element instead of 8, same outputs bit for bit): the
+                                       software pipeline with or without the non-temporal hint, its ring form, and the
+                                       latency-shaped kernels' NT and ALT members.  Every other kernel -- the latency-shaped
+                                       members with the default cache policy among them -- ignores the bit.  Unlike
+                                       RISVEC_STEP_THETA_BY_INDEX the tensor is not stale. */
 };
 
 /* risvec_bcd flags */

@@ -315,10 +315,13 @@ static hipError_t launch_step_vp(const RisVecState& s, const RisVecParams& p, co
 //                                     envs) per CU and 16x64 at most 8 (16x64: never NT); 8x36, 8x40, 16x256 and the
 //                                     run-time-M members at every size
 //     4. the compile-time shapes      k_step_fused_pipe<V,M,D,MarlCore> (NT beyond 1.055 IC)
-//                                     (RISVEC_STEP_THETA_IDX_CURRENT selects nothing: where the plan is this kernel -- or its
-//                                     ring form -- without NT, launch_step hands it state.theta_idx and it reads theta by
-//                                     index; everywhere else the bit is ignored)
 //     5. anything else                k_step_fused<VP,G,VEC>
+//   RISVEC_STEP_THETA_IDX_CURRENT selects nothing -- no plan and no name changes.  Where the plan is byte-bound and has a
+//   by-index instantiation, launch_step hands it state.theta_idx and that instantiation reads theta as 1-byte indices:
+//     the pipeline of 4. and its ring form, with or without NT      k_step_fused_pipe<..,NT?,TK>
+//     the NT and ALT members of 3. (always EMAX envs per wavefront) k_step_fused_lat<..,EMAX,NT|ALT,TK>
+//   Everywhere else the bit is ignored: the default-policy members of 3. (one memory round trip, not byte-bound: a table
+//   fill in front of their first use for nothing), the steering, generic and 3GPP kernels.
 //
 // Why (us per step; profiles/):
 //   * beyond 1.29 IC many short wavefronts with every request up front are what the best pure reader looks like: 1-4 %
@@ -520,9 +523,13 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
     StepArgs a = make_step_args(s, action, partner, n_groups, arrivals, seed, counter,
                                 flags & ~(uint32_t)(RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX | RISVEC_STEP_THETA_IDX_CURRENT));
     if (ring) a.ring = *ring;                                  // the transition store rides in the step kernel
-    // theta is kept by index (the API checked the shape), or the indices are known to match the tensor and the plan is
-    // the kernel that can read either: the software pipeline without the non-temporal hint
-    const bool idx_current = (flags & RISVEC_STEP_THETA_IDX_CURRENT) && pl.family == StepPlan::PIPE && pl.pol == 0;
+    // theta is kept by index (the API checked the shape), or the indices are known to match the tensor and the plan is one
+    // of the byte-bound kernels with a by-index instantiation: the software pipeline (either cache policy, the ring form
+    // included), or the latency family's EMAX member with the non-temporal hint or the alternating walk.  Not the latency
+    // members with the default policy: they live for one memory round trip, and a table fill in front of their first use
+    // would buy nothing.
+    const bool idx_current = (flags & RISVEC_STEP_THETA_IDX_CURRENT) &&
+                             (pl.family == StepPlan::PIPE || (pl.family == StepPlan::LAT && pl.pol != 0));
     if (pl.tk || idx_current) {
         a.theta_k = s.theta_idx;
         a.theta_k_stride = theta_idx_stride(s.n_ris);

@@ -273,7 +273,10 @@ static hipError_t launch_member(const RisVecState& s, const RisVecParams& p, con
         return hipErrorNotSupported;
     }
     if (pl.epwt == EMAX) {
-        switch (pl.pol * 2 + (pl.tk ? 1 : 0)) {
+        // by index: the plan says so (RISVEC_STEP_THETA_BY_INDEX), or launch_step handed an NT / ALT plan the current indices
+        // (RISVEC_STEP_THETA_IDX_CURRENT: same plan, same name, the TK instantiation of it)
+        const bool tk = pl.tk || (pl.pol != 0 && a.theta_k != nullptr);
+        switch (pl.pol * 2 + (tk ? 1 : 0)) {
             case 0: return launch_one<S, EMAX, false, 0, false>(s, p, a, 1, tj, st);
             case 1: return launch_one<S, EMAX, false, 0, true>(s, p, a, 1, tj, st);
             case 2: return launch_one<S, EMAX, false, 1, false>(s, p, a, 1, tj, st);

@@ -91,35 +91,31 @@ __device__ __forceinline__ float4 ld_nt(const float4* p) {
     return make_float4(t.x, t.y, t.z, t.w);
 }
 
-// the by-index theta source of a core's arguments: StepArgs has one, the other cores' arguments do not
-__device__ __forceinline__ const uint8_t* theta_k_of(const StepArgs& a) { return a.theta_k; }
-__device__ __forceinline__ int theta_k_stride_of(const StepArgs& a) { return a.theta_k_stride; }
-__device__ __forceinline__ const uint8_t* theta_k_of(const SarlArgs&) { return nullptr; }
-__device__ __forceinline__ int theta_k_stride_of(const SarlArgs&) { return 0; }
-__device__ __forceinline__ const uint8_t* theta_k_of(const GainArgs&) { return nullptr; }
-__device__ __forceinline__ int theta_k_stride_of(const GainArgs&) { return 0; }
-
 // per_wave > 0: a wavefront owns the CONTIGUOUS groups [wid * per_wave, (wid + 1) * per_wave) -- it walks one
 // contiguous piece of h_r from start to end; per_wave = 0: groups wid, wid + nw, ... (the round-1 form).
 // NT: h_r / theta are read with the non-temporal hint.
 //
-// Theta by index (the cores whose Args are StepArgs, not NT): A.theta_k is a run-time optional input like A.arrivals and
-// A.h_d -- nullptr reads the complex64 theta, otherwise the env's phase shifts are read as candidate indices, one byte
-// per element (state.theta_idx: 2 bytes per lane and unit where the tensor costs 16), and expanded through the
-// wavefront's 16-entry LDS table (theta_table_fill).  The choice is ONE wave-uniform branch in front of the group loop
-// between two straight-line copies of it (run<TK>): a test inside load_unit / do_group would be a join, and a join costs
-// the counted s_waitcnt there (see the notes on ragged rows and on arrivals_src).
-template <int V, int M, int D, class Core, bool NT = false>
+// TK, theta by index (the cores whose Args are StepArgs): the env's phase shifts are read as candidate indices, one byte
+// per element (A.theta_k = state.theta_idx: 2 bytes per lane and unit where the tensor costs 16), and expanded through
+// the wavefront's 16-entry LDS table (theta_table_fill).  An instantiation of its own, chosen on the host (launch_pipe:
+// A.theta_k != nullptr), like the latency family's TK and ALT: as a wave-uniform branch between two copies of the group
+// loop inside one kernel the choice cost BOTH copies their registers (the kernel arguments ended up spilled to VGPR lanes:
+// 87 SGPRs against 26, 697 v_readlane in the kernel against 48; EXPERIMENTS.md), and a test inside load_unit / do_group would
+// be a join, which costs the counted s_waitcnt there (see the notes on ragged rows and on arrivals_src).  The form
+// without TK never touches A.theta_k / A.theta_k_stride.
+// NT + TK: the h_r rows keep the hint, the index loads use the default policy -- the index tensor is 64 B per env (16.8 MB
+// at 262 144 envs), re-read every step, and fits the cache the hint is there to protect.
+template <int V, int M, int D, class Core, bool NT = false, bool TK = false>
 __global__ void __launch_bounds__(kBlock)
 k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_groups_total, int per_wave) {
     using In = typename Core::In;
     using S = PipeShape<V, M>;
     constexpr int VP = S::VP, EPW = S::EPW, NP = S::NP, G = S::G, NIT = S::NIT, VPP = S::VPP;
     constexpr int PC = S::PC, CHUNKS = S::CHUNKS, UPG = S::UPG, K = S::K;
-    constexpr bool TK_OK = !NT && std::is_same<typename Core::Args, StepArgs>::value;     // has a by-index copy
+    static_assert(!TK || std::is_same<typename Core::Args, StepArgs>::value, "theta by index: StepArgs carries the indices");
     static_assert(D <= UPG && UPG % D == 0, "ring depth must divide the units of a group");
     __shared__ float s_img[kBlock / kWave][kWave * 2];
-    __shared__ float2 s_ph[TK_OK ? kBlock / kWave : 1][16];    // by index: the 8 candidate phasors + the integer 0, per wavefront
+    __shared__ float2 s_ph[TK ? kBlock / kWave : 1][16];       // TK: the 8 candidate phasors + the integer 0, per wavefront
 
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int gl = lane % G, gv = lane / G;
@@ -151,159 +147,146 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
     }
     const unsigned row_off = (unsigned)(gv * NP);
 
+    using U = Unit<PC, NIT, TK>;
+    U ring[D];
+
+    auto load_unit = [&](U& u, int grp, int ui) {
+        const int i = ui / CHUNKS, c = ui % CHUNKS;
+        int e = grp * EPW + i;
+        e = e < e_last ? e : e_last;                       // tail: re-read the last env, masked later
+        // wave-uniform 64-bit base (SGPRs) + 32-bit lane offset + compile-time constant:
+        // the address arithmetic stays off the vector ALU
+        const float4* __restrict__ hb = h4 + (long long)e * (V * NP);
+        if constexpr (TK) {
+            // the indices FIRST: loads return in issue order, so the table lookup can run while the unit's h_r rows
+            // are still on their way
+            if (c == 0) {
+                const uint8_t* __restrict__ kb = A.theta_k + (long long)e * A.theta_k_stride;
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) u.k[it] = *reinterpret_cast<const uint16_t*>(kb + 2 * pcl[it]);
+            }
+        }
+#pragma unroll
+        for (int pc = 0; pc < PC; ++pc) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const float4* __restrict__ src = hb + (row_off + (unsigned)pcl[it] + ((c * PC + pc) * VPP * NP));
+                u.h[pc][it] = NT ? ld_nt(src) : *src;
+            }
+        }
+        if constexpr (!TK) {
+            if (c == 0) {
+                const float4* __restrict__ tb = t4 + (long long)e * NP;
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    u.t[it] = NT ? ld_nt(tb + pcl[it]) : tb[pcl[it]];
+                }
+            }
+        }
+    };
+
     // per_wave < 0 (experiment): the four wavefronts of a workgroup interleave over ONE contiguous range of
     // 4 * |per_wave| groups
     constexpr int WPB = kBlock / kWave;
     const int stride = per_wave > 0 ? 1 : (per_wave < 0 ? WPB : nw);
-    const int grp0 = per_wave > 0 ? wid * per_wave : (per_wave < 0 ? (wid / WPB) * (-per_wave * WPB) + (wid % WPB) : wid);
-    int grp_end = per_wave > 0 ? grp0 + per_wave : (per_wave < 0 ? (wid / WPB + 1) * (-per_wave * WPB) : n_groups_total);
+    int grp = per_wave > 0 ? wid * per_wave : (per_wave < 0 ? (wid / WPB) * (-per_wave * WPB) + (wid % WPB) : wid);
+    int grp_end = per_wave > 0 ? grp + per_wave : (per_wave < 0 ? (wid / WPB + 1) * (-per_wave * WPB) : n_groups_total);
     grp_end = grp_end < n_groups_total ? grp_end : n_groups_total;
     // Fetch the kernel-argument pointers in the SAME scalar-load round trip as the exit condition: left alone, the
     // compiler loads n_groups_total first, waits, branches, and only then requests the pointers -- a second cold
     // scalar-cache miss (~0.35 us) in front of every wavefront's first HBM request.
-    if constexpr (TK_OK) {
-        RISVEC_ARGS_IN_ONE_TRIP("s"(A.h_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave), "s"(d.E),
-                                "s"(A.theta_k), "s"(A.theta_k_stride));
+    if constexpr (TK) {
+        RISVEC_ARGS_IN_ONE_TRIP("s"(A.h_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b), "s"(n_groups_total), "s"(per_wave),
+                                "s"(d.E));
     } else {
         RISVEC_ARGS_IN_ONE_TRIP("s"(A.h_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave), "s"(d.E));
     }
-    if (grp0 >= grp_end) return;                           // whole wave: no cross-lane op is skipped
+    if (grp >= grp_end) return;                            // whole wave: no cross-lane op is skipped
+#pragma unroll
+    for (int ui = 0; ui < D; ++ui) load_unit(ring[ui], grp, ui);
+    if constexpr (TK) {
+        theta_table_fill(s_ph[wave], lane);                // once per wavefront, behind the first requests
+        __builtin_amdgcn_wave_barrier();                   // the wavefront's own table writes -> its reads
+    }
     const int v_mine = lane % VP;
 
-    // The whole group loop, once per theta source (tk: std::bool_constant)
-    auto run = [&](auto tk) {
-        constexpr bool TK = decltype(tk)::value;
-        using U = Unit<PC, NIT, TK>;
-        U ring[D];
-        int grp = grp0;
+    // One group: consume its UPG units (refilling the ring D units ahead, across the group
+    // boundary), prefetch the NEXT group's per-lane inputs into `in_nx`, then run the core with
+    // `in`.  Called alternately with (inA, inB) / (inB, inA) so no register copy - and hence
+    // no wait on the prefetch - is needed at the loop boundary.
+    auto do_group = [&](int g_cur, const In& in, In& in_nx) {
+        // The prefetch is unconditional (straight-line code keeps the compiler's vmcnt
+        // bookkeeping exact): a wave on its last group "prefetches" group 0 instead, which
+        // every such wave shares, so those requests are served by L2 and cost no HBM traffic.
+        const int nxt = (g_cur + stride < grp_end) ? g_cur + stride : 0;
+        const int e_mine = g_cur * EPW + lane / VP;
+        const bool active = e_mine < d.E;
+        // Take the wait for this group's per-lane inputs HERE (they were requested a whole
+        // group ago), not at their first use inside the core, where the compiler could only
+        // express it as vmcnt(0) and would drain the next group's prefetch with it.
+        Core::hold(in);
 
-        auto load_unit = [&](U& u, int g_ld, int ui) {
+        float2 w0[NIT], w1[NIT];
+#pragma unroll
+        for (int ui = 0; ui < UPG; ++ui) {
+            U& u = ring[ui % D];
             const int i = ui / CHUNKS, c = ui % CHUNKS;
-            int e = g_ld * EPW + i;
-            e = e < e_last ? e : e_last;                       // tail: re-read the last env, masked later
-            // wave-uniform 64-bit base (SGPRs) + 32-bit lane offset + compile-time constant:
-            // the address arithmetic stays off the vector ALU
-            const float4* __restrict__ hb = h4 + (long long)e * (V * NP);
-            if constexpr (TK) {
-                // the indices FIRST: loads return in issue order, so the table lookup can run while the unit's h_r rows
-                // are still on their way
-                if (c == 0) {
-                    const uint8_t* __restrict__ kb = theta_k_of(A) + (long long)e * theta_k_stride_of(A);
-#pragma unroll
-                    for (int it = 0; it < NIT; ++it) u.k[it] = *reinterpret_cast<const uint16_t*>(kb + 2 * pcl[it]);
-                }
-            }
-#pragma unroll
-            for (int pc = 0; pc < PC; ++pc) {
+            if (c == 0) {
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
-                    const float4* __restrict__ src = hb + (row_off + (unsigned)pcl[it] + ((c * PC + pc) * VPP * NP));
-                    u.h[pc][it] = NT ? ld_nt(src) : *src;
-                }
-            }
-            if constexpr (!TK) {
-                if (c == 0) {
-                    const float4* __restrict__ tb = t4 + (long long)e * NP;
-#pragma unroll
-                    for (int it = 0; it < NIT; ++it) {
-                        u.t[it] = NT ? ld_nt(tb + pcl[it]) : tb[pcl[it]];
+                    float2 t0, t1;
+                    if constexpr (TK) {
+                        t0 = s_ph[wave][u.k[it] & 15u];
+                        t1 = s_ph[wave][(u.k[it] >> 8) & 15u];
+                    } else {
+                        t0 = make_float2(u.t[it].x, u.t[it].y);
+                        t1 = make_float2(u.t[it].z, u.t[it].w);
                     }
+                    w0[it] = cmul(t0, make_float2(bq[it].x, bq[it].y));
+                    w1[it] = cmul(t1, make_float2(bq[it].z, bq[it].w));
                 }
             }
-        };
-
+            float val[8];
 #pragma unroll
-        for (int ui = 0; ui < D; ++ui) load_unit(ring[ui], grp, ui);
-        if constexpr (TK) {
-            theta_table_fill(s_ph[wave], lane);
-            __builtin_amdgcn_wave_barrier();                   // the wavefront's own table writes -> its reads
+            for (int pc = 0; pc < PC; ++pc) {
+                float2 acc = make_float2(0.f, 0.f);
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    acc = cfma(make_float2(u.h[pc][it].x, u.h[pc][it].y), w0[it], acc);
+                    acc = cfma(make_float2(u.h[pc][it].z, u.h[pc][it].w), w1[it], acc);
+                }
+                val[2 * pc] = acc.x;
+                val[2 * pc + 1] = acc.y;
+            }
+            treduce<K, G / 2>(val, gl);
+            if (gl % S::WSTRIDE == 0) {
+                const int j = gl / S::WSTRIDE;                 // value index = (row-in-unit, re/im)
+                const int v = (c * PC + (j >> 1)) * VPP + gv;
+                s_img[wave][(i * VP + v) * 2 + (j & 1)] = val[0];
+            }
+            // refill the slot just consumed, D units ahead (crossing into the next group)
+            if (ui + D < UPG) load_unit(u, g_cur, ui + D);
+            else load_unit(u, nxt, ui + D - UPG);
         }
+        // per-lane inputs of the next group: in flight during this group's core
+        in_nx = Core::load(d, A, nxt * EPW + lane / VP, v_mine, nxt * EPW + lane / VP < d.E);
 
-        // One group: consume its UPG units (refilling the ring D units ahead, across the group
-        // boundary), prefetch the NEXT group's per-lane inputs into `in_nx`, then run the core with
-        // `in`.  Called alternately with (inA, inB) / (inB, inA) so no register copy - and hence
-        // no wait on the prefetch - is needed at the loop boundary.
-        auto do_group = [&](int g_cur, const In& in, In& in_nx) {
-            // The prefetch is unconditional (straight-line code keeps the compiler's vmcnt
-            // bookkeeping exact): a wave on its last group "prefetches" group 0 instead, which
-            // every such wave shares, so those requests are served by L2 and cost no HBM traffic.
-            const int nxt = (g_cur + stride < grp_end) ? g_cur + stride : 0;
-            const int e_mine = g_cur * EPW + lane / VP;
-            const bool active = e_mine < d.E;
-            // Take the wait for this group's per-lane inputs HERE (they were requested a whole
-            // group ago), not at their first use inside the core, where the compiler could only
-            // express it as vmcnt(0) and would drain the next group's prefetch with it.
-            Core::hold(in);
-
-            float2 w0[NIT], w1[NIT];
-#pragma unroll
-            for (int ui = 0; ui < UPG; ++ui) {
-                U& u = ring[ui % D];
-                const int i = ui / CHUNKS, c = ui % CHUNKS;
-                if (c == 0) {
-#pragma unroll
-                    for (int it = 0; it < NIT; ++it) {
-                        float2 t0, t1;
-                        if constexpr (TK) {
-                            t0 = s_ph[wave][u.k[it] & 15u];
-                            t1 = s_ph[wave][(u.k[it] >> 8) & 15u];
-                        } else {
-                            t0 = make_float2(u.t[it].x, u.t[it].y);
-                            t1 = make_float2(u.t[it].z, u.t[it].w);
-                        }
-                        w0[it] = cmul(t0, make_float2(bq[it].x, bq[it].y));
-                        w1[it] = cmul(t1, make_float2(bq[it].z, bq[it].w));
-                    }
-                }
-                float val[8];
-#pragma unroll
-                for (int pc = 0; pc < PC; ++pc) {
-                    float2 acc = make_float2(0.f, 0.f);
-#pragma unroll
-                    for (int it = 0; it < NIT; ++it) {
-                        acc = cfma(make_float2(u.h[pc][it].x, u.h[pc][it].y), w0[it], acc);
-                        acc = cfma(make_float2(u.h[pc][it].z, u.h[pc][it].w), w1[it], acc);
-                    }
-                    val[2 * pc] = acc.x;
-                    val[2 * pc + 1] = acc.y;
-                }
-                treduce<K, G / 2>(val, gl);
-                if (gl % S::WSTRIDE == 0) {
-                    const int j = gl / S::WSTRIDE;                 // value index = (row-in-unit, re/im)
-                    const int v = (c * PC + (j >> 1)) * VPP + gv;
-                    s_img[wave][(i * VP + v) * 2 + (j & 1)] = val[0];
-                }
-                // refill the slot just consumed, D units ahead (crossing into the next group)
-                if (ui + D < UPG) load_unit(u, g_cur, ui + D);
-                else load_unit(u, nxt, ui + D - UPG);
-            }
-            // per-lane inputs of the next group: in flight during this group's core
-            in_nx = Core::load(d, A, nxt * EPW + lane / VP, v_mine, nxt * EPW + lane / VP < d.E);
-
-            // the wave's own LDS writes -> its own reads (LDS is in-order per wave; no other wave
-            // touches this slice); the barrier only pins the compiler's ordering
-            __builtin_amdgcn_wave_barrier();
-            const float2 img = *reinterpret_cast<const float2*>(&s_img[wave][lane * 2]);
-            Core::template run<VP>(d, P, A, e_mine, v_mine, active, img, in);
-            __builtin_amdgcn_wave_barrier();
-        };
-
-        In inA = Core::load(d, A, grp * EPW + lane / VP, v_mine, grp * EPW + lane / VP < d.E), inB;
-        while (true) {
-            do_group(grp, inA, inB);
-            grp += stride;
-            if (grp >= grp_end) break;
-            do_group(grp, inB, inA);
-            grp += stride;
-            if (grp >= grp_end) break;
-        }
+        // the wave's own LDS writes -> its own reads (LDS is in-order per wave; no other wave
+        // touches this slice); the barrier only pins the compiler's ordering
+        __builtin_amdgcn_wave_barrier();
+        const float2 img = *reinterpret_cast<const float2*>(&s_img[wave][lane * 2]);
+        Core::template run<VP>(d, P, A, e_mine, v_mine, active, img, in);
+        __builtin_amdgcn_wave_barrier();
     };
 
-    if constexpr (TK_OK) {
-        if (theta_k_of(A) != nullptr) run(std::true_type{});
-        else run(std::false_type{});
-    } else {
-        run(std::false_type{});
+    In inA = Core::load(d, A, grp * EPW + lane / VP, v_mine, grp * EPW + lane / VP < d.E), inB;
+    while (true) {
+        do_group(grp, inA, inB);
+        grp += stride;
+        if (grp >= grp_end) break;
+        do_group(grp, inB, inA);
+        grp += stride;
+        if (grp >= grp_end) break;
     }
 }
 
@@ -332,8 +315,17 @@ static hipError_t launch_pipe(const RisVecState& s, const typename Core::Params&
     const long long per_wave = (n_groups + want_waves - 1) / want_waves;
     want_waves = (n_groups + per_wave - 1) / per_wave;
     const unsigned grid = (unsigned)((want_waves + wpb - 1) / wpb);
-    if (nt) hipLaunchKernelGGL((k_step_fused_pipe<V, M, D, Core, true>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, 0);
-    else hipLaunchKernelGGL((k_step_fused_pipe<V, M, D, Core, false>), dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, 0);
+    auto go = [&](auto knl) { hipLaunchKernelGGL(knl, dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, 0); };
+    // the theta source is an instantiation, picked here; the by-index forms exist for the cores that step on StepArgs
+    if constexpr (std::is_same<typename Core::Args, StepArgs>::value) {
+        if (a.theta_k != nullptr) {
+            if (nt) go(k_step_fused_pipe<V, M, D, Core, true, true>);
+            else go(k_step_fused_pipe<V, M, D, Core, false, true>);
+            return hipGetLastError();
+        }
+    }
+    if (nt) go(k_step_fused_pipe<V, M, D, Core, true>);
+    else go(k_step_fused_pipe<V, M, D, Core, false>);
     return hipGetLastError();
 }
 
