@@ -830,6 +830,50 @@ int risvec_sarl_critic_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t f
                             const float *b1, const float *W2, const float *Wav, const float *W3, void *wstream,
                             size_t wstream_bytes, float *scales, void *workspace, size_t workspace_bytes,
                             risvec_stream_t stream);
+/* The multi-agent (SAC) twin global critic and the TD target of Global_SAC_Critic.global_learn
+ * (Simulation-MARL-BCD/global_sac_critic.py:338-352; the network: networks.py:7-49, a plain ReLU MLP on cat([state, action])),
+ * in ONE launch for n_rows rows and n_nets in {1, 2} weight sets of one shape:
+ *     x   = [state[row, 0:state_dims] | action[row, 0:action_dims]]        two pointers, read in place
+ *     h1  = relu(W1 x + b1);  h2 = relu(W2 h1 + b2);  h3 = relu(W3 h2 + b3);  q_c = qw . h3 + qb          c = 1 .. n_nets
+ *     m   = n_nets == 2 ? min(q_1, q_2) : q_1
+ *     ent = coef[0] logp_power[row] + coef[1] logp_intent[row]             a term whose logp pointer is NULL is absent
+ *     y[row] = done[row] ? reward[row] : reward[row] + gamma (m - ent)     (a select; the last step one fused multiply-add)
+ * state [n_rows, state_dims], action [n_rows, action_dims], reward, logp_power, logp_intent [n_rows] float32, done
+ * [n_rows] uint8 (0 / 1), coef [2] float32 ON THE DEVICE (the learner's log_alpha.exp() * entropy_scale: the single-alpha
+ * path passes the same value twice), all read in place with no alignment beyond their type's.  q1, q2, y [n_rows] are
+ * each optional (NULL: not written), at least one must be given; q2 needs n_nets == 2; y needs reward and done; a logp
+ * pointer needs coef and y.  n_nets == 1 is the plain forward of one CriticNetwork (the local critics of sac_agent.py).
+ * One launch on `stream`: no atomics, no second pass, no workspace, no synchronisation.  The three matrix products run on
+ * the fp16 matrix cores at float32 accuracy (operands split as for risvec_sarl_critic), the 1-wide q layer is a dot
+ * product in registers; no hidden layer and no concatenated input touches memory.
+ * Prepared weights of one net (rebuild after an update; S_0 / S_1 = float16 hi / lo of 2^s X, s one power of two per matrix):
+ *   wstream  fragment rows [64 lanes][8 halfs] (1 KiB) in three blocks, with KS = ceil((state_dims + action_dims) / 16),
+ *            NG = fc1 / 32, MT2 = fc2 / 128, MT3 = fc3 / 128; w < 4 is the wavefront that owns output tiles
+ *            [w MT, (w + 1) MT) of a layer, t = hi / lo:
+ *     fc1    row (g KS + s) 2 + t, g < NG: element (lane, j) = S_t[32 g + (lane & 31)][16 s + 8 (lane >> 5) + j] of X = the fc1
+ *            weight [fc1, 16 KS], zero beyond state_dims + action_dims;
+ *     fc2    row ((w 2 NG + k) MT2 + m) 2 + t, k < 2 NG: element (lane, j) =
+ *            S_t[16 k + 8 (j >> 2) + 4 (lane >> 5) + (j & 3)][32 (w MT2 + m) + (lane & 31)] of X = the fc2 weight [fc1, fc2];
+ *     fc3    row ((w fc2 / 16 + k) MT3 + m) 2 + t, k < fc2 / 16: the same element rule for X = the fc3 weight [fc2, fc3];
+ *   wstream_bytes  its size = risvec_marl_critic_stream_bytes(...), checked against the shape;
+ *   scales [3]  2^-s of fc1, fc2 and fc3;
+ *   b1 [fc1], b2 [fc2], b3 [fc3], qw [fc3], qb [1]: float32, 16-byte aligned, read in place.
+ * Built for state_dims + action_dims <= 128 (each >= 1), fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}
+ * (risvec_marl_critic_supported, host only); other shapes return RISVEC_ERR_UNSUPPORTED (stream_bytes: 0).  Every other
+ * argument error returns RISVEC_ERR_ARG; all are reported before anything is launched and without touching a device.
+ * Inputs beyond the float16 range (|x| > 65504) are not supported. */
+typedef struct RisVecMarlCriticNet {
+    const void *wstream;
+    int64_t wstream_bytes;
+    const float *scales;
+    const float *b1, *b2, *b3, *qw, *qb;
+} RisVecMarlCriticNet;
+int risvec_marl_critic_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3);
+int64_t risvec_marl_critic_stream_bytes(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3);
+int risvec_marl_critic(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                       int32_t n_nets, const RisVecMarlCriticNet *nets, const float *state, const float *action,
+                       const float *reward, const uint8_t *done, float gamma, const float *coef, const float *logp_power,
+                       const float *logp_intent, float *q1, float *q2, float *y, risvec_stream_t stream);
 /* The Polyak blend of update_network_parameters (Simulation-SARL/ddpg_torch.py:104-130) for n_tensors tensors in ONE
  * launch, in place:
  *     target[i][e] = fl32( fl32(tau * online[i][e]) + fl32(one_minus_tau * target[i][e]) )

@@ -1,0 +1,372 @@
+// The multi-agent (SAC) learner's first step on a sampled batch: the twin target critics of Global_SAC_Critic.global_learn
+// (Simulation-MARL-BCD/global_sac_critic.py:338-352) -- each a CriticNetwork.forward (networks.py:38-49), a plain ReLU MLP
+// on cat([state, action]) -- and the TD target, in ONE kernel, for n_rows rows and n_nets in {1, 2} weight sets of one shape:
+//     x   = [state[row] | action[row]]                     two pointers, read in place
+//     h1  = relu(W1 x + b1);  h2 = relu(W2 h1 + b2);  h3 = relu(W3 h2 + b3);  q = wq . h3 + bq        per net
+//     m   = n_nets == 2 ? min(q_1, q_2) : q_1
+//     ent = coef[0] logp_power[row] + coef[1] logp_intent[row]          a term whose logp pointer is NULL is absent
+//     y   = done ? reward : reward + gamma (m - ent)                    a select, as target[done] = rewards_g[done] is
+// Precision is that of k_sarl_critic.hip / k_sarl_actor.hip / k_policy_mlp.hip (read their headers): D = A.B with A =
+// weights (rows = output features) and B = activations (columns = 32 rows of the batch) on v_mfma_f32_32x32x16_f16, both
+// operands split into float16 hi + lo, the weight pre-multiplied by a power of two, three partial products accumulated
+// in float32, the scaling undone where the float32 bias is added.  There is no LayerNorm, so fc1 needs neither centring
+// nor a bias row.
+//
+// The FORM is that of k_sarl_critic: a workgroup of four wavefronts shares ONE tile of 32 rows and splits the OUTPUT
+// FEATURES of every layer four ways: wavefront w owns fc1 groups w, w + 4, .. and output tiles [w MT, (w + 1) MT) of fc2 /
+// fc3 (MT = features / 128).  A weight fragment is used by exactly one wavefront of the workgroup, so it goes L2 ->
+// registers with plain global loads, four k-steps ahead of its MFMAs, and LDS holds what IS shared:
+//   s_in  the split B fragments of the input x, staged ONCE for both nets   [KS k-steps][hi | lo][64 lanes] x 16 bytes
+//   s_h   the fc1 activations, then the fc2 activations (each dead before the next)  [max(2 NG, fc2 / 16)][hi | lo][64]
+//   s_red the per-row partial sums of the q dot product, one slot per net: [2][4 waves][32]
+// A lane leaves its C/D tile in LDS as two k-steps (registers 8u .. 8u+7 = k-step u, the permuted k order of the actor)
+// and every wavefront reads them back as B operands with one ds_read_b128 per fragment.  The workgroup walks the nets
+// one after the other, keeps q_1 in its s_red slot and finishes with the epilogue.
+//
+// Every barrier sits under wave-uniform control flow: all loop bounds and the net count come from kernel arguments,
+// template parameters and the wavefront index.  Rows at or beyond n_rows are computed on row 0's input and never stored.
+// No global address depends on loaded data; every weight prefetch index is clamped to the last fragment of its block.
+#include "risvec_launch.hpp"
+#include "risvec_step.hpp"
+
+namespace risvec {
+namespace {
+
+typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+typedef float f32x16_t __attribute__((ext_vector_type(16)));
+typedef float f32x8_t __attribute__((ext_vector_type(8)));
+
+struct MarlNetPtrs {
+    const uint4* ws;               // the weight stream: fragment rows of 64 x 16 bytes
+    const float* scales;           // [3] undo the fc1, fc2 and fc3 weight scalings
+    const float* b1;               // [F1]
+    const float* b2;               // [F2]
+    const float* b3;               // [F3]
+    const float* qw;               // [F3]
+    const float* qb;               // [1]
+};
+
+struct MarlCriticArgs {
+    long long n_rows;
+    int S, NA, KS, NG, n_nets;     // KS = k-steps of 16 of [state | action]; NG = fc1 / 32
+    const float* state;            // [n_rows, S]
+    const float* action;           // [n_rows, NA]
+    MarlNetPtrs net[2];
+    const float* reward;           // [n_rows] or NULL
+    const uint8_t* done;           // [n_rows] or NULL
+    float gamma;
+    const float* coef;             // [2] or NULL
+    const float* lp;               // [n_rows] or NULL
+    const float* li;               // [n_rows] or NULL
+    float* q1;                     // [n_rows] or NULL
+    float* q2;                     // [n_rows] or NULL
+    float* y;                      // [n_rows] or NULL
+};
+
+constexpr int kMcBlock = 256;        // 4 wavefronts = 1 per SIMD, all on the same 32 rows
+constexpr int kMcWaves = 4;
+constexpr int kAhead = 4;            // weight fragments are requested this many k-steps ahead of their MFMAs
+constexpr int kRedSlots = 2;
+
+__device__ __forceinline__ void split16(const f32x8_t& y, half8_t& hi, half8_t& lo) {
+    hi = __builtin_convertvector(y, half8_t);
+    lo = __builtin_convertvector(y - __builtin_convertvector(hi, f32x8_t), half8_t);
+}
+
+__device__ __forceinline__ half8_t ld_frag(const uint4* p) {
+    const uint4 v = *p;
+    return __builtin_bit_cast(half8_t, v);
+}
+
+__device__ __forceinline__ f32x16_t mfma3(const half8_t& ah, const half8_t& al, const half8_t& bh, const half8_t& bl, f32x16_t d) {
+    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, d, 0, 0, 0);
+    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, d, 0, 0, 0);
+    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, d, 0, 0, 0);
+    return d;
+}
+
+// acc[m] += W_m . B over nks k-steps.  wa: this wavefront's block of the stream, [nks][MT][hi | lo][64]; sb: the B
+// fragments in LDS, [nks][hi | lo][64].  nks >= 1.
+template <int MT>
+__device__ __forceinline__ void gemm_tiles(f32x16_t (&acc)[MT], const uint4* __restrict__ wa, const uint4* sb, int nks, int lane) {
+    half8_t ah[kAhead][MT], al[kAhead][MT];
+    auto fetch = [&](int i, int s) {
+        const uint4* p = wa + (size_t)(s < nks ? s : nks - 1) * (2 * MT * kWave) + lane;
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            ah[i][m] = ld_frag(p + (2 * m) * kWave);
+            al[i][m] = ld_frag(p + (2 * m + 1) * kWave);
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < kAhead; ++i) fetch(i, i);
+    for (int s0 = 0; s0 < nks; s0 += kAhead) {
+#pragma unroll
+        for (int i = 0; i < kAhead; ++i) {
+            const int s = s0 + i;
+            if (s < nks) {
+                const half8_t bh = ld_frag(sb + (2 * s) * kWave + lane), bl = ld_frag(sb + (2 * s + 1) * kWave + lane);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[m] = mfma3(ah[i][m], al[i][m], bh, bl, acc[m]);
+                fetch(i, s + kAhead);
+            }
+        }
+    }
+}
+
+// 16 per-feature parameters tab[base ..] in C/D register order: features (q & 3) + 8 (q >> 2) + 4 h
+__device__ __forceinline__ f32x16_t tile_of(const float* tab, int base, int h) {
+    f32x16_t tl;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 q4 = *reinterpret_cast<const float4*>(tab + base + 8 * g + 4 * h);
+        tl[4 * g] = q4.x; tl[4 * g + 1] = q4.y; tl[4 * g + 2] = q4.z; tl[4 * g + 3] = q4.w;
+    }
+    return tl;
+}
+
+__device__ __forceinline__ float sum16(const f32x16_t& v) {
+    float s = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += v[q];
+    return s;
+}
+
+// relu(acc u + bias) of one C/D tile
+__device__ __forceinline__ f32x16_t bias_relu(const f32x16_t& acc, float u, const f32x16_t& b) {
+    f32x16_t y = acc * u + b;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) y[q] = fmaxf(y[q], 0.0f);
+    return y;
+}
+
+// registers 8u .. 8u+7 of a C/D tile -> the split B fragments of k-step 2 tile + u, left in LDS
+__device__ __forceinline__ void put_tile(uint4* sh, int tile, const f32x16_t& y, int lane) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        f32x8_t v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = y[8 * u + j];
+        half8_t hi, lo;
+        split16(v, hi, lo);
+        uint4* p = sh + ((2 * tile + u) * 2) * kWave + lane;
+        p[0] = __builtin_bit_cast(uint4, hi);
+        p[kWave] = __builtin_bit_cast(uint4, lo);
+    }
+}
+
+// rows of 1 KiB of the three blocks of one net's stream, in stream order
+struct MarlLayout { long long fc1, fc2, fc3, rows; };
+__host__ __device__ inline MarlLayout marl_layout(int KS, int NG, int MT2, int MT3) {
+    MarlLayout l;
+    l.fc1 = 0;
+    l.fc2 = l.fc1 + (long long)NG * KS * 2;
+    l.fc3 = l.fc2 + (long long)kMcWaves * (2 * NG) * MT2 * 2;
+    l.rows = l.fc3 + (long long)kMcWaves * (8 * MT2) * MT3 * 2;
+    return l;
+}
+
+template <int MT2, int MT3>
+__global__ void __launch_bounds__(kMcBlock)
+k_marl_critic(MarlCriticArgs A) {
+    constexpr int K3 = 8 * MT2;                               // fc3 k-steps = fc2 / 16
+    extern __shared__ uint4 s_mem[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    const int KS = A.KS, NG = A.NG;
+    uint4* s_in = s_mem;                                      // [KS][2][64]
+    uint4* s_h = s_mem + KS * 2 * kWave;                      // [max(2 NG, K3)][2][64]
+    const int hsteps = max(2 * NG, K3);
+    float* s_red = reinterpret_cast<float*>(s_h + hsteps * 2 * kWave);   // [kRedSlots][4][32]
+    const MarlLayout L = marl_layout(KS, NG, MT2, MT3);
+    const long long e0 = (long long)blockIdx.x * 32;
+
+    // ---- the input as split B fragments: k-step s, lane (r, h) holds x[16 s + 8 h + j], j < 8; x = [state | action | 0 ..]
+    {
+        const int S = A.S, W = A.S + A.NA;
+        for (int idx = tid; idx < KS * kWave; idx += kMcBlock) {
+            const int s = idx >> 6, l = idx & 63, rr = l & 31, hh = l >> 5;
+            const long long row = e0 + rr < A.n_rows ? e0 + rr : 0;
+            const float* ps = A.state + row * S;
+            const float* pa = A.action + row * A.NA;
+            f32x8_t v;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = 16 * s + 8 * hh + j;
+                v[j] = k < S ? ps[k] : (k < W ? pa[k - S] : 0.0f);
+            }
+            half8_t hi, lo;
+            split16(v, hi, lo);
+            s_in[(2 * s) * kWave + l] = __builtin_bit_cast(uint4, hi);
+            s_in[(2 * s + 1) * kWave + l] = __builtin_bit_cast(uint4, lo);
+        }
+    }
+    __syncthreads();
+
+    // One net: fc1 -> s_h, fc2 -> s_h, fc3 and the q dot product -> s_red[slot].  Called under wave-uniform control flow;
+    // ends on a barrier, after which s_h is free again and s_red[slot] is complete.
+    auto run_net = [&](const MarlNetPtrs& P, int slot) {
+        const float u1 = P.scales[0], u2 = P.scales[1], u3 = P.scales[2];
+        // ---- fc1, groups wave, wave + 4, ..: bias, ReLU, and the split fragments of the group's 32 features go to LDS
+        const int ngw = NG > wave ? (NG - wave + kMcWaves - 1) / kMcWaves : 0;
+        if (ngw > 0) {                                        // wave-uniform; no barrier inside
+            const int nst = ngw * KS;
+            const uint4* w1 = P.ws + L.fc1 * kWave + lane;
+            half8_t ah[kAhead], al[kAhead];
+            int fg = wave, fs = 0;                            // (group, k-step) of the next fetch
+            auto fetch = [&](int i) {
+                const uint4* p = w1 + (size_t)(fg * KS + fs) * (2 * kWave);
+                ah[i] = ld_frag(p);
+                al[i] = ld_frag(p + kWave);
+                if (fs + 1 < KS) ++fs;
+                else if (fg + kMcWaves < NG) { fg += kMcWaves; fs = 0; }    // else: stay on the last fragment
+            };
+#pragma unroll
+            for (int i = 0; i < kAhead; ++i) fetch(i);
+            f32x16_t d;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) d[q] = 0.0f;
+            int g = wave, s = 0;
+            for (int i0 = 0; i0 < nst; i0 += kAhead) {
+#pragma unroll
+                for (int i = 0; i < kAhead; ++i) {
+                    if (i0 + i < nst) {
+                        const half8_t bh = ld_frag(s_in + (2 * s) * kWave + lane), bl = ld_frag(s_in + (2 * s + 1) * kWave + lane);
+                        d = mfma3(ah[i], al[i], bh, bl, d);
+                        fetch(i);
+                        if (++s == KS) {
+                            put_tile(s_h, g, bias_relu(d, u1, tile_of(P.b1, 32 * g, h)), lane);
+#pragma unroll
+                            for (int q = 0; q < 16; ++q) d[q] = 0.0f;
+                            s = 0;
+                            g += kMcWaves;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- fc2: output tiles [wave MT2, (wave + 1) MT2) over all 2 NG k-steps
+        f32x16_t acc[MT2];
+#pragma unroll
+        for (int m = 0; m < MT2; ++m)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[m][q] = 0.0f;
+        gemm_tiles<MT2>(acc, P.ws + (L.fc2 + (long long)wave * (2 * NG) * MT2 * 2) * kWave, s_h, 2 * NG, lane);
+        __syncthreads();                                      // every wavefront is past its fc2 MFMAs: s_h is free
+#pragma unroll
+        for (int m = 0; m < MT2; ++m) {
+            const int t = wave * MT2 + m;
+            put_tile(s_h, t, bias_relu(acc[m], u2, tile_of(P.b2, 32 * t, h)), lane);
+        }
+        __syncthreads();
+
+        // ---- fc3 + ReLU, then the 1-wide q layer as a dot product in registers
+        f32x16_t a3[MT3];
+#pragma unroll
+        for (int m = 0; m < MT3; ++m)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) a3[m][q] = 0.0f;
+        gemm_tiles<MT3>(a3, P.ws + (L.fc3 + (long long)wave * K3 * MT3 * 2) * kWave, s_h, K3, lane);
+        f32x16_t qs;
+#pragma unroll
+        for (int m = 0; m < MT3; ++m) {
+            const int f0 = 32 * (wave * MT3 + m);
+            const f32x16_t p = bias_relu(a3[m], u3, tile_of(P.b3, f0, h)) * tile_of(P.qw, f0, h);
+            qs = m == 0 ? p : qs + p;
+        }
+        float qp = sum16(qs);
+        qp += __shfl_xor(qp, 32, kWave);
+        if (h == 0) s_red[(slot * kMcWaves + wave) * 32 + r] = qp;
+        __syncthreads();                                      // every wavefront is past its fc3 MFMAs: s_h is free
+    };
+    run_net(A.net[0], 0);
+    const bool twin = A.n_nets == 2;                          // a kernel argument: uniform over the grid
+    if (twin) run_net(A.net[1], 1);
+
+    if (wave == 0 && h == 0) {
+        const long long e = e0 + r;
+        if (e < A.n_rows) {
+            auto red = [&](int slot) {
+                const float* p = s_red + slot * kMcWaves * 32 + r;
+                return ((p[0] + p[32]) + p[64]) + p[96];
+            };
+            const float qv1 = red(0) + A.net[0].qb[0];
+            float m = qv1;
+            if (A.q1) A.q1[e] = qv1;
+            if (twin) {
+                const float qv2 = red(1) + A.net[1].qb[0];
+                if (A.q2) A.q2[e] = qv2;
+                m = fminf(qv1, qv2);
+            }
+            if (A.y) {
+                const float rw = A.reward[e];
+                float t = m;
+                if (A.lp || A.li) {
+                    float ent = 0.0f;
+                    if (A.lp) ent = A.coef[0] * A.lp[e];
+                    if (A.li) ent = A.lp ? fmaf(A.coef[1], A.li[e], ent) : A.coef[1] * A.li[e];
+                    t = m - ent;
+                }
+                A.y[e] = A.done[e] ? rw : fmaf(A.gamma, t, rw);      // a select, as target[done] = rewards_g[done] is
+            }
+        }
+    }
+}
+
+int ks_of(int width) { return (width + 15) / 16; }
+
+template <int MT2, int MT3>
+hipError_t launch_marl(const MarlCriticArgs& a, hipStream_t st) {
+    const int hsteps = std::max(2 * a.NG, 8 * MT2);
+    const size_t lds = (size_t)(a.KS + hsteps) * 2 * kWave * sizeof(uint4) + (size_t)kRedSlots * kMcWaves * 32 * sizeof(float);
+    auto kern = k_marl_critic<MT2, MT3>;
+    if (lds > 64 * 1024) {
+        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (err != hipSuccess) return err;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_rows + 31) / 32)), dim3(kMcBlock), lds, st, a);
+    return hipGetLastError();
+}
+
+template <int MT2>
+hipError_t launch_marl_f3(int F3, const MarlCriticArgs& a, hipStream_t st) {
+    return F3 == 256 ? launch_marl<MT2, 2>(a, st) : launch_marl<MT2, 1>(a, st);
+}
+
+}  // namespace
+
+bool marl_critic_supported(int S, int A, int F1, int F2, int F3) {
+    return S >= 1 && A >= 1 && S <= 127 && A <= 127 && S + A <= 128 && F1 >= 32 && F1 % 32 == 0 && F1 <= 1024 &&
+           (F2 == 128 || F2 == 256 || F2 == 512) && (F3 == 128 || F3 == 256);
+}
+
+long long marl_critic_stream_bytes(int S, int A, int F1, int F2, int F3) {
+    if (!marl_critic_supported(S, A, F1, F2, F3)) return 0;
+    return marl_layout(ks_of(S + A), F1 / 32, F2 / 128, F3 / 128).rows * kWave * (long long)sizeof(uint4);
+}
+
+hipError_t launch_marl_critic(long long n_rows, int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticNet* nets,
+                              const float* state, const float* action, const float* reward, const uint8_t* done, float gamma,
+                              const float* coef, const float* logp_power, const float* logp_intent, float* q1, float* q2,
+                              float* y, hipStream_t st) {
+    if (!marl_critic_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > 2) return hipErrorInvalidValue;
+    MarlCriticArgs c{};
+    c.n_rows = n_rows; c.S = S; c.NA = A; c.KS = ks_of(S + A); c.NG = F1 / 32; c.n_nets = n_nets;
+    c.state = state; c.action = action;
+    for (int i = 0; i < 2; ++i) {
+        const RisVecMarlCriticNet& n = nets[i < n_nets ? i : 0];      // the unused slot of a single net repeats net 1
+        c.net[i] = MarlNetPtrs{static_cast<const uint4*>(n.wstream), n.scales, n.b1, n.b2, n.b3, n.qw, n.qb};
+    }
+    c.reward = reward; c.done = done; c.gamma = gamma; c.coef = coef; c.lp = logp_power; c.li = logp_intent;
+    c.q1 = q1; c.q2 = q2; c.y = y;
+    note_kernel("k_marl_critic<%d,%d>x%d", F2 / 128, F3 / 128, n_nets);
+    switch (F2) {
+        case 128: return launch_marl_f3<1>(F3, c, st);
+        case 256: return launch_marl_f3<2>(F3, c, st);
+        case 512: return launch_marl_f3<4>(F3, c, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace risvec

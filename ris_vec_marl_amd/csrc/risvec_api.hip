@@ -1056,6 +1056,52 @@ int risvec_sarl_critic_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t f
                                                       workspace, (hipStream_t)stream));
 }
 
+int risvec_marl_critic_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
+    return risvec::marl_critic_supported(state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;
+}
+
+int64_t risvec_marl_critic_stream_bytes(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
+    return risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+}
+
+int risvec_marl_critic(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                       int32_t n_nets, const RisVecMarlCriticNet* nets, const float* state, const float* action,
+                       const float* reward, const uint8_t* done, float gamma, const float* coef, const float* logp_power,
+                       const float* logp_intent, float* q1, float* q2, float* y, risvec_stream_t stream) {
+    const char* fn = "risvec_marl_critic";
+    if (n_rows < 1) return fail(RISVEC_ERR_ARG, "%s: n_rows=%d must be >= 1", fn, n_rows);
+    if (n_nets < 1 || n_nets > 2) return fail(RISVEC_ERR_ARG, "%s: n_nets=%d must be 1 or 2", fn, n_nets);
+    if (!risvec::marl_critic_supported(state_dims, action_dims, fc1, fc2, fc3))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (built for state_dims + "
+                    "action_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256; use library "
+                    "kernels elsewhere)", fn, state_dims, action_dims, fc1, fc2, fc3);
+    if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
+    const long long need = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+    for (int c = 0; c < n_nets; ++c) {
+        const RisVecMarlCriticNet& n = nets[c];
+        if (n.wstream_bytes != need)
+            return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream_bytes=%lld, this shape's weight stream has %lld", fn, c,
+                        (long long)n.wstream_bytes, need);
+        const struct { const void* p; const char* name; } ptrs[] = {{n.wstream, "wstream"}, {n.scales, "scales"}, {n.b1, "b1"},
+                                                                    {n.b2, "b2"}, {n.b3, "b3"}, {n.qw, "qw"}};
+        for (const auto& w : ptrs) {
+            if (!w.p) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is NULL", fn, c, w.name);
+            if (!aligned16(w.p)) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is not 16-byte aligned", fn, c, w.name);
+        }
+        if (!n.qb) return fail(RISVEC_ERR_ARG, "%s: nets[%d].qb is NULL", fn, c);
+    }
+    if (!state || !action) return fail(RISVEC_ERR_ARG, "%s: state or action is NULL", fn);
+    if (!q1 && !q2 && !y) return fail(RISVEC_ERR_ARG, "%s: q1, q2 and y are all NULL", fn);
+    if (q2 && n_nets != 2) return fail(RISVEC_ERR_ARG, "%s: q2 needs n_nets == 2", fn);
+    if (y && (!reward || !done)) return fail(RISVEC_ERR_ARG, "%s: y needs reward and done", fn);
+    if ((logp_power || logp_intent) && !coef) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need coef", fn);
+    if ((logp_power || logp_intent) && !y) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need y", fn);
+    if (!std::isfinite(gamma)) return fail(RISVEC_ERR_ARG, "%s: gamma=%g must be finite", fn, (double)gamma);
+    return finish(fn, risvec::launch_marl_critic(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, state, action,
+                                                 reward, done, gamma, coef, logp_power, logp_intent, q1, q2, y,
+                                                 (hipStream_t)stream));
+}
+
 int risvec_soft_update(int32_t n_tensors, const float* const* online, float* const* target, const int64_t* numel, float tau,
                        float one_minus_tau, risvec_stream_t stream) {
     const char* fn = "risvec_soft_update";

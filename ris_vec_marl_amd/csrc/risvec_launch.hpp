@@ -112,6 +112,16 @@ hipError_t launch_sarl_critic_pack(int IN, int F1, int F2, int F3, int A, const 
                                    const float* Wav, const float* W3, void* wstream, float* scales, void* workspace,
                                    hipStream_t st);
 
+// The SAC twin global critic forward and TD target in one launch (k_marl_critic.hip): n_nets in {1, 2} plain ReLU MLPs on
+// [state | action].  marl_critic_stream_bytes(): the size of ONE net's weight stream for a supported shape (0 otherwise).
+// reward / done are read only when y is given, coef only with a logp pointer; q1, q2 and y are optional.
+bool marl_critic_supported(int S, int A, int F1, int F2, int F3);
+long long marl_critic_stream_bytes(int S, int A, int F1, int F2, int F3);
+hipError_t launch_marl_critic(long long n_rows, int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticNet* nets,
+                              const float* state, const float* action, const float* reward, const uint8_t* done, float gamma,
+                              const float* coef, const float* logp_power, const float* logp_intent, float* q1, float* q2,
+                              float* y, hipStream_t st);
+
 // target = tau online + one_minus_tau target for n_tensors <= kSoftUpdateMax tensors in one launch (k_soft_update.hip);
 // the three arrays are host arrays, copied into the kernel's argument block.
 constexpr int kSoftUpdateMax = 32;
