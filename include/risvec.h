@@ -874,6 +874,36 @@ int risvec_marl_critic(int32_t n_rows, int32_t state_dims, int32_t action_dims, 
                        int32_t n_nets, const RisVecMarlCriticNet *nets, const float *state, const float *action,
                        const float *reward, const uint8_t *done, float gamma, const float *coef, const float *logp_power,
                        const float *logp_intent, float *q1, float *q2, float *y, risvec_stream_t stream);
+/* The prepared weights of risvec_marl_critic for n_nets in {1, 2} nets of one shape, built on the device from the float32
+ * weights as the learner holds them (Linear weights [out, in]), read in place: call it after every update of the target
+ * critics (each call of update_global_network_parameters, global_sac_critic.py:394-400).  Two launches on `stream` for
+ * all nets together, no allocation, no synchronisation.  The first takes the largest magnitudes of slices of W1, W2 and
+ * W3 of every net, one workspace slot per net, matrix and slice (one writer per slot, every slot written: no atomics,
+ * nothing to initialise).  The second combines the slots into s = floor(log2f(64 / max(amax, 1e-30))) clamped to
+ * [-40, 40] per net and matrix -- quotient and logarithm in float32 for all three matrices -- and writes every 16-byte
+ * fragment of the layout above exactly once, padding included (the buffers may hold anything before the call): scale
+ * by 2^s in float64, round to float32, S_0 = half(x), S_1 = half(x - float(S_0)).  A maximum does not depend on the order
+ * it is taken in and everything else is exact or correctly rounded: the same bits on every call.
+ *   W1, W2, W3     [fc1, state_dims + action_dims], [fc2, fc1], [fc3, fc2]: float-aligned (W2 and W3 of every net on 16
+ *                  bytes lets their fragments be read as float4);
+ *   wstream, wstream_bytes  the stream to write, 16-byte aligned, and its size = risvec_marl_critic_stream_bytes(...);
+ *   scales [3]     receives 2^-s of fc1, fc2 and fc3;
+ *   workspace      risvec_marl_critic_pack_workspace bytes (0: a shape risvec_marl_critic is not built for, or n_nets
+ *                  outside {1, 2}), 16-byte aligned, of any content; holds the maxima between the launches.
+ * Shapes outside risvec_marl_critic_supported return RISVEC_ERR_UNSUPPORTED.  A NULL or misaligned pointer, n_nets
+ * outside {1, 2}, a wrong wstream_bytes, too small a workspace and two nets that name the same wstream or the same
+ * scales return RISVEC_ERR_ARG; all are reported before anything is launched and without touching a device. */
+typedef struct RisVecMarlCriticPackNet {
+    const float *W1, *W2, *W3;
+    void *wstream;
+    int64_t wstream_bytes;
+    float *scales;
+} RisVecMarlCriticPackNet;
+size_t risvec_marl_critic_pack_workspace(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                                         int32_t n_nets);
+int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
+                            const RisVecMarlCriticPackNet *nets, void *workspace, size_t workspace_bytes,
+                            risvec_stream_t stream);
 /* The Polyak blend of update_network_parameters (Simulation-SARL/ddpg_torch.py:104-130) for n_tensors tensors in ONE
  * launch, in place:
  *     target[i][e] = fl32( fl32(tau * online[i][e]) + fl32(one_minus_tau * target[i][e]) )

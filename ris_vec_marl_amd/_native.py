@@ -159,6 +159,10 @@ class RisVecMarlCriticNet(C.Structure):
                 ("qw", _FP), ("qb", _FP)]
 
 
+class RisVecMarlCriticPackNet(C.Structure):
+    _fields_ = [("W1", _FP), ("W2", _FP), ("W3", _FP), ("wstream", _FP), ("wstream_bytes", C.c_int64), ("scales", _FP)]
+
+
 NOMA_MAX_VEH = 16
 NOMA_HAS_LAST, NOMA_UNSTICK_USED, NOMA_HAS_GROUPS = 1, 2, 4
 
@@ -247,6 +251,8 @@ _PROTOS = {
     "risvec_marl_critic_supported": (C.c_int, [C.c_int32] * 5),
     "risvec_marl_critic_stream_bytes": (C.c_int64, [C.c_int32] * 5),
     "risvec_marl_critic": (C.c_int, [C.c_int32] * 7 + [_FP] * 5 + [C.c_float] + [_FP] * 7),
+    "risvec_marl_critic_pack_workspace": (C.c_size_t, [C.c_int32] * 6),
+    "risvec_marl_critic_pack": (C.c_int, [C.c_int32] * 6 + [_FP, _FP, C.c_size_t, _FP]),
     "risvec_soft_update": (C.c_int, [C.c_int32, _FP, _FP, _FP, C.c_float, C.c_float, _FP]),
     "risvec_policy_heads": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "risvec_policy_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64, C.c_uint32,

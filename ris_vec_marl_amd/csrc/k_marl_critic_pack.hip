@@ -1,0 +1,236 @@
+// The weight streams of k_marl_critic.hip, built on the device from the float32 weights of n_nets in {1, 2} nets in two
+// launches: what pack_marl_critic_weights (ris_vec_marl_amd/marl_critic.py) computes with library kernels once per net,
+// element for element.
+//
+//   k_marl_critic_pack_stats  kMaxBlocks x n_nets workgroups that never talk to each other.  Workgroup (b, c) takes slice b
+//                             of W1, of W2 and of W3 of net c and leaves the largest magnitude of each in slot
+//                             [c][matrix][b] of the workspace.  A maximum does not depend on the order it is taken in, a
+//                             slot has one writer, every slot is written: no atomics, no counters, nothing to initialise.
+//   k_marl_critic_pack        one lane per PAIR of 16-byte fragments: the hi and the lo fragment of the same 8 weights
+//                             are adjacent rows of the stream (t is the fastest row index of all three blocks), so a lane
+//                             reads its 8 weights once and stores both; every stream exactly once.  blockIdx.y is the
+//                             net.  Every wavefront first combines the kMaxBlocks slots of its net's matrix (one per
+//                             lane, a butterfly of maxima) into s = clamp(floor(log2f(64 / max(amax, 1e-30))), -40, 40)
+//                             -- the quotient and the logarithm in float32 for all three: this net's fc1 operand is the
+//                             float32 weight itself, not a centred float64 one -- then scales in float64, rounds to
+//                             float32 and splits into hi = half(ws), lo = half(ws - float(hi)).  fc1 columns beyond
+//                             state_dims + action_dims are stored as zeros.  Wavefront 0 of each net writes that net's
+//                             scales[3] = 2^-s.
+//
+// W1 rows are state_dims + action_dims floats wide: read float by float.  W2 and W3 rows are multiples of 32 floats wide,
+// so their fragments are two float4 wherever every such matrix of the call starts on 16 bytes, and eight floats
+// elsewhere (a launch-wide choice).  No product feeds a sum anywhere in this file, so there is nothing for the compiler
+// to contract; the pragma below says so all the same.
+#include "risvec_launch.hpp"
+
+#pragma clang fp contract(off)
+
+// How many workgroups per net share the maxima of W1, W2 and W3 (1 .. 64).  A build-time constant so that an A/B build
+// can measure another count (tools/time_marl_critic_refresh.py records the one that was measured against a single
+// workgroup).
+#ifndef RISVEC_MARL_CRITIC_PACK_MAX_BLOCKS
+#define RISVEC_MARL_CRITIC_PACK_MAX_BLOCKS 32
+#endif
+
+namespace risvec {
+namespace {
+
+typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+
+constexpr int kStatBlock = 1024;                 // 16 wavefronts per workgroup of the statistics launch
+constexpr int kStatWaves = kStatBlock / kWave;
+constexpr int kMaxBlocks = RISVEC_MARL_CRITIC_PACK_MAX_BLOCKS;   // workgroups per net that take the maxima; <= 64
+constexpr int kPackBlock = 256;
+constexpr int kWaves = 4;                        // wavefronts of k_marl_critic: each owns a quarter of a layer's tiles
+constexpr int kMaxNets = 2;
+static_assert(kMaxBlocks >= 1 && kMaxBlocks <= kWave, "one slot per lane of a wavefront");
+
+// scales / maxima are kept in the order of scales[3]: fc1, fc2, fc3
+enum { kFc1 = 0, kFc2 = 1, kFc3 = 2 };
+
+struct PackNet {
+    const float* W1;                             // [F1, IN]
+    const float* W2;                             // [F2, F1]
+    const float* W3;                             // [F3, F2]
+    uint4* ws;                                   // [rows, 64] 16-byte fragments
+    float* scales;                               // [3]
+};
+
+struct PackArgs {
+    int IN, F1, F2, F3;
+    int KS, NG, MT2, MT3;
+    int n_fc1, n_fc2, n_fc3;                     // fragment-row pairs of the three blocks, in stream order
+    int vec;                                     // W2 and W3 of every net start on 16 bytes
+    PackNet net[kMaxNets];
+    float* amax;                                 // workspace: [n_nets][3][kMaxBlocks] slices of fc1, fc2, fc3
+};
+
+// net c of the call (c is uniform over the workgroup): a select per field, never an indexed copy of the argument block
+__device__ __forceinline__ PackNet net_of(const PackArgs& P, int c) {
+    return PackNet{c ? P.net[1].W1 : P.net[0].W1, c ? P.net[1].W2 : P.net[0].W2, c ? P.net[1].W3 : P.net[0].W3,
+                   c ? P.net[1].ws : P.net[0].ws, c ? P.net[1].scales : P.net[0].scales};
+}
+
+// the largest of v over the workgroup (order-independent); red: kStatWaves slots of LDS
+__device__ __forceinline__ float block_max(float v, float* red) {
+    for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
+    __syncthreads();
+    float r = red[0];
+    for (int i = 1; i < kStatWaves; ++i) r = fmaxf(r, red[i]);
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ float max4(float m, const float4& v) {
+    return fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fmaxf(fabsf(v.y), fabsf(v.z))), fabsf(v.w));
+}
+
+// largest |x| of this thread's share of slice b (of nb) of p[0 .. n): floats up to the first 16-byte boundary and
+// behind the last whole float4 belong to slice 0, the float4 between are dealt out in nb runs
+__device__ __forceinline__ float amax_slice(const float* p, long long n, int b, int nb) {
+    const int tid = threadIdx.x;
+    long long head = (4 - (long long)((reinterpret_cast<uintptr_t>(p) >> 2) & 3)) & 3;
+    head = head < n ? head : n;
+    const long long n4 = (n - head) / 4, tail = head + 4 * n4;
+    float m = 0.0f;
+    if (b == 0) {
+        if (tid < head) m = fabsf(p[tid]);
+        if (tid >= kWave && tail + (tid - kWave) < n) m = fabsf(p[tail + (tid - kWave)]);     // at most 3 floats
+    }
+    const float4* v = reinterpret_cast<const float4*>(p + head);
+    const long long per = (n4 + nb - 1) / nb, lo = per * b, hi = lo + per < n4 ? lo + per : n4;
+#pragma unroll 4
+    for (long long i = lo + tid; i < hi; i += kStatBlock) m = max4(m, v[i]);
+    return m;
+}
+
+__global__ void __launch_bounds__(kStatBlock)
+k_marl_critic_pack_stats(PackArgs P) {
+    __shared__ float s_red[kStatWaves];
+    const int b = blockIdx.x, c = blockIdx.y;
+    const PackNet N = net_of(P, c);
+    const float a1 = block_max(amax_slice(N.W1, (long long)P.F1 * P.IN, b, kMaxBlocks), s_red);
+    const float a2 = block_max(amax_slice(N.W2, (long long)P.F2 * P.F1, b, kMaxBlocks), s_red);
+    const float a3 = block_max(amax_slice(N.W3, (long long)P.F3 * P.F2, b, kMaxBlocks), s_red);
+    if (threadIdx.x == 0) {
+        float* slot = P.amax + (size_t)c * 3 * kMaxBlocks + b;
+        slot[kFc1 * kMaxBlocks] = a1;
+        slot[kFc2 * kMaxBlocks] = a2;
+        slot[kFc3 * kMaxBlocks] = a3;
+    }
+}
+
+// the shift s of matrix `which` of net c (wave-uniform), every lane of the wavefront taking part
+__device__ __forceinline__ int shift_of(const PackArgs& P, int c, int which, int lane) {
+    float a = lane < kMaxBlocks ? P.amax[((size_t)c * 3 + which) * kMaxBlocks + lane] : 0.0f;
+    for (int o = kWave / 2; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, kWave));
+    return (int)fminf(fmaxf(floorf(log2f(64.0f / fmaxf(a, 1e-30f))), -40.0f), 40.0f);
+}
+
+// 8 scaled weights -> the hi and the lo halves: rows 2 pr and 2 pr + 1 of the stream
+__device__ __forceinline__ void store_pair(uint4* ws, long long pr, int lane, const float (&w)[8]) {
+    half8_t hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        hi[j] = (_Float16)w[j];
+        lo[j] = (_Float16)(w[j] - (float)hi[j]);
+    }
+    ws[(2 * pr) * kWave + lane] = __builtin_bit_cast(uint4, hi);
+    ws[(2 * pr + 1) * kWave + lane] = __builtin_bit_cast(uint4, lo);
+}
+
+// A fragment whose k index runs over an accumulator tile's rows: element j = X[f0 + 8 (j >> 2) + (j & 3)][n], where
+// X[f][n] = W[n * ld + f] (a Linear weight [out, in] read as [in, out]); f0 and ld multiples of 4
+__device__ __forceinline__ void acc_order_weights(const float* W, int ld, int n, int f0, bool vec, double mult, float (&w)[8]) {
+    const float* p = W + (size_t)n * ld + f0;
+    float v[8];
+    if (vec) {
+        const float4 lo4 = *reinterpret_cast<const float4*>(p);
+        const float4 hi4 = *reinterpret_cast<const float4*>(p + 8);
+        v[0] = lo4.x; v[1] = lo4.y; v[2] = lo4.z; v[3] = lo4.w; v[4] = hi4.x; v[5] = hi4.y; v[6] = hi4.z; v[7] = hi4.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = p[8 * (j >> 2) + (j & 3)];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = (float)((double)v[j] * mult);
+}
+
+__global__ void __launch_bounds__(kPackBlock)
+k_marl_critic_pack(PackArgs P) {
+    // pr, the pair of fragment rows, is the same for the 64 lanes of a wavefront: every branch below is wave-uniform
+    // but the column guard of fc1
+    const int idx = blockIdx.x * kPackBlock + threadIdx.x;       // < 2^31: at most 2560 pairs of rows per net
+    const int lane = idx & (kWave - 1), r = lane & 31, h = lane >> 5;
+    const int c = blockIdx.y;
+    int q = idx >> 6;
+    const long long pr = q;
+    if (q >= P.n_fc1 + P.n_fc2 + P.n_fc3) return;                // the last workgroup's spare wavefronts
+    const PackNet N = net_of(P, c);
+    if (q == 0) {                                                // wavefront 0 of this net: its three scales
+        float u = 0.0f;
+        for (int i = 0; i < 3; ++i) {
+            const int s = shift_of(P, c, i, lane);
+            if (lane == i) u = ldexpf(1.0f, -s);
+        }
+        if (lane < 3) N.scales[lane] = u;
+    }
+    float w[8];
+    if (q < P.n_fc1) {                                           // pair (g KS + s): [W1 | 0]
+        const double mult = ldexp(1.0, shift_of(P, c, kFc1, lane));
+        const int f = 32 * (q / P.KS) + r, s = q % P.KS, IN = P.IN;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = 16 * s + 8 * h + j;
+            w[j] = k < IN ? (float)((double)N.W1[(size_t)f * IN + k] * mult) : 0.0f;
+        }
+    } else if ((q -= P.n_fc1) < P.n_fc2) {                       // pair ((wv 2 NG + k) MT2 + m): X = W2^T
+        const double mult = ldexp(1.0, shift_of(P, c, kFc2, lane));
+        const int ks = 2 * P.NG, wv = q / (ks * P.MT2), k = (q / P.MT2) % ks, m = q % P.MT2;
+        acc_order_weights(N.W2, P.F1, 32 * (wv * P.MT2 + m) + r, 16 * k + 4 * h, P.vec != 0, mult, w);
+    } else {                                                     // pair ((wv fc2 / 16 + k) MT3 + m): X = W3^T
+        q -= P.n_fc2;
+        const double mult = ldexp(1.0, shift_of(P, c, kFc3, lane));
+        const int ks = 8 * P.MT2, wv = q / (ks * P.MT3), k = (q / P.MT3) % ks, m = q % P.MT3;
+        acc_order_weights(N.W3, P.F2, 32 * (wv * P.MT3 + m) + r, 16 * k + 4 * h, P.vec != 0, mult, w);
+    }
+    store_pair(N.ws, pr, lane, w);
+}
+
+}  // namespace
+
+long long marl_critic_pack_workspace(int S, int A, int F1, int F2, int F3, int n_nets) {
+    if (!marl_critic_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return 0;
+    const long long bytes = (long long)n_nets * 3 * kMaxBlocks * (long long)sizeof(float);
+    return (bytes + 15) / 16 * 16;
+}
+
+hipError_t launch_marl_critic_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
+                                   void* workspace, hipStream_t st) {
+    if (!marl_critic_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return hipErrorInvalidValue;
+    const int IN = S + A, KS = (IN + 15) / 16, NG = F1 / 32, MT2 = F2 / 128, MT3 = F3 / 128;
+    PackArgs a{};
+    a.IN = IN; a.F1 = F1; a.F2 = F2; a.F3 = F3; a.KS = KS; a.NG = NG; a.MT2 = MT2; a.MT3 = MT3;
+    a.n_fc1 = NG * KS; a.n_fc2 = kWaves * 2 * NG * MT2; a.n_fc3 = kWaves * 8 * MT2 * MT3;
+    // the pairs of rows in all: half the rows of marl_critic_stream_bytes()
+    const long long pairs = (long long)a.n_fc1 + a.n_fc2 + a.n_fc3;
+    if (pairs * 2048 != marl_critic_stream_bytes(S, A, F1, F2, F3)) return hipErrorInvalidValue;
+    uintptr_t align = 0;
+    for (int i = 0; i < kMaxNets; ++i) {
+        const RisVecMarlCriticPackNet& n = nets[i < n_nets ? i : 0];  // the unused slot of a single net repeats net 1
+        a.net[i] = PackNet{n.W1, n.W2, n.W3, static_cast<uint4*>(n.wstream), n.scales};
+        align |= reinterpret_cast<uintptr_t>(n.W2) | reinterpret_cast<uintptr_t>(n.W3);
+    }
+    a.vec = (align & 15u) == 0 ? 1 : 0;
+    a.amax = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(k_marl_critic_pack_stats, dim3(kMaxBlocks, n_nets), dim3(kStatBlock), 0, st, a);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    note_kernel("k_marl_critic_pack x%d", n_nets);
+    hipLaunchKernelGGL(k_marl_critic_pack, dim3((unsigned)((pairs * kWave + kPackBlock - 1) / kPackBlock), n_nets),
+                       dim3(kPackBlock), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace risvec

@@ -1102,6 +1102,51 @@ int risvec_marl_critic(int32_t n_rows, int32_t state_dims, int32_t action_dims, 
                                                  (hipStream_t)stream));
 }
 
+size_t risvec_marl_critic_pack_workspace(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                                         int32_t n_nets) {
+    return (size_t)risvec::marl_critic_pack_workspace(state_dims, action_dims, fc1, fc2, fc3, n_nets);
+}
+
+int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
+                            const RisVecMarlCriticPackNet* nets, void* workspace, size_t workspace_bytes,
+                            risvec_stream_t stream) {
+    const char* fn = "risvec_marl_critic_pack";
+    if (n_nets < 1 || n_nets > 2) return fail(RISVEC_ERR_ARG, "%s: n_nets=%d must be 1 or 2", fn, n_nets);
+    if (!risvec::marl_critic_supported(state_dims, action_dims, fc1, fc2, fc3))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (risvec_marl_critic is built "
+                    "for state_dims + action_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or "
+                    "256)", fn, state_dims, action_dims, fc1, fc2, fc3);
+    if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
+    const long long bytes = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+    for (int c = 0; c < n_nets; ++c) {
+        const RisVecMarlCriticPackNet& n = nets[c];
+        // the weights are read float by float wherever they do not start on 16 bytes: float alignment is all they need
+        const struct { const float* p; const char* name; } weights[] = {{n.W1, "W1"}, {n.W2, "W2"}, {n.W3, "W3"},
+                                                                        {n.scales, "scales"}};
+        for (const auto& w : weights) {
+            if (!w.p) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is NULL", fn, c, w.name);
+            if (reinterpret_cast<uintptr_t>(w.p) & 3u)
+                return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is not 4-byte aligned", fn, c, w.name);
+        }
+        if (!n.wstream) return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream is NULL", fn, c);
+        if (!aligned16(n.wstream)) return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream is not 16-byte aligned", fn, c);
+        if (n.wstream_bytes != bytes)
+            return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream_bytes=%lld, this shape's weight stream has %lld", fn, c,
+                        (long long)n.wstream_bytes, bytes);
+    }
+    if (n_nets == 2 && nets[0].wstream == nets[1].wstream)
+        return fail(RISVEC_ERR_ARG, "%s: nets[0].wstream and nets[1].wstream are the same buffer", fn);
+    if (n_nets == 2 && nets[0].scales == nets[1].scales)
+        return fail(RISVEC_ERR_ARG, "%s: nets[0].scales and nets[1].scales are the same buffer", fn);
+    REQ_PTR(workspace, "workspace");
+    const size_t need = (size_t)risvec::marl_critic_pack_workspace(state_dims, action_dims, fc1, fc2, fc3, n_nets);
+    if (workspace_bytes < need)
+        return fail(RISVEC_ERR_ARG, "%s: workspace_bytes=%zu, this call needs %zu (risvec_marl_critic_pack_workspace)", fn,
+                    workspace_bytes, need);
+    return finish(fn, risvec::launch_marl_critic_pack(state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, workspace,
+                                                      (hipStream_t)stream));
+}
+
 int risvec_soft_update(int32_t n_tensors, const float* const* online, float* const* target, const int64_t* numel, float tau,
                        float one_minus_tau, risvec_stream_t stream) {
     const char* fn = "risvec_soft_update";

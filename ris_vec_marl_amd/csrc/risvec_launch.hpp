@@ -121,6 +121,12 @@ hipError_t launch_marl_critic(long long n_rows, int S, int A, int F1, int F2, in
                               const float* state, const float* action, const float* reward, const uint8_t* done, float gamma,
                               const float* coef, const float* logp_power, const float* logp_intent, float* q1, float* q2,
                               float* y, hipStream_t st);
+// The weight streams and scales of n_nets in {1, 2} such nets from their float32 weights, in two launches in all
+// (k_marl_critic_pack.hip); the workspace holds marl_critic_pack_workspace() bytes (0: no such shape or net count) and
+// needs no initialisation.
+long long marl_critic_pack_workspace(int S, int A, int F1, int F2, int F3, int n_nets);
+hipError_t launch_marl_critic_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
+                                   void* workspace, hipStream_t st);
 
 // target = tau online + one_minus_tau target for n_tensors <= kSoftUpdateMax tensors in one launch (k_soft_update.hip);
 // the three arrays are host arrays, copied into the kernel's argument block.

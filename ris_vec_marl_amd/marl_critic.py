@@ -10,14 +10,15 @@ ReLU MLP on `cat([state, action])` -- the minimum, the entropy term and the TD t
 
 `BatchedTwinCritic.forward` / `td_target` are one launch (`risvec_marl_critic`); the log-probability sums arrive as
 tensors the learner already has.  `soft_update_from` is `update_global_network_parameters` (:394-400) for both nets in
-one launch.  Nothing here differentiates: the gradient half of `global_learn` stays with the learner.  No CPU compute
+one launch; with pack="device" the next `td_target` rebuilds both weight streams in two launches in all
+(`risvec_marl_critic_pack`).  Nothing here differentiates: the gradient half of `global_learn` stays with the learner.  No CPU compute
 path.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Mapping, NamedTuple, Optional, Tuple
+from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -81,6 +82,76 @@ def pack_marl_critic_weights(W1, W2, W3) -> Tuple[torch.Tensor, torch.Tensor]:
     return stream, torch.stack([u1, u2, u3]).float().contiguous()
 
 
+def pack_marl_critic_weights_device(weights: Sequence, out: Optional[Sequence] = None,
+                                    workspace: Optional[torch.Tensor] = None) -> list:
+    """`pack_marl_critic_weights` of 1 or 2 nets of one shape, computed on the device by `risvec_marl_critic_pack`
+    (csrc/k_marl_critic_pack.hip): two launches in all on the current stream, the float32 weights read in place, no copy
+    and no synchronisation.  weights: a sequence of 1 or 2 triples (W1, W2, W3), contiguous float32 tensors on one HIP
+    device; out: a matching sequence of (wstream [rows, 64, 8] float16, scales [3] float32) to write into, every byte of
+    them (default: new tensors); workspace: a uint8 tensor of at least `risvec_marl_critic_pack_workspace` bytes (default:
+    a new one).  -> the list of (wstream, scales) pairs, bit for bit what the host function gives net by net.  What would
+    have to be copied or converted is refused with ValueError."""
+    what = "pack_marl_critic_weights_device"
+    lib = N.load()
+    try:
+        weights = [tuple(ws) for ws in weights]
+    except TypeError:
+        raise ValueError("%s: weights is a sequence of 1 or 2 triples (W1, W2, W3)" % what) from None
+    n_nets = len(weights)
+    if n_nets not in (1, 2) or any(len(ws) != 3 for ws in weights):
+        raise ValueError("%s: weights is a sequence of 1 or 2 triples (W1, W2, W3), got %d nets" % (what, n_nets))
+    flat = [t for ws in weights for t in ws]
+    if not all(isinstance(t, torch.Tensor) for t in flat):
+        raise ValueError("%s: the weights must be contiguous float32 tensors on one device" % what)
+    dev = flat[0].device
+    if not all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in flat):
+        raise ValueError("%s: the weights must be contiguous float32 tensors on one device" % what)
+    if dev.type != "cuda":
+        raise ValueError("%s: the weights must be on a HIP device (they are read in place; pack_marl_critic_weights runs "
+                         "anywhere)" % what)
+    N.require_hip(dev)
+    if any(t.dim() != 2 for t in flat):
+        raise ValueError("%s: W1, W2 and W3 are Linear weights [out, in]" % what)
+    (F1, IN), F2, F3 = weights[0][0].shape, weights[0][1].shape[0], weights[0][2].shape[0]
+    want = ((F1, IN), (F2, F1), (F3, F2))
+    for c, ws in enumerate(weights):
+        for name, t, shape in zip(("W1", "W2", "W3"), ws, want):
+            if tuple(t.shape) != shape:
+                raise ValueError("%s: %s of net %d has shape %s, the shapes of net 1 ask for %s"
+                                 % (what, name, c + 1, tuple(t.shape), shape))
+    # the rule depends on the two widths through their sum only
+    dims = (IN - 1, 1, F1, F2, F3)
+    need = int(lib.risvec_marl_critic_pack_workspace(*dims, n_nets)) if IN >= 2 else 0
+    if need == 0:
+        raise ValueError("no fused twin-critic kernel for state_dims + action_dims=%d fc1=%d fc2=%d fc3=%d" % (IN, F1, F2, F3))
+    g = marl_critic_geom(*dims)
+    if out is None:
+        out = [(torch.empty(g.rows, 64, 8, dtype=torch.float16, device=dev), torch.empty(3, device=dev)) for _ in range(n_nets)]
+    try:
+        out = [tuple(o) for o in out]
+    except TypeError:
+        raise ValueError("%s: out is a sequence of %d pairs (wstream, scales)" % (what, n_nets)) from None
+    if len(out) != n_nets or any(len(o) != 2 for o in out):
+        raise ValueError("%s: out is a sequence of %d pairs (wstream, scales)" % (what, n_nets))
+    for c, (stream, scales) in enumerate(out):
+        if stream is None or scales is None:
+            raise ValueError("%s: out is a sequence of %d pairs (wstream, scales)" % (what, n_nets))
+        N.in_place(stream, torch.float16, (g.rows, 64, 8), "%s: out[%d][0]" % (what, c), dev)
+        N.in_place(scales, torch.float32, (3,), "%s: out[%d][1]" % (what, c), dev)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
+            or not workspace.is_contiguous()):
+        raise ValueError("%s: workspace must be a contiguous uint8 tensor on %s" % (what, dev))
+    nets = (N.RisVecMarlCriticPackNet * n_nets)()
+    for c, (ws, (stream, scales)) in enumerate(zip(weights, out)):
+        nets[c] = N.RisVecMarlCriticPackNet(ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), stream.data_ptr(),
+                                            stream.numel() * stream.element_size(), scales.data_ptr())
+    N.check(lib.risvec_marl_critic_pack(*dims, n_nets, C.cast(nets, C.c_void_p), workspace.data_ptr(), workspace.numel(),
+                                        N.stream(dev)))
+    return out
+
+
 def _unpack(stream: torch.Tensor, scales: torch.Tensor, state_dims: int, action_dims: int, fc1_dims: int, fc2_dims: int,
             fc3_dims: int) -> dict:
     """What the kernel multiplies by, as float64: {"fc1" [state_dims + action_dims, fc1], "fc2" [fc1, fc2], "fc3" [fc2,
@@ -103,6 +174,7 @@ class _Net:
     def __init__(self, device):
         self.device = device
         self.packed = (None, None)                            # (key, (wstream, scales))
+        self.pack_buffers = None                              # pack="device": (wstream, scales), at first use
 
 
 class BatchedTwinCritic:
@@ -112,6 +184,7 @@ class BatchedTwinCritic:
     local critics of `sac_agent.py:276-284` have the same class and the same target form, one call per agent."""
 
     GEMM_MODES = ("fused", "library")
+    PACK_MODES = ("host", "device")
     #: with gemm=None, batches of fewer rows than this run the library path even where the fused kernel is built
     #: (the measured crossover, profiles/marl_critic.json; 1 = fused at every row count)
     AUTO_MIN_ROWS = 1
@@ -143,6 +216,9 @@ class BatchedTwinCritic:
                              "state_dims + action_dims <= 128, fc1 %% 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, "
                              "256})" % ((gemm,) + dims + (", ".join(self.GEMM_MODES),)))
         self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
+        self._fused_ok = fused_ok
+        self._pack = "host"                                   # see `pack`
+        self._pack_workspace = None                           # pack="device": one workspace for both nets, at first use
         self.packs = 0                                        # how often a net's weight stream was rebuilt
         dev = self.device
         g = torch.Generator(device="cpu").manual_seed(seed)
@@ -159,6 +235,26 @@ class BatchedTwinCritic:
                 setattr(net, w, uni(fan_out, fan_in, r=r))
                 setattr(net, b, uni(fan_out, r=r))
             self.nets.append(net)
+
+    @property
+    def pack(self) -> str:
+        """How the fused kernel's weight streams are rebuilt after a weight update.  "host" (the default):
+        `pack_marl_critic_weights` once per stale net, library kernels into new tensors.  "device":
+        `pack_marl_critic_weights_device`, two launches for all stale nets together into buffers allocated once -- for
+        target critics that are blended every learning step (see `soft_update_from`); only where the fused kernel covers
+        the shape.  Setting it marks the streams stale; a refused value changes nothing."""
+        return self._pack
+
+    @pack.setter
+    def pack(self, mode) -> None:
+        if mode not in self.PACK_MODES or (mode == "device" and not self._fused_ok):
+            raise ValueError("pack=%r is not available for state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (modes: %s; device: "
+                             "where the fused kernel is built, see gemm)"
+                             % (mode, self.state_dims, self.action_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims,
+                                ", ".join(self.PACK_MODES)))
+        if mode != self._pack:
+            self._pack = mode
+            self.mark_stale()
 
     # ------------------------------------------------------------------ weights
     def state_dict(self) -> list:
@@ -230,15 +326,35 @@ class BatchedTwinCritic:
         for net in self.nets:
             net.packed = (None, net.packed[1])
 
-    def _fused_weights(self, net: _Net):
-        """(wstream, scales) of one net, rebuilt when a packed weight tensor is replaced or updated in place, or after
-        `mark_stale`."""
-        ws = tuple(getattr(net, a) for a in net._PACKED)
-        key = tuple((t.data_ptr(), t._version) for t in ws)
-        if net.packed[0] != key:
-            net.packed = (key, pack_marl_critic_weights(*ws))
-            self.packs += 1
-        return net.packed[1]
+    def _fused_weights(self) -> list:
+        """(wstream, scales) of every net; a net's are rebuilt when one of its packed weight tensors is replaced or updated
+        in place, or after `mark_stale` (pack="host": library kernels into new tensors, net by net; pack="device": the
+        stale nets together in two launches, into the buffers of their first rebuild)."""
+        stale = []
+        for net in self.nets:
+            ws = tuple(getattr(net, a) for a in net._PACKED)
+            key = tuple((t.data_ptr(), t._version) for t in ws)
+            if net.packed[0] != key:
+                stale.append((net, key, ws))
+        if stale and self._pack == "device":
+            dev = self.device
+            if self._pack_workspace is None:
+                need = int(N.load().risvec_marl_critic_pack_workspace(self.state_dims, self.action_dims, self.fc1_dims,
+                                                                      self.fc2_dims, self.fc3_dims, self.n_nets))
+                self._pack_workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
+            rows = marl_critic_geom(self.state_dims, self.action_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims).rows
+            for net, _, _ in stale:
+                if net.pack_buffers is None:
+                    net.pack_buffers = (torch.zeros(rows, 64, 8, dtype=torch.float16, device=dev), torch.zeros(3, device=dev))
+            pack_marl_critic_weights_device([ws for _, _, ws in stale], out=[net.pack_buffers for net, _, _ in stale],
+                                            workspace=self._pack_workspace)
+            for net, key, _ in stale:
+                net.packed = (key, net.pack_buffers)
+        else:
+            for net, key, ws in stale:
+                net.packed = (key, pack_marl_critic_weights(*ws))
+        self.packs += len(stale)
+        return [net.packed[1] for net in self.nets]
 
     # ------------------------------------------------------------------ forward
     def _rows(self, state, action) -> int:
@@ -278,8 +394,7 @@ class BatchedTwinCritic:
 
     def _launch(self, n, state, action, reward, done, gamma, coef, lp, li, qs, y) -> None:
         nets = (N.RisVecMarlCriticNet * self.n_nets)()
-        for c, net in enumerate(self.nets):
-            ws, scales = self._fused_weights(net)
+        for c, (net, (ws, scales)) in enumerate(zip(self.nets, self._fused_weights())):
             nets[c] = N.RisVecMarlCriticNet(ws.data_ptr(), ws.numel() * ws.element_size(), scales.data_ptr(), net.b1.data_ptr(),
                                             net.b2.data_ptr(), net.b3.data_ptr(), net.Wq.data_ptr(), net.bq.data_ptr())
         q1 = qs[0] if qs is not None else None
