@@ -238,6 +238,11 @@ const char *risvec_last_kernel(void);
 /* 1 when the calling thread's last step launch read theta as candidate indices (RISVEC_STEP_THETA_BY_INDEX, or
  * RISVEC_STEP_THETA_IDX_CURRENT where the kernel has that reader), 0 when it read the complex64 state.theta or none. */
 int risvec_last_theta_by_index(void);
+/* The walk of the calling thread's last software-pipeline launch (k_step_fused_pipe): 0 = its envs front to back, 1 =
+ * back to front.  The fused MARL step (ring form included) with the default cache policy alternates the two by the
+ * parity of its `counter` argument, so that a launch starts on the lines the launch before read last; the results and
+ * the kernel name do not depend on the walk.  Every other pipeline launch (non-temporal, SARL, gain) walks forward. */
+int risvec_last_pipe_walk(void);
 const char *risvec_last_error(void);
 
 /* Forms of a step call, for risvec_step_kernel(): risvec_step, risvec_step_fused, risvec_step_ring (cached / fused),
@@ -270,6 +275,11 @@ typedef struct RisVecForce {
     int32_t lat_alt;            /* its alternating walk (taken where the non-temporal form is not) */
     int32_t pipe_nt;            /* non-temporal loads in the software pipeline (MARL, SARL and gain)   */
     int32_t colsum_nt;          /* non-temporal loads in the BCD column sums                  */
+    int32_t pipe_rev;           /* the pipeline's walk (fused MARL step, default cache policy): BY_RULE the parity of
+                                   the step counter, OFF always forward, ON always backward (the non-temporal form has
+                                   no backward kernel and walks forward) */
+    int32_t pipe_waves;         /* 0 by rule, else the number of wavefronts the pipeline launches, each with a contiguous
+                                   run of env groups: lets a test give one wavefront several groups at a few dozen envs */
 } RisVecForce;
 int risvec_force_forms(const RisVecForce *f);
 

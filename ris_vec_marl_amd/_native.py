@@ -151,7 +151,8 @@ class RisVecStepRing(C.Structure):
 
 class RisVecForce(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("struct_bytes", C.c_uint32), ("lat", C.c_int32), ("lat_epw", C.c_int32),
-                ("lat_nt", C.c_int32), ("lat_alt", C.c_int32), ("pipe_nt", C.c_int32), ("colsum_nt", C.c_int32)]
+                ("lat_nt", C.c_int32), ("lat_alt", C.c_int32), ("pipe_nt", C.c_int32), ("colsum_nt", C.c_int32),
+                ("pipe_rev", C.c_int32), ("pipe_waves", C.c_int32)]
 
 
 class RisVecMarlCriticNet(C.Structure):
@@ -174,6 +175,7 @@ _PROTOS = {
     "risvec_last_error": (C.c_char_p, []),
     "risvec_last_kernel": (C.c_char_p, []),
     "risvec_last_theta_by_index": (C.c_int, []),
+    "risvec_last_pipe_walk": (C.c_int, []),
     "risvec_step_kernel": (C.c_char_p, [C.POINTER(RisVecState), C.c_uint32, C.c_int32]),
     "risvec_force_forms": (C.c_int, [C.POINTER(RisVecForce)]),
     "risvec_default_params": (None, [C.POINTER(RisVecParams)]),
@@ -364,6 +366,12 @@ def last_theta_by_index() -> int:
     return int(load().risvec_last_theta_by_index())
 
 
+def last_pipe_walk() -> int:
+    """0 / 1: the calling thread's last software-pipeline launch walked its envs forward / backward
+    (risvec_last_pipe_walk)."""
+    return int(load().risvec_last_pipe_walk())
+
+
 def step_kernel(state, flags: int = 0, form: int = FORM_FUSED):
     """Name of the kernel a step call of this form would launch for `state` (risvec_step_kernel), without launching;
     None when the shape has no such form."""
@@ -374,13 +382,17 @@ def step_kernel(state, flags: int = 0, form: int = FORM_FUSED):
 @contextlib.contextmanager
 def forced(**fields):
     """FOR TESTS AND SAME-BOX A/Bs ONLY: force kernel forms inside the block (risvec_force_forms), the dispatch rules
-    again after it.  lat / lat_nt / lat_alt / pipe_nt / colsum_nt: True forces the form on, False off; lat_epw: 1, 2 or 4."""
+    again after it.  lat / lat_nt / lat_alt / pipe_nt / colsum_nt / pipe_rev: True (or FORCE_ON) forces the form on,
+    False (or FORCE_OFF) off, BY_RULE leaves it to the rules; lat_epw: 1, 2 or 4; pipe_waves: the pipeline's wavefronts."""
     f = RisVecForce(abi_version=ABI_VERSION, struct_bytes=C.sizeof(RisVecForce))
     names = {n for n, _ in RisVecForce._fields_} - {"abi_version", "struct_bytes"}
     for k, v in fields.items():
         if k not in names:
             raise TypeError("forced(): no field %r" % k)
-        setattr(f, k, v if k == "lat_epw" else (FORCE_ON if v else FORCE_OFF))
+        if k in ("lat_epw", "pipe_waves") or (not isinstance(v, bool) and v in (BY_RULE, FORCE_OFF, FORCE_ON)):
+            setattr(f, k, v)
+        else:
+            setattr(f, k, FORCE_ON if v else FORCE_OFF)
     lib = load()
     check(lib.risvec_force_forms(C.byref(f)))
     try:

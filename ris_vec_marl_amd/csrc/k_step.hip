@@ -536,7 +536,13 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
     }
     hipError_t err;
     if (pl.family == StepPlan::LAT) err = launch_step_fused_lat(s, p, a, pl, 1, RisVecTraj{}, st);
-    else if (pl.family == StepPlan::PIPE) err = launch_step_fused_pipe(s, p, a, pl, st);
+    else if (pl.family == StepPlan::PIPE) {
+        // The pipeline with the default cache policy walks the envs forward on even steps and backward on odd ones (the
+        // parity ALT uses): a launch then starts on the lines the launch before read last (EXPERIMENTS.md 2026-10-19).  Same kernel
+        // name, same results; RisVecForce::pipe_rev pins the direction.
+        const bool rev = pl.pol == 0 && forced_or(forced_forms().pipe_rev, (a.counter & 1u) != 0);
+        err = launch_step_fused_pipe(s, p, a, pl, rev, st);
+    }
     else err = with_vp(s.n_veh, [&](auto vp) { return launch_step_vp<vp>(s, p, a, pl, st); });
     note_kernel("%s", pl.name);
     note_theta_by_index(a.theta_k != nullptr);

@@ -105,7 +105,17 @@ __device__ __forceinline__ float4 ld_nt(const float4* p) {
 // without TK never touches A.theta_k / A.theta_k_stride.
 // NT + TK: the h_r rows keep the hint, the index loads use the default policy -- the index tensor is 64 B per env (16.8 MB
 // at 262 144 envs), re-read every step, and fits the cache the hint is there to protect.
-template <int V, int M, int D, class Core, bool NT = false, bool TK = false>
+//
+// REV, the backward walk (the cores whose Args are StepArgs, without NT): the wavefront owns the SAME groups and reads
+// the same bytes, in the mirrored order -- its groups descending, the units of a group UPG-1 ... 0 (last env first, last
+// chunk first), the row loads of a unit in descending address order.  The host alternates the two walks from step to
+// step (launch_step: the step counter's parity), so what a wavefront read LAST in one launch is what it asks for FIRST in
+// the next, while those lines are still close: a launch's tail is served faster to the next launch than the rest of the
+// stream, and block -> XCD does not move between launches (tools/l2_carry_probe.py; EXPERIMENTS.md 2026-10-19, also on
+// what the counters do and do not show about where the lines are found).  Which env a unit belongs to never enters
+// the arithmetic, so the results are the forward walk's bit for bit.  An instantiation, not a flag: every ring slot,
+// unit index and s_img address stays a compile-time constant, and there is no branch on the direction.
+template <int V, int M, int D, class Core, bool NT = false, bool TK = false, bool REV = false>
 __global__ void __launch_bounds__(kBlock)
 k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_groups_total, int per_wave) {
     using In = typename Core::In;
@@ -114,6 +124,8 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
     constexpr int PC = S::PC, CHUNKS = S::CHUNKS, UPG = S::UPG, K = S::K;
     static_assert(!TK || std::is_same<typename Core::Args, StepArgs>::value, "theta by index: StepArgs carries the indices");
     static_assert(D <= UPG && UPG % D == 0, "ring depth must divide the units of a group");
+    static_assert(!REV || (std::is_same<typename Core::Args, StepArgs>::value && !NT), "the backward walk: StepArgs cores, default policy");
+    constexpr int C_FIRST = REV ? CHUNKS - 1 : 0;          // the chunk of an env that is served first: theta rides with it
     __shared__ float s_img[kBlock / kWave][kWave * 2];
     __shared__ float2 s_ph[TK ? kBlock / kWave : 1][16];       // TK: the 8 candidate phasors + the integer 0, per wavefront
 
@@ -160,25 +172,32 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
         if constexpr (TK) {
             // the indices FIRST: loads return in issue order, so the table lookup can run while the unit's h_r rows
             // are still on their way
-            if (c == 0) {
+            if (c == C_FIRST) {
                 const uint8_t* __restrict__ kb = A.theta_k + (long long)e * A.theta_k_stride;
 #pragma unroll
-                for (int it = 0; it < NIT; ++it) u.k[it] = *reinterpret_cast<const uint16_t*>(kb + 2 * pcl[it]);
+                for (int k = 0; k < NIT; ++k) {
+                    const int it = REV ? NIT - 1 - k : k;
+                    u.k[it] = *reinterpret_cast<const uint16_t*>(kb + 2 * pcl[it]);
+                }
             }
         }
+        // (REV: the issue order is mirrored, every destination register is the one the forward walk uses)
 #pragma unroll
-        for (int pc = 0; pc < PC; ++pc) {
+        for (int kp = 0; kp < PC; ++kp) {
+            const int pc = REV ? PC - 1 - kp : kp;
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) {
+            for (int k = 0; k < NIT; ++k) {
+                const int it = REV ? NIT - 1 - k : k;
                 const float4* __restrict__ src = hb + (row_off + (unsigned)pcl[it] + ((c * PC + pc) * VPP * NP));
                 u.h[pc][it] = NT ? ld_nt(src) : *src;
             }
         }
         if constexpr (!TK) {
-            if (c == 0) {
+            if (c == C_FIRST) {
                 const float4* __restrict__ tb = t4 + (long long)e * NP;
 #pragma unroll
-                for (int it = 0; it < NIT; ++it) {
+                for (int k = 0; k < NIT; ++k) {
+                    const int it = REV ? NIT - 1 - k : k;
                     u.t[it] = NT ? ld_nt(tb + pcl[it]) : tb[pcl[it]];
                 }
             }
@@ -202,8 +221,16 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
         RISVEC_ARGS_IN_ONE_TRIP("s"(A.h_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave), "s"(d.E));
     }
     if (grp >= grp_end) return;                            // whole wave: no cross-lane op is skipped
+    // REV: start at the wavefront's last group and come down to its first.  A few scalar adds: a wavefront owns a handful
+    // of groups (2 at the headline shape), and the count is not worth a division in front of the first request.
+    const int grp_first = grp;
+    if constexpr (REV) {
+        while (grp + stride < grp_end) grp += stride;
+    }
+    // the unit served at position `pos` of a group's walk
+    auto unit_at = [](int pos) { return REV ? UPG - 1 - pos : pos; };
 #pragma unroll
-    for (int ui = 0; ui < D; ++ui) load_unit(ring[ui], grp, ui);
+    for (int pos = 0; pos < D; ++pos) load_unit(ring[pos], grp, unit_at(pos));
     if constexpr (TK) {
         theta_table_fill(s_ph[wave], lane);                // once per wavefront, behind the first requests
         __builtin_amdgcn_wave_barrier();                   // the wavefront's own table writes -> its reads
@@ -218,7 +245,8 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
         // The prefetch is unconditional (straight-line code keeps the compiler's vmcnt
         // bookkeeping exact): a wave on its last group "prefetches" group 0 instead, which
         // every such wave shares, so those requests are served by L2 and cost no HBM traffic.
-        const int nxt = (g_cur + stride < grp_end) ? g_cur + stride : 0;
+        const int nxt = REV ? ((g_cur - stride >= grp_first) ? g_cur - stride : 0)
+                            : ((g_cur + stride < grp_end) ? g_cur + stride : 0);
         const int e_mine = g_cur * EPW + lane / VP;
         const bool active = e_mine < d.E;
         // Take the wait for this group's per-lane inputs HERE (they were requested a whole
@@ -228,10 +256,11 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
 
         float2 w0[NIT], w1[NIT];
 #pragma unroll
-        for (int ui = 0; ui < UPG; ++ui) {
-            U& u = ring[ui % D];
+        for (int pos = 0; pos < UPG; ++pos) {
+            U& u = ring[pos % D];
+            const int ui = unit_at(pos);
             const int i = ui / CHUNKS, c = ui % CHUNKS;
-            if (c == 0) {
+            if (c == C_FIRST) {
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
                     float2 t0, t1;
@@ -247,8 +276,10 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
                 }
             }
             float val[8];
+            // (REV: the rows in the order they arrive; each row's sum is its own chain, so the bits do not move)
 #pragma unroll
-            for (int pc = 0; pc < PC; ++pc) {
+            for (int kp = 0; kp < PC; ++kp) {
+                const int pc = REV ? PC - 1 - kp : kp;
                 float2 acc = make_float2(0.f, 0.f);
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
@@ -265,8 +296,8 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
                 s_img[wave][(i * VP + v) * 2 + (j & 1)] = val[0];
             }
             // refill the slot just consumed, D units ahead (crossing into the next group)
-            if (ui + D < UPG) load_unit(u, g_cur, ui + D);
-            else load_unit(u, nxt, ui + D - UPG);
+            if (pos + D < UPG) load_unit(u, g_cur, unit_at(pos + D));
+            else load_unit(u, nxt, unit_at(pos + D - UPG));
         }
         // per-lane inputs of the next group: in flight during this group's core
         in_nx = Core::load(d, A, nxt * EPW + lane / VP, v_mine, nxt * EPW + lane / VP < d.E);
@@ -280,13 +311,15 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
     };
 
     In inA = Core::load(d, A, grp * EPW + lane / VP, v_mine, grp * EPW + lane / VP < d.E), inB;
+    const int step = REV ? -stride : stride;
+    auto done = [&](int g) { return REV ? g < grp_first : g >= grp_end; };
     while (true) {
         do_group(grp, inA, inB);
-        grp += stride;
-        if (grp >= grp_end) break;
+        grp += step;
+        if (done(grp)) break;
         do_group(grp, inB, inA);
-        grp += stride;
-        if (grp >= grp_end) break;
+        grp += step;
+        if (done(grp)) break;
     }
 }
 
@@ -298,26 +331,46 @@ k_step_fused_pipe(Dims d, typename Core::Params P, typename Core::Args A, int n_
 // waves) and buy nothing once ~8 waves/CU already keep >= 16 KiB in flight each.
 constexpr int kPipeWavesPerCu = 8;
 
+// risvec_last_pipe_walk(): the walk of the calling thread's last pipeline launch (0 forward, 1 backward)
+static thread_local int g_pipe_walk = 0;
+
 // NT: non-temporal h_r / theta loads, once the per-step stream no longer fits the 256 MiB Infinity Cache (plan_pipe).
 // Measured (same box, E x 8 x 64, us per step default / nt): 40 960 envs (188 MiB) 32.9 / 39.0, 57 344 (263 MiB)
 // 46.0 / 53.8, 65 536 (288 MiB) 59.4 / 57.8, 262 144 (1.15 GiB) 245-250 / 221-223; 32 768 x 16 x 256 (1.1 GiB) with the
 // BCD sweep 276-284 / 240-252 -- below the cache size the re-read of last step's lines is worth more than the hint,
 // above it the hint is worth 10 %.
+//
+// rev: the backward walk (REV).  The direction is the caller's: launch_step alternates it from step to step.  Built for
+// the cores that step on StepArgs, without NT; every other launch walks forward whatever `rev` says.
+// RisVecForce::pipe_waves (tests): that many wavefronts instead, each with a CONTIGUOUS run of groups (per_wave > 0), so
+// that one wavefront can own several groups at a few dozen envs.
 template <int V, int M, int D, class Core>
 static hipError_t launch_pipe(const RisVecState& s, const typename Core::Params& p, const typename Core::Args& a, bool nt,
-                              hipStream_t st) {
+                              bool rev, hipStream_t st) {
     using S = PipeShape<V, M>;
     const int n_groups = (s.n_envs + S::EPW - 1) / S::EPW;
     const int wpb = kBlock / kWave;
-    long long want_waves = (long long)num_cus() * kPipeWavesPerCu;
+    const int forced_waves = forced_forms().pipe_waves;
+    long long want_waves = forced_waves > 0 ? forced_waves : (long long)num_cus() * kPipeWavesPerCu;
     if (want_waves > n_groups) want_waves = n_groups;
     // balance: every wave gets the same number of groups (the last one possibly fewer)
     const long long per_wave = (n_groups + want_waves - 1) / want_waves;
     want_waves = (n_groups + per_wave - 1) / per_wave;
     const unsigned grid = (unsigned)((want_waves + wpb - 1) / wpb);
-    auto go = [&](auto knl) { hipLaunchKernelGGL(knl, dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, 0); };
-    // the theta source is an instantiation, picked here; the by-index forms exist for the cores that step on StepArgs
+    const int contiguous = forced_waves > 0 ? (int)per_wave : 0;
+    auto go = [&](auto knl) {
+        hipLaunchKernelGGL(knl, dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, n_groups, contiguous);
+    };
+    g_pipe_walk = 0;
+    // the theta source and the walk are instantiations, picked here; the by-index and backward forms exist for the
+    // cores that step on StepArgs
     if constexpr (std::is_same<typename Core::Args, StepArgs>::value) {
+        if (rev && !nt) {
+            if (a.theta_k != nullptr) go(k_step_fused_pipe<V, M, D, Core, false, true, true>);
+            else go(k_step_fused_pipe<V, M, D, Core, false, false, true>);
+            g_pipe_walk = 1;
+            return hipGetLastError();
+        }
         if (a.theta_k != nullptr) {
             if (nt) go(k_step_fused_pipe<V, M, D, Core, true, true>);
             else go(k_step_fused_pipe<V, M, D, Core, false, true>);
@@ -342,25 +395,28 @@ struct RingCores {
 
 // the compile-time shape of the plan (RISVEC_FIXED_SHAPES: one table for every core)
 template <class Cores, class P, class A>
-static hipError_t launch_pipe_shape(const RisVecState& s, const P& p, const A& a, const StepPlan& pl, hipStream_t st) {
+static hipError_t launch_pipe_shape(const RisVecState& s, const P& p, const A& a, const StepPlan& pl, bool rev,
+                                    hipStream_t st) {
 #define RISVEC_X(VV, MM, DD, EMIN, EMAX, T) \
-    if (pl.V == VV && pl.M == MM) return launch_pipe<VV, MM, DD, typename Cores::template at<VV>>(s, p, a, pl.pol == 1, st);
+    if (pl.V == VV && pl.M == MM) return launch_pipe<VV, MM, DD, typename Cores::template at<VV>>(s, p, a, pl.pol == 1, rev, st);
     RISVEC_FIXED_SHAPES(RISVEC_X)
 #undef RISVEC_X
     return hipErrorNotSupported;
 }
 
 hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
-                                  hipStream_t st) {
-    if (pl.ring) return launch_pipe_shape<RingCores>(s, p, a, pl, st);
-    return launch_pipe_shape<AnyV<MarlCore>>(s, p, a, pl, st);
+                                  bool rev, hipStream_t st) {
+    if (pl.ring) return launch_pipe_shape<RingCores>(s, p, a, pl, rev, st);
+    return launch_pipe_shape<AnyV<MarlCore>>(s, p, a, pl, rev, st);
 }
+
+int last_pipe_walk() { return g_pipe_walk; }
 
 template <class Core, class P, class A>
 static hipError_t launch_core(const RisVecState& s, const P& p, const A& a, hipStream_t st) {
     const StepPlan pl = plan_pipe(s, Core::name());
     if (pl.family == StepPlan::NONE) return hipErrorNotSupported;
-    const hipError_t err = launch_pipe_shape<AnyV<Core>>(s, p, a, pl, st);
+    const hipError_t err = launch_pipe_shape<AnyV<Core>>(s, p, a, pl, false, st);
     note_kernel("%s", pl.name);
     return err;
 }

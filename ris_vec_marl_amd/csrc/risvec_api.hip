@@ -211,6 +211,8 @@ const char* risvec_last_kernel(void) { return g_kernel; }
 
 int risvec_last_theta_by_index(void) { return g_theta_by_index; }
 
+int risvec_last_pipe_walk(void) { return risvec::last_pipe_walk(); }
+
 const char* risvec_last_error(void) { return g_err; }
 
 const char* risvec_step_kernel(const RisVecState* s, uint32_t flags, int32_t form) {
@@ -240,11 +242,12 @@ int risvec_force_forms(const RisVecForce* f) {
     if (f->abi_version != RISVEC_ABI_VERSION || f->struct_bytes != sizeof(RisVecForce))
         return fail(RISVEC_ERR_ARG, "%s: RisVecForce ABI mismatch (version %u/%u, bytes %u/%zu)", fn, f->abi_version,
                     (unsigned)RISVEC_ABI_VERSION, f->struct_bytes, sizeof(RisVecForce));
-    for (int32_t v : {f->lat, f->lat_nt, f->lat_alt, f->pipe_nt, f->colsum_nt})
+    for (int32_t v : {f->lat, f->lat_nt, f->lat_alt, f->pipe_nt, f->colsum_nt, f->pipe_rev})
         if (v != RISVEC_BY_RULE && v != RISVEC_FORCE_OFF && v != RISVEC_FORCE_ON)
             return fail(RISVEC_ERR_ARG, "%s: %d is not RISVEC_BY_RULE / RISVEC_FORCE_OFF / RISVEC_FORCE_ON", fn, v);
     if (f->lat_epw != 0 && f->lat_epw != 1 && f->lat_epw != 2 && f->lat_epw != 4)
         return fail(RISVEC_ERR_ARG, "%s: lat_epw=%d is not 0 (by rule), 1, 2 or 4", fn, f->lat_epw);
+    if (f->pipe_waves < 0) return fail(RISVEC_ERR_ARG, "%s: pipe_waves=%d is not 0 (by rule) or a wavefront count", fn, f->pipe_waves);
     g_force = *f;
     return RISVEC_OK;
 }

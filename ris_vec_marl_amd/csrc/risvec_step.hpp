@@ -780,8 +780,11 @@ bool step_fused_lat_covers(int V, int M);
 bool theta_by_index_supported(int V, int M);
 
 // the launchers of the plan's family: k_step_pipe.hip, k_step_lat.hip
+// rev: walk the envs backwards (k_step_fused_pipe<..., REV>; forward where the plan has no such kernel: NT)
 hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
-                                  hipStream_t st);
+                                  bool rev, hipStream_t st);
+// 0 / 1: the walk the calling thread's last software-pipeline launch took (risvec_last_pipe_walk)
+int last_pipe_walk();
 hipError_t launch_gain_pipe(const RisVecState& s, hipStream_t st);
 hipError_t launch_step_fused_lat(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
                                  int n_steps, const RisVecTraj& tj, hipStream_t st);

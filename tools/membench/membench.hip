@@ -124,3 +124,51 @@ extern "C" int membench_read_aux(const void* src, long long n_float4, void* sink
 #undef RA
     return (int)hipGetLastError();
 }
+
+// ---- L2 carry-over probe: do clean L2 lines survive a kernel boundary, and does a walk that alternates its direction
+// from launch to launch find the tail of the previous launch there?  Workgroup b owns chunk b in every launch (so the
+// chunk -> XCD map moves only if the dispatcher's block -> XCD map does); its four wavefronts read the chunk with
+// 16-byte loads, 8 in flight per lane.  REV mirrors the walk exactly: last position first, every load's address
+// descending.  Positions past the end of the chunk re-read its last element (an L1 hit, no branch round a load).
+// Lane 0 records the XCC the workgroup ran on (HW_REG_XCC_ID = hardware register 20, bits 3:0).
+template <bool REV>
+__global__ void __launch_bounds__(256)
+k_read_walk(const float4* __restrict__ src, long long n, float* __restrict__ sink, int* __restrict__ xcc_out) {
+    constexpr int U = 8;
+    const long long per = (n + gridDim.x - 1) / gridDim.x;
+    const long long base = (long long)blockIdx.x * per;
+    long long cnt = n - base < per ? n - base : per;
+    if (threadIdx.x == 0 && xcc_out != nullptr)
+        xcc_out[blockIdx.x] = (int)__builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11));
+    if (cnt <= 0) { sink[(long long)blockIdx.x * 256 + threadIdx.x] = 0.f; return; }
+    const float4* __restrict__ p = src + base;
+    const long long last = cnt - 1;
+    float4 acc[U];
+#pragma unroll
+    for (int k = 0; k < U; ++k) acc[k] = make_float4(0, 0, 0, 0);
+    for (long long q0 = 0; q0 < cnt; q0 += U * 256) {
+        float4 x[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            long long q = q0 + k * 256 + threadIdx.x;          // position in walk order
+            q = q < last ? q : last;
+            x[k] = p[REV ? last - q : q];
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) { acc[k].x += x[k].x; acc[k].y += x[k].y; acc[k].z += x[k].z; acc[k].w += x[k].w; }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < U; ++k) s += acc[k].x + acc[k].y + acc[k].z + acc[k].w;
+    sink[(long long)blockIdx.x * 256 + threadIdx.x] = s;
+}
+
+// sink: blocks * 256 floats; xcc_out: blocks ints, or null
+extern "C" int membench_read_walk(const void* src, long long n_float4, void* sink, int blocks, int reverse, void* xcc_out,
+                                  void* stream) {
+    const float4* s = (const float4*)src; float* k = (float*)sink; int* x = (int*)xcc_out; hipStream_t st = (hipStream_t)stream;
+    if (blocks <= 0 || n_float4 <= 0) return -1;
+    if (reverse) hipLaunchKernelGGL(k_read_walk<true>, dim3(blocks), dim3(256), 0, st, s, n_float4, k, x);
+    else hipLaunchKernelGGL(k_read_walk<false>, dim3(blocks), dim3(256), 0, st, s, n_float4, k, x);
+    return (int)hipGetLastError();
+}
