@@ -1,0 +1,133 @@
+"""The shapes at which the three learner-side MFMA kernels (`k_marl_critic`, `k_sarl_critic`, `k_sarl_actor`) are swept:
+every template instantiation and every edge of their run-time parameters, inside the domain their `*_supported()`
+functions advertise.  Shared by tests/test_mlp_sweep_hip.py (the kernels against float64) and the three
+test_*_host.py files (geometry, stream size, packing and, where fc1 <= 160, the NumPy walk of the stream).  A plain
+module: no fixtures, no test collection.
+
+Each case names the instantiation the library must dispatch to and the edge it is there for.  A case may be swapped for
+another only if every instantiation and every edge below is still hit, with the reason written beside it."""
+from typing import NamedTuple, Tuple
+
+
+class Case(NamedTuple):
+    dims: tuple
+    kernel: str            # what `_native.last_kernel()` must start with after the fused forward
+    edge: str
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# k_marl_critic<MT2,MT3>: dims = (S, A, fc1, fc2, fc3); KS = ceil((S + A) / 16), NG = fc1 / 32, MT2 = fc2 / 128,
+# MT3 = fc3 / 128; kAhead = 4 k-steps of prefetch.
+MARL_CRITIC = (
+    Case((1, 1, 32, 128, 128), "k_marl_critic<1,1>",
+         "KS = 1: nst < kAhead, every fc1 prefetch slot clamped; NG = 1: three wavefronts own no fc1 group and fc2 has "
+         "nks = 2 < kAhead; the state / action boundary at k = 1"),
+    Case((1, 15, 32, 512, 128), "k_marl_critic<4,1>",
+         "S + A = 16 exactly: one full k-step, no padding; s_h sized by fc2, since 2 NG < 8 MT2"),
+    Case((16, 1, 64, 128, 256), "k_marl_critic<1,2>",
+         "S + A = 17: the second k-step holds one value and 15 zeros; the action is its first element"),
+    Case((127, 1, 160, 256, 128), "k_marl_critic<2,1>",
+         "S + A = 128, no zero padding; the boundary at k = 127; NG = 5: wavefront 0 owns two groups, the others one"),
+    Case((1, 127, 1024, 128, 256), "k_marl_critic<1,2>",
+         "NG = 32; s_h sized by fc1; 148 480 bytes of dynamic LDS (the > 64 KiB attribute path)"),
+    Case((33, 46, 992, 512, 128), "k_marl_critic<4,1>",
+         "NG = 31: wavefront 3 owns one group fewer; KS = 5: groups end inside a prefetch round of kAhead"),
+)
+#: (index into MARL_CRITIC, n_nets): every case as a twin, the smallest and the largest as one net too
+MARL_CRITIC_RUNS = tuple((i, 2) for i in range(len(MARL_CRITIC))) + ((0, 1), (4, 1))
+
+# ---------------------------------------------------------------------------------------------------------------------
+# k_sarl_critic<MT2,MT3>: dims = (IN, fc1, fc2, fc3, A); KS = ceil((IN + 1) / 16) (the bias row is input IN),
+# KSA = ceil(A / 16).
+SARL_CRITIC = (
+    Case((15, 32, 128, 128, 1), "k_sarl_critic<1,1>",
+         "IN = 15: the bias row is the last element of a full k-step (KS = 1); NG = 1; A = 1 (KSA = 1, 15 zeros)"),
+    Case((16, 64, 128, 256, 16), "k_sarl_critic<1,2>",
+         "IN = 16: the bias row opens a k-step of its own (KS = 2); A = 16: one full action k-step"),
+    Case((128, 160, 256, 128, 96), "k_sarl_critic<2,1>",
+         "IN = 128: KS = 9; A = 96: KSA = 6; NG = 5"),
+    Case((47, 96, 256, 256, 17), "k_sarl_critic<2,2>",
+         "IN + 1 = 48 fills KS = 3; A = 17: the second action k-step holds one value; NG = 3"),
+    Case((127, 1024, 512, 128, 33), "k_sarl_critic<4,1>",
+         "IN + 1 = 128: KS = 8 full; NG = 32: s_h sized by fc1, dynamic LDS > 64 KiB; A = 33"),
+    Case((5, 992, 128, 256, 96), "k_sarl_critic<1,2>",
+         "KS = 1 with NG = 31; KSA = 6 > kAhead with MT2 = 1"),
+)
+
+# ---------------------------------------------------------------------------------------------------------------------
+# k_sarl_actor<MT,KS>: dims = (IN, fc1, fc2, A); MT = fc2 / 32; KS = ceil((IN + 1) / 16) padded up to the next of
+# {3, 6, 7, 9}; NG = fc1 / 32; p1 = groups per pass-1 item; HT = ceil(A / 32).  `obs` = (V, tn) with V (tn + 5) = IN:
+# the observation shape the inputs are drawn in.
+class ActorCase(NamedTuple):
+    dims: tuple
+    kernel: str
+    edge: str
+    obs: Tuple[int, int]
+
+
+SARL_ACTOR = (
+    ActorCase((5, 32, 128, 1), "k_sarl_actor<4,3>",
+              "two all-zero k-steps; NG = 1: a pass-1 item with one group of p1 = 4 filled, T = 3 items; A = 1", (1, 0)),
+    ActorCase((47, 96, 256, 33), "k_sarl_actor<8,3>",
+              "IN + 1 = 48 fills KS = 3; NG = 3; A = 33: the second head tile holds one action", (1, 42)),
+    ActorCase((48, 160, 128, 32), "k_sarl_actor<4,6>",
+              "ks 4 padded to 6; NG = 5 with p1 = 2: the last pass-1 item half filled; A = 32: one full head tile", (8, 1)),
+    ActorCase((96, 64, 128, 65), "k_sarl_actor<4,7>",
+              "ks 7 exact, 15 zeros behind the bias row; NG = 2; A = 65: the third head tile holds one action", (8, 7)),
+    ActorCase((111, 992, 256, 96), "k_sarl_actor<8,7>",
+              "IN + 1 = 112 fills KS = 7; NG = 31 with p1 = 3: no multiple; A = 96: three full head tiles", (3, 32)),
+    ActorCase((112, 1024, 128, 96), "k_sarl_actor<4,9>",
+              "ks 8 padded to 9: one all-zero k-step; NG = 32", (8, 9)),
+    ActorCase((128, 1024, 256, 96), "k_sarl_actor<8,9>",
+              "IN = 128: the bias row alone in k-step 9; the 156 KiB ring; NG = 32", (8, 11)),
+)
+
+#: rows of the long call: critics 70 = two full 32-row tiles and one of 6 rows; actor 161 = one full 128-row workgroup, a
+#: full wavefront and one row.  Row 0 is all zero; the outputs are PAD rows longer and keep their sentinel beyond n.
+CRITIC_ROWS, ACTOR_ROWS, PAD = 70, 161, 40
+
+
+def seeds(kind: str, index: int) -> Tuple[int, int]:
+    """(weight seed, batch seed) of case `index` of a list: fixed, so that the host check of the headroom (float32
+    against float64 at these very inputs) and the GPU tests see the same numbers.  A twin's second net takes weight
+    seed + 1."""
+    base = {"marl": 1100, "critic": 1300, "actor": 1500}[kind]
+    if (kind, index) in _OTHER_WEIGHT_SEED:
+        return _OTHER_WEIGHT_SEED[kind, index], base + 10 * index + 5
+    return base + 10 * index, base + 10 * index + 5
+
+
+# The actor's error measure divides by the row's largest |logit|, and with ONE action that is the row's only logit: where
+# it crosses zero inside the batch the measure is ill-conditioned for any float32 forward (weight seed 1500: float32
+# against float64 6.3e-6, 1501: 9.2e-5).  At seed 1508 every logit of the batch has magnitude above 1 and the float32
+# forward sits at 2.9e-7, as at the other shapes.  test_mlp_sweep_host.py holds every case to that headroom.
+_OTHER_WEIGHT_SEED = {("actor", 0): 1508}
+
+
+def actor_weights(dims, seed):
+    """A weight set of the actor under the reference's key names, float32 arrays, by the recipe of `driver_actor`
+    (test_sarl_actor_hip.py): the reference's init ranges (networks.py:115-125: 1 / sqrt(fc1), 1 / sqrt(fc2), 0.003), the
+    head weight widened 60 x so that the outputs span (0, 1), LayerNorm weights in [0.5, 1.5] and biases in +-0.2."""
+    import numpy as np
+    IN, F1, F2, A = dims
+    rng = np.random.default_rng(seed)
+    u = lambda r, *s: rng.uniform(-r, r, s).astype(np.float32)     # noqa: E731
+    w = {"fc1.weight": u(F1 ** -0.5, F1, IN), "fc1.bias": u(F1 ** -0.5, F1), "fc2.weight": u(F2 ** -0.5, F2, F1),
+         "fc2.bias": u(F2 ** -0.5, F2), "mu.weight": u(0.003, A, F2) * np.float32(60.0), "mu.bias": u(0.003, A)}
+    for i, f in ((1, F1), (2, F2)):
+        w["bn%d.weight" % i] = rng.uniform(0.5, 1.5, f).astype(np.float32)
+        w["bn%d.bias" % i] = u(0.2, f)
+    return w
+
+
+def case_id(case) -> str:
+    return "x".join(str(d) for d in case.dims)
+
+
+def dims_of(cases) -> list:
+    """The distinct shapes of a case list, in order."""
+    seen = []
+    for c in cases:
+        if c.dims not in seen:
+            seen.append(c.dims)
+    return seen

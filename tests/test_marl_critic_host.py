@@ -15,10 +15,13 @@ import torch
 from ris_vec_marl_amd import _native as N
 from ris_vec_marl_amd import marl_critic as MC
 from tests import marl_critic_ref as R
+from tests import mlp_sweep_shapes as SW
 
-# (S, A, fc1, fc2, fc3): the driver's two, the fixtures' two, the corners of the rule
+# (S, A, fc1, fc2, fc3): the driver's two, the fixtures' two, the corners of the rule, then the shapes of the GPU sweep
+# (every instantiation and edge of the kernel; test_mlp_sweep_hip.py)
 SHAPES = [(20, 24, 1024, 512, 256), (40, 80, 1024, 512, 256), (40, 80, 64, 128, 128), (20, 24, 64, 128, 128),
           (127, 1, 1024, 512, 256), (1, 127, 32, 128, 128), (1, 1, 32, 128, 256), (33, 46, 160, 256, 128)]
+SHAPES += [d for d in SW.dims_of(SW.MARL_CRITIC) if d not in SHAPES]
 SMALL = [s for s in SHAPES if s[2] <= 160]
 
 

@@ -9,8 +9,11 @@ import torch
 
 from ris_vec_marl_amd import _native as N
 from ris_vec_marl_amd import actor as ACT
+from tests import mlp_sweep_shapes as SW
 
+# then the shapes of the GPU sweep (every instantiation and edge of the kernel; test_mlp_sweep_hip.py)
 SHAPES = [(80, 512, 256, 56), (104, 512, 256, 80), (36, 64, 128, 24), (128, 1024, 256, 96), (5, 32, 128, 1), (79, 96, 128, 33)]
+SHAPES += [d for d in SW.dims_of(SW.SARL_ACTOR) if d not in SHAPES]
 
 
 @pytest.mark.parametrize("dims,ok", [((80, 512, 256, 56), 1), ((104, 512, 256, 80), 1), ((36, 64, 128, 24), 1),

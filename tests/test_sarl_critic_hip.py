@@ -325,8 +325,13 @@ def test_dispatch_and_argument_checks():
     critic.forward(x, a)
     assert N.last_kernel().startswith("k_sarl_critic<4,2>")
     small = make_critic((36, 64, 128, 128, 24), gemm="fused")
-    small.forward(*batch((36, 64, 128, 128, 24), 40, 24))
+    xs, as_ = batch((36, 64, 128, 128, 24), 40, 24)
+    q_small = small.forward(xs, as_)
     assert N.last_kernel().startswith("k_sarl_critic<1,1>")
+    small_sd = {k: v.numpy() for k, v in small.state_dict().items()}
+    small_err = R.err(q_small.cpu().numpy(), R.critic_q64(small_sd, xs.cpu().numpy(), as_.cpu().numpy()))
+    print("(36, 64, 128, 128, 24) fused <1,1>: err %.3g" % small_err)
+    assert small_err < R.BAR
     reward, done = torch.zeros(40, device=DEV), torch.zeros(40, dtype=torch.bool, device=DEV)
     x3 = x.reshape(40, 8, 10)
     assert torch.equal(critic.forward(x3, a), critic.forward(x, a))      # [n, V, input_dims / V] in place

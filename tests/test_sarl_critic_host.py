@@ -13,11 +13,14 @@ import torch
 
 from ris_vec_marl_amd import _native as N
 from ris_vec_marl_amd import critic as CR
+from tests import mlp_sweep_shapes as SW
 from tests import sarl_critic_ref as R
 
-# (in, fc1, fc2, fc3, n_actions): the driver's two, the fixtures' two, the corners of the rule
+# (in, fc1, fc2, fc3, n_actions): the driver's two, the fixtures' two, the corners of the rule, then the shapes of the GPU
+# sweep (every instantiation and edge of the kernel; test_mlp_sweep_hip.py)
 SHAPES = [(80, 1024, 512, 256, 56), (104, 1024, 512, 256, 80), (80, 96, 128, 128, 56), (36, 64, 128, 128, 24),
           (128, 1024, 512, 256, 96), (5, 32, 128, 128, 1), (79, 160, 256, 128, 33)]
+SHAPES += [d for d in SW.dims_of(SW.SARL_CRITIC) if d not in SHAPES]
 SMALL = [s for s in SHAPES if s[1] <= 160]
 
 
