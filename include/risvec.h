@@ -695,6 +695,25 @@ int risvec_policy_sample(int32_t n_envs, int32_t n_veh, int64_t env_offset, cons
                          uint32_t counter, float cpu_share_floor, float *power_raw, float *probs, float *onehot,
                          float *action_env, float *p_off01, float *action_store, risvec_stream_t stream);
 
+/* The learner's policy.sample_normal(obs_j, mask=mask_j) (sac_agent.py:80-127) for every sampled row and agent, with
+ * what global_learn does with it (global_sac_critic.py:326-336), in one launch.  heads [V, B, 4+V], mask [B,V,V] or
+ * NULL, tau [V], hard [V] or NULL, eps [B,V,2] / expo [B,V,V] (NULL: Philox keyed by row_offset + b, the sites, block
+ * -> value mapping and 2^-24 floor of risvec_policy_sample) as for risvec_policy_sample, and for the same heads and
+ * draws power / probs / the arg-max are that entry point's power_raw / probs / onehot bit for bit.
+ * Outputs, each optional (NULL: not written; at least one must be given):
+ *   power [B,V,2], probs [B,V,V] (y, soft or straight-through per hard[v]),
+ *   next_actions [B, V*(V+2)]  per agent [onehot(argmax y) (V), power (2)]: the target critics' action input,
+ *   logp_power [B,V]   = sum_i ( -eps_i^2/2 - log_std_i - log(2 pi)/2 - log(1 - p_i^2 + 1e-6) ), from the draw eps
+ *                        itself (equal to the reference's (x_t - mu)^2 / (2 var) form without its cancellation),
+ *   logp_intent [B,V]  = sum_k y_k lsm_k, or lsm[argmax y] where hard[v]; lsm = log_softmax(masked logits),
+ *   logp_power_sum [B], logp_intent_sum [B]: the float32 sums over the agents in agent order 0..V-1 (no atomics);
+ *                        n_veh <= 16 only -- with more agents a non-NULL sum pointer is RISVEC_ERR_ARG.
+ * n_rows == 0 returns RISVEC_OK without a launch; every other invalid argument is RISVEC_ERR_ARG. */
+int risvec_policy_sample_normal(int32_t n_rows, int32_t n_veh, int64_t row_offset, const float *heads, const uint8_t *mask,
+                                const float *tau, const uint8_t *hard, const float *eps, const float *expo, uint64_t seed,
+                                uint32_t counter, float *power, float *probs, float *next_actions, float *logp_power,
+                                float *logp_intent, float *logp_power_sum, float *logp_intent_sum, risvec_stream_t stream);
+
 /* The two non-GEMM ends of PolicyNetwork.forward (sac_agent.py:62-78), all agents and envs per launch;
  * the fc1 x fc2 product in between is a plain batched GEMM (rocBLAS).  Row-major float32 everywhere.
  *   layer1: obs [E,V,in] , W1 [V,in,F1] (= fc1.weight^T), b1 / ln_w / ln_b [V,F1]

@@ -259,6 +259,8 @@ _PROTOS = {
     "risvec_policy_heads": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "risvec_policy_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64, C.c_uint32,
                                        C.c_float, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "risvec_policy_sample_normal": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64,
+                                              C.c_uint32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "risvec_episode_clear": (C.c_int, [C.c_int32, C.c_int32, _FP, _FP]),
     "risvec_episode_accumulate": (C.c_int, [C.c_int32, C.c_int32, _FP, _FP, _FP, C.c_float, _FP, _FP]),
     "risvec_episode_partial_rows": (C.c_int32, [C.c_int32]),

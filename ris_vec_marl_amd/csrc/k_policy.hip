@@ -8,15 +8,11 @@
 //   one-hot of choose_action (SAC:215-216), and -- optionally -- the env action, pairing power and replay
 //   action row of TRAIN:1386-1396, 1601-1608, 1776-1784 (what k_marshal_* would do in a second launch).
 // Draws are injected (parity) or Philox.  pow2ceil(V) lanes per (env, agent) row; V <= 64.
-#include <cfloat>
-
 #include "risvec_launch.hpp"
-#include "risvec_step.hpp"      // DPP exchanges (xchg / gsum)
+#include "risvec_policy_row.hpp"  // the row math shared with k_policy_learn.hip
 
 namespace risvec {
 namespace {
-
-constexpr uint32_t kSitePolicyEps = 9, kSitePolicyGumbel = 10;
 
 struct PolicyArgs {
     int E, V;
@@ -56,41 +52,9 @@ k_policy_sample(PolicyArgs A) {
     const float* h = A.heads + ((long long)v * A.E + e) * H;
     const uint32_t genv = (uint32_t)(A.env_offset + e);
     // ---- discrete head: masked logits, Gumbel-softmax  (SAC:91-113) --------------------------------------
-    const bool open_k = k < V && (!A.mask || A.mask[gid * V + k] != 0);
-    const bool any_open = gsum<VP>(A.mask && open_k ? 1.0f : 0.0f) > 0.0f;
-    const bool blocked = A.mask && any_open && !open_k;        // an all-zero row is opened up (SAC:97-100)
-    float z = -INFINITY;
-    if (k < V) {
-        float ex;
-        if (A.expo) ex = A.expo[gid * V + k];
-        else {
-            const uint4 r = philox4x32_10(genv, (uint32_t)v, A.counter, kSitePolicyGumbel + 0x100u * (k >> 2), A.seed);
-            const uint32_t x = (k & 3) == 0 ? r.x : (k & 3) == 1 ? r.y : (k & 3) == 2 ? r.z : r.w;
-            // Exp(1), u in (0, 1].  u == 1 would be 0, its Gumbel +inf and the row inf - inf: as torch's device
-            // exponential_() does (what F.gumbel_softmax draws with, SAC:110-113), that one draw is 2^-24 instead
-            const uint32_t m = x >> 8;
-            ex = m == 0xFFFFFFu ? 0x1p-24f : -logf(((float)m + 1.0f) * 0x1p-24f);
-        }
-        const float ml = blocked ? -FLT_MAX / 2.0f : h[4 + k];        // torch.finfo(float32).min / 2  (SAC:103)
-        z = (ml + -logf(ex)) / A.tau[v];                              // (logits + gumbel) / tau
-    }
-    float zmax = z;
-    int arg = k < V ? k : 0x7fffffff;
-#pragma unroll
-    for (int o = 1; o < VP; o <<= 1) {                                // arg-max, first index on ties
-        float oz; int oa;
-        if (o == 1) { oz = xchg<1>(zmax); oa = __builtin_bit_cast(int, xchg<1>(__builtin_bit_cast(float, arg))); }
-        else if (o == 2) { oz = xchg<2>(zmax); oa = __builtin_bit_cast(int, xchg<2>(__builtin_bit_cast(float, arg))); }
-        else if (o == 4) { oz = xchg<4>(zmax); oa = __builtin_bit_cast(int, xchg<4>(__builtin_bit_cast(float, arg))); }
-        else if (o == 8) { oz = xchg<8>(zmax); oa = __builtin_bit_cast(int, xchg<8>(__builtin_bit_cast(float, arg))); }
-        else if (o == 16) { oz = xchg<16>(zmax); oa = __builtin_bit_cast(int, xchg<16>(__builtin_bit_cast(float, arg))); }
-        else { oz = xchg<32>(zmax); oa = __builtin_bit_cast(int, xchg<32>(__builtin_bit_cast(float, arg))); }
-        if (oz > zmax || (oz == zmax && oa < arg)) { zmax = oz; arg = oa; }
-    }
-    const float ez = k < V ? expf(z - zmax) : 0.0f;
-    const float sum = gsum<VP>(ez);
-    float pk = ez / sum;
-    if (A.hard && A.hard[v]) pk = ((k == arg ? 1.0f : 0.0f) - pk) + pk;   // y_hard - y_soft + y_soft (SAC:110-113)
+    const PolicyIntent I = policy_row_intent<VP>(h, A.mask, A.expo, A.tau, A.hard, gid, V, v, k, genv, A.counter, A.seed);
+    const float pk = I.pk;
+    const int arg = I.arg;
     if (mine) {
         A.probs[gid * V + k] = pk;
         if (A.onehot) A.onehot[gid * V + k] = k == arg ? 1.0f : 0.0f;     // choose_action, SAC:215-216
@@ -98,15 +62,8 @@ k_policy_sample(PolicyArgs A) {
     }
     // ---- continuous head + marshalling, lane 0 of the row  (SAC:72, 83-86; TRAIN:1391-1396, 1601-1608) ---
     if (live_row && k == 0) {
-        float e0, e1;
-        if (A.eps) { e0 = A.eps[gid * 2]; e1 = A.eps[gid * 2 + 1]; }
-        else {
-            const uint4 r = philox4x32_10(genv, (uint32_t)v, A.counter, kSitePolicyEps, A.seed);
-            const float2 n = normal2(r.x, r.y);
-            e0 = n.x; e1 = n.y;
-        }
-        const float ls0 = fminf(fmaxf(h[2], -20.0f), 2.0f), ls1 = fminf(fmaxf(h[3], -20.0f), 2.0f);
-        const float p0 = tanhf(e0 * expf(ls0) + h[0]), p1 = tanhf(e1 * expf(ls1) + h[1]);
+        const PolicyPower P = policy_row_power(h, A.eps, gid, v, genv, A.counter, A.seed);
+        const float p0 = P.p0, p1 = P.p1;
         A.power_raw[gid * 2] = p0;
         A.power_raw[gid * 2 + 1] = p1;
         if (A.action_store) {

@@ -896,6 +896,32 @@ int risvec_policy_sample(int32_t n_envs, int32_t n_veh, int64_t env_offset, cons
                                                    (hipStream_t)stream));
 }
 
+int risvec_policy_sample_normal(int32_t n_rows, int32_t n_veh, int64_t row_offset, const float* heads, const uint8_t* mask,
+                                const float* tau, const uint8_t* hard, const float* eps, const float* expo, uint64_t seed,
+                                uint32_t counter, float* power, float* probs, float* next_actions, float* logp_power,
+                                float* logp_intent, float* logp_power_sum, float* logp_intent_sum, risvec_stream_t stream) {
+    const char* fn = "risvec_policy_sample_normal";
+    if (n_rows == 0) return RISVEC_OK;                       // an empty batch: nothing to launch
+    if (n_rows < 0) return fail(RISVEC_ERR_ARG, "%s: n_rows=%d must be >= 0", fn, n_rows);
+    if (n_veh < 1 || n_veh > RISVEC_MAX_VEH)
+        return fail(RISVEC_ERR_ARG, "%s: n_veh=%d outside [1,%d]", fn, n_veh, RISVEC_MAX_VEH);
+    if (row_offset < 0 || row_offset + n_rows > 0xFFFFFFFFLL)
+        return fail(RISVEC_ERR_ARG, "%s: row_offset+n_rows must fit 32 bits", fn);
+    REQ_PTR(heads, "heads"); REQ_PTR(tau, "tau");
+    OPT_PTR(mask, "mask"); OPT_PTR(eps, "eps"); OPT_PTR(expo, "expo");
+    OPT_PTR(power, "power"); OPT_PTR(probs, "probs"); OPT_PTR(next_actions, "next_actions");
+    OPT_PTR(logp_power, "logp_power"); OPT_PTR(logp_intent, "logp_intent");
+    OPT_PTR(logp_power_sum, "logp_power_sum"); OPT_PTR(logp_intent_sum, "logp_intent_sum");
+    if (!power && !probs && !next_actions && !logp_power && !logp_intent && !logp_power_sum && !logp_intent_sum)
+        return fail(RISVEC_ERR_ARG, "%s: no output given", fn);
+    if ((logp_power_sum || logp_intent_sum) && risvec::policy_sample_normal_rows_per_block(n_veh) < 1)
+        return fail(RISVEC_ERR_ARG, "%s: the sums over the agents are built for n_veh <= 16 (got %d): add the per-agent "
+                    "outputs instead", fn, n_veh);
+    return finish(fn, risvec::launch_policy_sample_normal(n_rows, n_veh, row_offset, heads, mask, tau, hard, eps, expo, seed,
+                                                          counter, power, probs, next_actions, logp_power, logp_intent,
+                                                          logp_power_sum, logp_intent_sum, (hipStream_t)stream));
+}
+
 int risvec_policy_layer1(int32_t n_envs, int32_t n_veh, int32_t in_dims, int32_t f1, const float* obs, const float* W1,
                          const float* b1, const float* ln_w, const float* ln_b, float* out, risvec_stream_t stream) {
     const char* fn = "risvec_policy_layer1";

@@ -69,6 +69,15 @@ hipError_t launch_policy_sample(int E, int V, long long env_offset, const float*
                                 uint32_t counter, float floor_eff, float* power_raw, float* probs, float* onehot,
                                 float* action_env, float* p_off01, float* action_store, hipStream_t st);
 
+// sample_normal of every (row, agent) with the learner's next_actions and log-prob sums (k_policy_learn.hip).
+// policy_sample_normal_rows_per_block(): batch rows one workgroup owns (0 for V > 16: no sums).
+int policy_sample_normal_rows_per_block(int V);
+hipError_t launch_policy_sample_normal(int B, int V, long long row_offset, const float* heads, const uint8_t* mask,
+                                       const float* tau, const uint8_t* hard, const float* eps, const float* expo,
+                                       uint64_t seed, uint32_t counter, float* power, float* probs, float* next_actions,
+                                       float* logp_power, float* logp_intent, float* logp_power_sum, float* logp_intent_sum,
+                                       hipStream_t st);
+
 hipError_t launch_policy_layer1(int E, int V, int IN, int F, const float* obs, const float* W1, const float* b1,
                                 const float* lw, const float* lb, float* out, hipStream_t st);
 hipError_t launch_policy_layer1_split16(int E, int V, int IN, int F, const float* obs, const float* W1, const float* b1,

@@ -8,6 +8,10 @@ three small GEMMs of `forward` (5 -> fc1 -> fc2 -> {mu, log_std, intent_logits})
 (rocBLAS: plain library GEMMs); everything after them -- clamp, Normal sample + tanh, logits mask,
 Gumbel-softmax, arg-max one-hot AND the marshalling of TRAIN:1386-1396, 1601-1608, 1776-1784 -- is one
 hand-written HIP launch (`risvec_policy_sample`, csrc/k_policy.hip).  No CPU path.
+
+`sample_normal` is the learner's side of the same networks (`global_sac_critic.py:296-336`): per agent
+`policy.sample_normal` with its log-probabilities, the target critics' `next_actions` row and the log-probability sums
+over the agents, one launch after the forward (`risvec_policy_sample_normal`, csrc/k_policy_learn.hip).
 """
 from __future__ import annotations
 
@@ -245,8 +249,91 @@ class BatchedPolicy:
         out = (power, probs, onehot)
         return out + (a_env, p01, a_store) if marsh else out
 
+    # ------------------------------------------------------------------ learner
+    SUMS_MAX_AGENTS = 16          # `risvec_policy_sample_normal` adds over the agents for V <= 16 (V pow2ceil(V) <= 256)
+
+    def sample_normal(self, obs: torch.Tensor, mask: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                      expo: Optional[torch.Tensor] = None, *, sums: bool = True,
+                      out: Optional[Sequence[Optional[torch.Tensor]]] = None) -> Tuple[Optional[torch.Tensor], ...]:
+        """`agents[j].policy.sample_normal(obs_j, mask=mask_j)` (SAC:80-127) for every row and agent, with what the
+        learner's target does with the results (`global_sac_critic.py:326-336`): the forward (`forward_heads`, one MFMA
+        launch where gemm == "fused") and ONE hand-written launch (`risvec_policy_sample_normal`, csrc/k_policy_learn.hip).
+        obs [B,V,input_dims]; mask [B,V,V] or None; `eps` [B,V,2] / `expo` [B,V,V] inject the draws (default Philox, the
+        call counter advancing as in `choose_action`).  Returns
+            (power [B,V,2], probs [B,V,V], logp_power [B,V], logp_intent [B,V], next_actions [B,V*(V+2)],
+             logp_power_sum [B] or None, logp_intent_sum [B] or None)
+        next_actions holds per agent [onehot(argmax probs) (V), power (2)]; the sums (`sums=True`) are the float32 sums
+        over the agents in agent order -- the `action_`, `logp_power`, `logp_intent` of `BatchedTwinCritic.td_target`.
+        With more than 16 agents the launch leaves the sums out and they are `logp_*.sum(1)`.
+        `out` = (next_actions, logp_power_sum, logp_intent_sum): caller-owned contiguous float32 tensors written in
+        place (an entry may be None: a new tensor; the sums must be None when `sums` is False)."""
+        B, V = int(obs.shape[0]), self.n_agents
+        if tuple(obs.shape) != (B, V, self.input_dims):
+            raise ValueError("obs must have shape [B, %d, %d]" % (V, self.input_dims))
+        dev = self.device
+        na = sp = si = None
+        if out is not None:
+            if len(out) != 3:
+                raise ValueError("sample_normal: out = (next_actions, logp_power_sum, logp_intent_sum)")
+            na = N.in_place(out[0], torch.float32, (B, V * (V + 2)), "sample_normal: out next_actions", dev)
+            sp = N.in_place(out[1], torch.float32, (B,), "sample_normal: out logp_power_sum", dev)
+            si = N.in_place(out[2], torch.float32, (B,), "sample_normal: out logp_intent_sum", dev)
+            if not sums and (sp is not None or si is not None):
+                raise ValueError("sample_normal: out holds a sum tensor but sums=False")
+        heads = self.forward_heads(obs)
+        mk = None if mask is None else N.mask_u8(mask.to(dev)).reshape(B, V, V).contiguous()
+        ep = None if eps is None else eps.to(dev, torch.float32).reshape(B, V, 2).contiguous()
+        ex = None if expo is None else expo.to(dev, torch.float32).reshape(B, V, V).contiguous()
+        power = torch.empty(B, V, 2, device=dev)
+        probs = torch.empty(B, V, V, device=dev)
+        lpp = torch.empty(B, V, device=dev)
+        lpi = torch.empty(B, V, device=dev)
+        if na is None:
+            na = torch.empty(B, V * (V + 2), device=dev)
+        if sums:
+            sp = torch.empty(B, device=dev) if sp is None else sp
+            si = torch.empty(B, device=dev) if si is None else si
+        in_launch = sums and V <= self.SUMS_MAX_AGENTS
+        self._calls += 1
+        N.check(N.load().risvec_policy_sample_normal(
+            B, V, self.env_offset, heads.data_ptr(), N.ptr(mk), self.tau.data_ptr(), self.gumbel_hard.data_ptr(), N.ptr(ep),
+            N.ptr(ex), self.seed, self._calls, power.data_ptr(), probs.data_ptr(), na.data_ptr(), lpp.data_ptr(),
+            lpi.data_ptr(), N.ptr(sp) if in_launch else None, N.ptr(si) if in_launch else None, N.stream(dev)))
+        if sums and not in_launch:
+            torch.sum(lpp, 1, out=sp)
+            torch.sum(lpi, 1, out=si)
+        return power, probs, lpp, lpi, na, sp, si
+
+    def sample_normal_torch(self, obs: torch.Tensor, mask: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None,
+                            expo: Optional[torch.Tensor] = None, *, sums: bool = True) -> Tuple[Optional[torch.Tensor], ...]:
+        """What `sample_normal` returns, with library kernels only after the same `forward_heads`: the timing baseline
+        of the hand-written launch and a second opinion in its tests.  Draws not given come from torch's generator (not
+        the Philox streams), and the call counter stays where it is."""
+        B, V = int(obs.shape[0]), self.n_agents
+        dev = self.device
+        h = self.forward_heads(obs).transpose(0, 1)                                        # [B, V, 4 + V]
+        mu, ls, logits = h[..., 0:2], h[..., 2:4].clamp(-20.0, 2.0), h[..., 4:]
+        e = torch.randn(B, V, 2, device=dev) if eps is None else eps.to(dev, torch.float32).reshape(B, V, 2)
+        x = torch.empty(B, V, V, device=dev).exponential_() if expo is None else expo.to(dev, torch.float32).reshape(B, V, V)
+        power = torch.tanh(torch.addcmul(mu, e, ls.exp()))
+        logp_power = (-0.5 * e * e - ls - 0.5 * math.log(2.0 * math.pi) - torch.log(1.0 - power * power + 1e-6)).sum(-1)
+        if mask is not None:
+            allowed = mask.to(dev).reshape(B, V, V) != 0
+            allowed = allowed | ~allowed.any(-1, keepdim=True)                            # an all-zero row is opened up
+            logits = logits.masked_fill(~allowed, torch.finfo(torch.float32).min / 2)
+        soft = torch.softmax((logits - x.log()) / self.tau.view(1, V, 1), -1)            # Gumbel = -log(Exp(1))
+        idx = soft.argmax(-1, keepdim=True)
+        onehot = torch.zeros_like(soft).scatter_(-1, idx, 1.0)
+        hard = self.gumbel_hard.bool().view(1, V, 1)
+        probs = torch.where(hard, (onehot - soft) + soft, soft)
+        lsm = torch.log_softmax(logits, -1)
+        logp_intent = torch.where(hard[..., 0], lsm.gather(-1, idx)[..., 0], (probs * lsm).sum(-1))
+        next_actions = torch.cat([onehot, power], -1).reshape(B, V * (V + 2))
+        sp, si = (logp_power.sum(1), logp_intent.sum(1)) if sums else (None, None)
+        return power.contiguous(), probs, logp_power, logp_intent, next_actions, sp, si
+
     # ------------------------------------------------------------------ checkpoint
-    _KEYS = ("W1", "b1", "W2", "b2", "Wh", "bh", "ln1_w", "ln1_b", "ln2_w", "ln2_b", "tau", "gumbel_hard")
+    _KEYS =("W1", "b1", "W2", "b2", "Wh", "bh", "ln1_w", "ln1_b", "ln2_w", "ln2_b", "tau", "gumbel_hard")
 
     def state_dict(self) -> dict:
         return {k: getattr(self, k).detach().cpu().clone() for k in self._KEYS}
