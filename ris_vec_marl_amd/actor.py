@@ -10,13 +10,13 @@ launches, actor and everything else.  No CPU compute path.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
-from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
+from typing import Mapping, NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _native as N
+from ._wstream import _split_scaled, centre_fc1, polyak_pairs, polyak_tau, soft_update_tensors
 
 _KS_BUILT = (3, 6, 7, 9)          # fc1 k-steps of 16 the kernel is instantiated for (csrc/k_sarl_actor.hip)
 
@@ -49,23 +49,6 @@ def _supported(input_dims: int, fc1_dims: int, fc2_dims: int, n_actions: int) ->
     tests compare the two)."""
     return (1 <= input_dims <= 128 and fc1_dims >= 32 and fc1_dims % 32 == 0 and fc1_dims <= 1024 and fc2_dims in (128, 256)
             and 1 <= n_actions <= 96)
-
-
-def centre_fc1(W1: torch.Tensor, b1: torch.Tensor) -> torch.Tensor:
-    """[input_dims + 1, fc1] float64: the fc1 weight (as [in, out]) with the bias as one more input row, every row
-    centred over the feature axis -- the pre-activation it produces has mean 0 over the features for any input."""
-    wb = torch.cat([W1.double().T, b1.double()[None, :]], 0)
-    return wb - wb.mean(-1, keepdim=True)
-
-
-def _split_scaled(w: torch.Tensor, target: float = 64.0):
-    """(hi, lo, 2^-s): w 2^s with its largest entry in [target, 2 target), split into float16 hi + lo (the scaling keeps lo
-    in the float16 normal range; powers of two cancel exactly)."""
-    amax = w.abs().amax().clamp_min(1e-30)
-    shift = torch.floor(torch.log2(target / amax)).clamp(-40, 40)
-    ws = (w.double() * torch.exp2(shift)).float()
-    hi = ws.to(torch.float16)
-    return hi, (ws - hi.float()).to(torch.float16), torch.exp2(-shift).float()
 
 
 def pack_actor_weights(W1, b1, ln1_w, ln1_b, W2, Wmu) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -175,54 +158,6 @@ def unpack_actor_weights(stream: torch.Tensor, scales: torch.Tensor, input_dims:
     ln = s.view(torch.float32).view(g.items, g.rows, 256)[g.t1:g.t1 + NG, 2 * KS]
     return {"fc1": fc1_of(p2[:, :2 * KS]), "fc1_pass1": fc1_of(p1), "fc2": w2, "mu": wm[:, :n_actions].contiguous(),
             "ln1_w": ln[:, :32].reshape(-1).double(), "ln1_b": ln[:, 32:64].reshape(-1).double()}
-
-
-def polyak_pairs(target, online, what: str):
-    """[(online tensor, target tensor)] in the order of `target._WEIGHTS` for `target.soft_update_from(online, tau)`:
-    `online` is an object of `target`'s class and shape or a mapping under the reference's key names.  Refuses what
-    `share_state_dict` refuses (KeyError for a missing key, ValueError for a tensor that is not contiguous float32 of
-    the right shape on the target's device) before anything is touched."""
-    names = {a: k for k, a in target._SD.items()}
-    if isinstance(online, Mapping):
-        for k in target._SD:
-            if k not in online:
-                raise KeyError("%s: %r is missing" % (what, k))
-        src = {a: online[names[a]] for a in target._WEIGHTS}
-    elif isinstance(online, type(target)):
-        src = {a: getattr(online, a) for a in target._WEIGHTS}
-    else:
-        raise ValueError("%s: online must be a %s of the same shape or a mapping of its weights under the reference's key names"
-                         % (what, type(target).__name__))
-    pairs = []
-    for a in target._WEIGHTS:
-        t, mine = src[a], getattr(target, a)
-        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != target.device
-                or not t.is_contiguous() or tuple(t.shape) != tuple(mine.shape)):
-            raise ValueError("%s: %s must be a contiguous float32 tensor of shape %s on %s (it is read in place)"
-                             % (what, names[a], tuple(mine.shape), target.device))
-        if t.data_ptr() == mine.data_ptr():
-            raise ValueError("%s: %s is the target's own tensor" % (what, names[a]))
-        pairs.append((t, mine))
-    return pairs
-
-
-def polyak_tau(tau, what: str) -> float:
-    tau = float(tau)
-    if not math.isfinite(tau) or not 0.0 <= tau <= 1.0:
-        raise ValueError("%s: tau must be finite and in [0, 1]" % what)
-    return tau
-
-
-def soft_update_tensors(pairs: Sequence[Tuple[torch.Tensor, torch.Tensor]], tau: float, device) -> None:
-    """target = tau * online + (1 - tau) * target for up to 32 (online, target) pairs of contiguous float32 device tensors in
-    ONE launch on the current stream (`risvec_soft_update`, csrc/k_soft_update.hip), in place, with the bits of that
-    expression on float32 tensors (`ddpg_torch.py:122-127`).  The targets' version counters are not advanced."""
-    N.require_hip(device)
-    n = len(pairs)
-    on = (C.c_void_p * n)(*(o.data_ptr() for o, _ in pairs))
-    tg = (C.c_void_p * n)(*(t.data_ptr() for _, t in pairs))
-    ne = (C.c_int64 * n)(*(t.numel() for _, t in pairs))
-    N.check(N.load().risvec_soft_update(n, on, tg, ne, tau, 1.0 - tau, N.stream(device)))
 
 
 class BatchedActor:

@@ -19,10 +19,8 @@ from typing import Mapping, NamedTuple, Optional, Tuple
 import torch
 
 from . import _native as N
-from .actor import _split_scaled, centre_fc1, polyak_pairs, polyak_tau, soft_update_tensors
-
-_WAVES = 4                        # wavefronts of a workgroup: each owns a quarter of every layer's output features
-
+from ._wstream import (_WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags, centre_fc1, polyak_pairs, polyak_tau,
+                       soft_update_tensors)
 
 class CriticGeom(NamedTuple):
     """Layout of the weight stream of `risvec_sarl_critic` (include/risvec.h): fragment rows of 1 KiB in four blocks that
@@ -55,39 +53,6 @@ def _supported(input_dims: int, fc1_dims: int, fc2_dims: int, fc3_dims: int, n_a
     tests compare the two)."""
     return (1 <= input_dims <= 128 and fc1_dims >= 32 and fc1_dims % 32 == 0 and fc1_dims <= 1024
             and fc2_dims in (128, 256, 512) and fc3_dims in (128, 256) and 1 <= n_actions <= 96)
-
-
-# A fragments [tiles, k-steps, 2 (hi | lo), 64 lanes, 8] of X [K, N] (input-major), N = 32 tiles; lane = 32 h + r holds
-# output feature 32 tile + r.  "nat": k = 16 s + 8 h + j (the operand comes from memory); "cd": k = 16 s + 8 (j >> 2) +
-# 4 h + (j & 3) (the operand is the previous MFMA's accumulator, registers 8u .. 8u+7 = k-step u).
-def _frags(hi: torch.Tensor, lo: torch.Tensor, order: str) -> torch.Tensor:
-    K, Nn = hi.shape
-    s = torch.stack([hi, lo], 0)
-    if order == "nat":                                                # (t, s, h, j, tile, r) -> (tile, s, t, h, r, j)
-        return s.reshape(2, K // 16, 2, 8, Nn // 32, 32).permute(4, 1, 0, 2, 5, 3).reshape(Nn // 32, K // 16, 2, 64, 8)
-    # (t, s, jh, h, jl, tile, r) -> (tile, s, t, h, r, jh, jl)
-    return s.reshape(2, K // 16, 2, 2, 4, Nn // 32, 32).permute(5, 1, 0, 3, 6, 2, 4).reshape(Nn // 32, K // 16, 2, 64, 8)
-
-
-def _unfrags(f: torch.Tensor, order: str) -> torch.Tensor:
-    """hi + lo of `_frags` back as float64 X [K, N]."""
-    tiles, ks = f.shape[0], f.shape[1]
-    f = f.double()
-    f = f[:, :, 0] + f[:, :, 1]                                       # (tile, s, lane, j)
-    if order == "nat":                                                # (tile, s, h, r, j) -> (s, h, j, tile, r)
-        return f.reshape(tiles, ks, 2, 32, 8).permute(1, 2, 4, 0, 3).reshape(16 * ks, 32 * tiles)
-    # (tile, s, h, r, jh, jl) -> (s, jh, h, jl, tile, r)
-    return f.reshape(tiles, ks, 2, 32, 2, 4).permute(1, 4, 2, 5, 0, 3).reshape(16 * ks, 32 * tiles)
-
-
-def _by_wave(f: torch.Tensor, mt: int) -> torch.Tensor:
-    """[4 mt tiles, ks, 2, 64, 8] -> rows in stream order (w, s, m, t)."""
-    ks = f.shape[1]
-    return f.reshape(_WAVES, mt, ks, 2, 64, 8).permute(0, 2, 1, 3, 4, 5).reshape(-1, 64, 8)
-
-
-def _from_wave(rows: torch.Tensor, mt: int, ks: int) -> torch.Tensor:
-    return rows.reshape(_WAVES, ks, mt, 2, 64, 8).permute(0, 2, 1, 3, 4, 5).reshape(_WAVES * mt, ks, 2, 64, 8)
 
 
 def pack_critic_weights(W1, b1, W2, Wav, W3) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -6,11 +6,8 @@
 //     m   = n_nets == 2 ? min(q_1, q_2) : q_1
 //     ent = coef[0] logp_power[row] + coef[1] logp_intent[row]          a term whose logp pointer is NULL is absent
 //     y   = done ? reward : reward + gamma (m - ent)                    a select, as target[done] = rewards_g[done] is
-// Precision is that of k_sarl_critic.hip / k_sarl_actor.hip / k_policy_mlp.hip (read their headers): D = A.B with A =
-// weights (rows = output features) and B = activations (columns = 32 rows of the batch) on v_mfma_f32_32x32x16_f16, both
-// operands split into float16 hi + lo, the weight pre-multiplied by a power of two, three partial products accumulated
-// in float32, the scaling undone where the float32 bias is added.  There is no LayerNorm, so fc1 needs neither centring
-// nor a bias row.
+// Orientation, precision and register order are those of risvec_mfma.hpp (read its header).  There is no LayerNorm, so
+// fc1 needs neither centring nor a bias row.
 //
 // The FORM is that of k_sarl_critic: a workgroup of four wavefronts shares ONE tile of 32 rows and splits the OUTPUT
 // FEATURES of every layer four ways: wavefront w owns fc1 groups w, w + 4, .. and output tiles [w MT, (w + 1) MT) of fc2 /
@@ -27,14 +24,11 @@
 // template parameters and the wavefront index.  Rows at or beyond n_rows are computed on row 0's input and never stored.
 // No global address depends on loaded data; every weight prefetch index is clamped to the last fragment of its block.
 #include "risvec_launch.hpp"
+#include "risvec_mfma.hpp"
 #include "risvec_step.hpp"
 
 namespace risvec {
 namespace {
-
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x8_t __attribute__((ext_vector_type(8)));
 
 struct MarlNetPtrs {
     const uint4* ws;               // the weight stream: fragment rows of 64 x 16 bytes
@@ -64,107 +58,8 @@ struct MarlCriticArgs {
 };
 
 constexpr int kMcBlock = 256;        // 4 wavefronts = 1 per SIMD, all on the same 32 rows
-constexpr int kMcWaves = 4;
-constexpr int kAhead = 4;            // weight fragments are requested this many k-steps ahead of their MFMAs
+constexpr int kMcWaves = kCriticWaves;
 constexpr int kRedSlots = 2;
-
-__device__ __forceinline__ void split16(const f32x8_t& y, half8_t& hi, half8_t& lo) {
-    hi = __builtin_convertvector(y, half8_t);
-    lo = __builtin_convertvector(y - __builtin_convertvector(hi, f32x8_t), half8_t);
-}
-
-__device__ __forceinline__ half8_t ld_frag(const uint4* p) {
-    const uint4 v = *p;
-    return __builtin_bit_cast(half8_t, v);
-}
-
-__device__ __forceinline__ f32x16_t mfma3(const half8_t& ah, const half8_t& al, const half8_t& bh, const half8_t& bl, f32x16_t d) {
-    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, d, 0, 0, 0);
-    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, d, 0, 0, 0);
-    d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, d, 0, 0, 0);
-    return d;
-}
-
-// acc[m] += W_m . B over nks k-steps.  wa: this wavefront's block of the stream, [nks][MT][hi | lo][64]; sb: the B
-// fragments in LDS, [nks][hi | lo][64].  nks >= 1.
-template <int MT>
-__device__ __forceinline__ void gemm_tiles(f32x16_t (&acc)[MT], const uint4* __restrict__ wa, const uint4* sb, int nks, int lane) {
-    half8_t ah[kAhead][MT], al[kAhead][MT];
-    auto fetch = [&](int i, int s) {
-        const uint4* p = wa + (size_t)(s < nks ? s : nks - 1) * (2 * MT * kWave) + lane;
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            ah[i][m] = ld_frag(p + (2 * m) * kWave);
-            al[i][m] = ld_frag(p + (2 * m + 1) * kWave);
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < kAhead; ++i) fetch(i, i);
-    for (int s0 = 0; s0 < nks; s0 += kAhead) {
-#pragma unroll
-        for (int i = 0; i < kAhead; ++i) {
-            const int s = s0 + i;
-            if (s < nks) {
-                const half8_t bh = ld_frag(sb + (2 * s) * kWave + lane), bl = ld_frag(sb + (2 * s + 1) * kWave + lane);
-#pragma unroll
-                for (int m = 0; m < MT; ++m) acc[m] = mfma3(ah[i][m], al[i][m], bh, bl, acc[m]);
-                fetch(i, s + kAhead);
-            }
-        }
-    }
-}
-
-// 16 per-feature parameters tab[base ..] in C/D register order: features (q & 3) + 8 (q >> 2) + 4 h
-__device__ __forceinline__ f32x16_t tile_of(const float* tab, int base, int h) {
-    f32x16_t tl;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float4 q4 = *reinterpret_cast<const float4*>(tab + base + 8 * g + 4 * h);
-        tl[4 * g] = q4.x; tl[4 * g + 1] = q4.y; tl[4 * g + 2] = q4.z; tl[4 * g + 3] = q4.w;
-    }
-    return tl;
-}
-
-__device__ __forceinline__ float sum16(const f32x16_t& v) {
-    float s = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += v[q];
-    return s;
-}
-
-// relu(acc u + bias) of one C/D tile
-__device__ __forceinline__ f32x16_t bias_relu(const f32x16_t& acc, float u, const f32x16_t& b) {
-    f32x16_t y = acc * u + b;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) y[q] = fmaxf(y[q], 0.0f);
-    return y;
-}
-
-// registers 8u .. 8u+7 of a C/D tile -> the split B fragments of k-step 2 tile + u, left in LDS
-__device__ __forceinline__ void put_tile(uint4* sh, int tile, const f32x16_t& y, int lane) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        f32x8_t v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = y[8 * u + j];
-        half8_t hi, lo;
-        split16(v, hi, lo);
-        uint4* p = sh + ((2 * tile + u) * 2) * kWave + lane;
-        p[0] = __builtin_bit_cast(uint4, hi);
-        p[kWave] = __builtin_bit_cast(uint4, lo);
-    }
-}
-
-// rows of 1 KiB of the three blocks of one net's stream, in stream order
-struct MarlLayout { long long fc1, fc2, fc3, rows; };
-__host__ __device__ inline MarlLayout marl_layout(int KS, int NG, int MT2, int MT3) {
-    MarlLayout l;
-    l.fc1 = 0;
-    l.fc2 = l.fc1 + (long long)NG * KS * 2;
-    l.fc3 = l.fc2 + (long long)kMcWaves * (2 * NG) * MT2 * 2;
-    l.rows = l.fc3 + (long long)kMcWaves * (8 * MT2) * MT3 * 2;
-    return l;
-}
 
 template <int MT2, int MT3>
 __global__ void __launch_bounds__(kMcBlock)
@@ -206,7 +101,8 @@ k_marl_critic(MarlCriticArgs A) {
     // ends on a barrier, after which s_h is free again and s_red[slot] is complete.
     auto run_net = [&](const MarlNetPtrs& P, int slot) {
         const float u1 = P.scales[0], u2 = P.scales[1], u3 = P.scales[2];
-        // ---- fc1, groups wave, wave + 4, ..: bias, ReLU, and the split fragments of the group's 32 features go to LDS
+        // ---- fc1, groups wave, wave + 4, .. (the group walk is the twin of k_sarl_critic.hip's; keep the two in step): bias,
+        // ReLU, and the split fragments of the group's 32 features go to LDS
         const int ngw = NG > wave ? (NG - wave + kMcWaves - 1) / kMcWaves : 0;
         if (ngw > 0) {                                        // wave-uniform; no barrier inside
             const int nst = ngw * KS;
@@ -314,19 +210,11 @@ k_marl_critic(MarlCriticArgs A) {
     }
 }
 
-int ks_of(int width) { return (width + 15) / 16; }
-
 template <int MT2, int MT3>
 hipError_t launch_marl(const MarlCriticArgs& a, hipStream_t st) {
     const int hsteps = std::max(2 * a.NG, 8 * MT2);
     const size_t lds = (size_t)(a.KS + hsteps) * 2 * kWave * sizeof(uint4) + (size_t)kRedSlots * kMcWaves * 32 * sizeof(float);
-    auto kern = k_marl_critic<MT2, MT3>;
-    if (lds > 64 * 1024) {
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return err;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_rows + 31) / 32)), dim3(kMcBlock), lds, st, a);
-    return hipGetLastError();
+    return launch_dynamic_lds(k_marl_critic<MT2, MT3>, dim3((unsigned)((a.n_rows + 31) / 32)), dim3(kMcBlock), lds, st, a);
 }
 
 template <int MT2>

@@ -22,6 +22,7 @@
 // elsewhere (a launch-wide choice).  No product feeds a sum anywhere in this file, so there is nothing for the compiler
 // to contract; the pragma below says so all the same.
 #include "risvec_launch.hpp"
+#include "risvec_pack.hpp"
 
 #pragma clang fp contract(off)
 
@@ -35,13 +36,7 @@
 namespace risvec {
 namespace {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-
-constexpr int kStatBlock = 1024;                 // 16 wavefronts per workgroup of the statistics launch
-constexpr int kStatWaves = kStatBlock / kWave;
 constexpr int kMaxBlocks = RISVEC_MARL_CRITIC_PACK_MAX_BLOCKS;   // workgroups per net that take the maxima; <= 64
-constexpr int kPackBlock = 256;
-constexpr int kWaves = 4;                        // wavefronts of k_marl_critic: each owns a quarter of a layer's tiles
 constexpr int kMaxNets = 2;
 static_assert(kMaxBlocks >= 1 && kMaxBlocks <= kWave, "one slot per lane of a wavefront");
 
@@ -71,7 +66,8 @@ __device__ __forceinline__ PackNet net_of(const PackArgs& P, int c) {
                    c ? P.net[1].ws : P.net[0].ws, c ? P.net[1].scales : P.net[0].scales};
 }
 
-// the largest of v over the workgroup (order-independent); red: kStatWaves slots of LDS
+// the largest of v over the workgroup (order-independent); red: kStatWaves slots of LDS.  The float32 form with fmaxf:
+// this file's own, chosen over the template of risvec_pack.hpp (a compare and a select), which compiles differently
 __device__ __forceinline__ float block_max(float v, float* red) {
     for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
     if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
@@ -80,29 +76,6 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     for (int i = 1; i < kStatWaves; ++i) r = fmaxf(r, red[i]);
     __syncthreads();
     return r;
-}
-
-__device__ __forceinline__ float max4(float m, const float4& v) {
-    return fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fmaxf(fabsf(v.y), fabsf(v.z))), fabsf(v.w));
-}
-
-// largest |x| of this thread's share of slice b (of nb) of p[0 .. n): floats up to the first 16-byte boundary and
-// behind the last whole float4 belong to slice 0, the float4 between are dealt out in nb runs
-__device__ __forceinline__ float amax_slice(const float* p, long long n, int b, int nb) {
-    const int tid = threadIdx.x;
-    long long head = (4 - (long long)((reinterpret_cast<uintptr_t>(p) >> 2) & 3)) & 3;
-    head = head < n ? head : n;
-    const long long n4 = (n - head) / 4, tail = head + 4 * n4;
-    float m = 0.0f;
-    if (b == 0) {
-        if (tid < head) m = fabsf(p[tid]);
-        if (tid >= kWave && tail + (tid - kWave) < n) m = fabsf(p[tail + (tid - kWave)]);     // at most 3 floats
-    }
-    const float4* v = reinterpret_cast<const float4*>(p + head);
-    const long long per = (n4 + nb - 1) / nb, lo = per * b, hi = lo + per < n4 ? lo + per : n4;
-#pragma unroll 4
-    for (long long i = lo + tid; i < hi; i += kStatBlock) m = max4(m, v[i]);
-    return m;
 }
 
 __global__ void __launch_bounds__(kStatBlock)
@@ -123,38 +96,7 @@ k_marl_critic_pack_stats(PackArgs P) {
 
 // the shift s of matrix `which` of net c (wave-uniform), every lane of the wavefront taking part
 __device__ __forceinline__ int shift_of(const PackArgs& P, int c, int which, int lane) {
-    float a = lane < kMaxBlocks ? P.amax[((size_t)c * 3 + which) * kMaxBlocks + lane] : 0.0f;
-    for (int o = kWave / 2; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, kWave));
-    return (int)fminf(fmaxf(floorf(log2f(64.0f / fmaxf(a, 1e-30f))), -40.0f), 40.0f);
-}
-
-// 8 scaled weights -> the hi and the lo halves: rows 2 pr and 2 pr + 1 of the stream
-__device__ __forceinline__ void store_pair(uint4* ws, long long pr, int lane, const float (&w)[8]) {
-    half8_t hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        hi[j] = (_Float16)w[j];
-        lo[j] = (_Float16)(w[j] - (float)hi[j]);
-    }
-    ws[(2 * pr) * kWave + lane] = __builtin_bit_cast(uint4, hi);
-    ws[(2 * pr + 1) * kWave + lane] = __builtin_bit_cast(uint4, lo);
-}
-
-// A fragment whose k index runs over an accumulator tile's rows: element j = X[f0 + 8 (j >> 2) + (j & 3)][n], where
-// X[f][n] = W[n * ld + f] (a Linear weight [out, in] read as [in, out]); f0 and ld multiples of 4
-__device__ __forceinline__ void acc_order_weights(const float* W, int ld, int n, int f0, bool vec, double mult, float (&w)[8]) {
-    const float* p = W + (size_t)n * ld + f0;
-    float v[8];
-    if (vec) {
-        const float4 lo4 = *reinterpret_cast<const float4*>(p);
-        const float4 hi4 = *reinterpret_cast<const float4*>(p + 8);
-        v[0] = lo4.x; v[1] = lo4.y; v[2] = lo4.z; v[3] = lo4.w; v[4] = hi4.x; v[5] = hi4.y; v[6] = hi4.z; v[7] = hi4.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = p[8 * (j >> 2) + (j & 3)];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) w[j] = (float)((double)v[j] * mult);
+    return shift_of_slots(lane < kMaxBlocks ? P.amax[((size_t)c * 3 + which) * kMaxBlocks + lane] : 0.0f);
 }
 
 __global__ void __launch_bounds__(kPackBlock)
@@ -209,10 +151,11 @@ long long marl_critic_pack_workspace(int S, int A, int F1, int F2, int F3, int n
 hipError_t launch_marl_critic_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
                                    void* workspace, hipStream_t st) {
     if (!marl_critic_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return hipErrorInvalidValue;
-    const int IN = S + A, KS = (IN + 15) / 16, NG = F1 / 32, MT2 = F2 / 128, MT3 = F3 / 128;
+    const int IN = S + A, KS = ks_of(IN), NG = F1 / 32, MT2 = F2 / 128, MT3 = F3 / 128;
+    const MarlLayout L = marl_layout(KS, NG, MT2, MT3);              // a block's pairs: half its rows
     PackArgs a{};
     a.IN = IN; a.F1 = F1; a.F2 = F2; a.F3 = F3; a.KS = KS; a.NG = NG; a.MT2 = MT2; a.MT3 = MT3;
-    a.n_fc1 = NG * KS; a.n_fc2 = kWaves * 2 * NG * MT2; a.n_fc3 = kWaves * 8 * MT2 * MT3;
+    a.n_fc1 = (int)((L.fc2 - L.fc1) / 2); a.n_fc2 = (int)((L.fc3 - L.fc2) / 2); a.n_fc3 = (int)((L.rows - L.fc3) / 2);
     // the pairs of rows in all: half the rows of marl_critic_stream_bytes()
     const long long pairs = (long long)a.n_fc1 + a.n_fc2 + a.n_fc3;
     if (pairs * 2048 != marl_critic_stream_bytes(S, A, F1, F2, F3)) return hipErrorInvalidValue;

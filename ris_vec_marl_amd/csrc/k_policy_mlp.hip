@@ -4,11 +4,10 @@
 // (the three-launch form moves 805 + 805 + 268 + 268 MB per step at E = 32 768; this one reads the
 // observations and writes the heads).
 //
-// Orientation.  D = A.B with A = weights (rows = output features), B = activations (columns = the 32 envs of
-// this wavefront), so after the K loop a LANE holds, for its env (lane & 31), half of that env's output
-// features in registers (C/D map of v_mfma_f32_32x32x16: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) +
-// 4 (lane >> 5)); the other half sits in lane ^ 32.  LayerNorm over the features is therefore in-register sums
-// plus ONE cross-lane exchange, and each layer's output is the next MFMA's B operand as it stands.
+// Orientation, precision and register order are those of risvec_mfma.hpp (read its header): a wavefront owns 32 envs, a
+// LANE holds, for its env (lane & 31), half of that env's output features in registers, the other half sits in
+// lane ^ 32.  LayerNorm over the features is therefore in-register sums plus ONE cross-lane exchange, and each layer's
+// output is the next MFMA's B operand as it stands.
 //
 // B operand, generated on the fly -- by the matrix cores too.  LayerNorm needs the row statistics of the fc1
 // pre-activation first; fc1 being linear they have a closed form: with the weight centred over the feature
@@ -20,12 +19,7 @@
 // the next MFMA when the k order of the fc2 weight is chosen to match (registers 8u .. 8u+7 are k-step u): ReLU and
 // the float16 split are all the vector ALU has to do, and no fc1 weight is read by the vector path at all.
 //
-// Precision.  Both operands are split, x = hi + lo with hi = fp16(x), lo = fp16(x - hi), and the three
-// significant partial products hi.hi + hi.lo + lo.hi taken as three MFMAs per 16-feature chunk with float32
-// accumulation: 2^-22 relative per product.  The weight is pre-multiplied by a power of two (per agent, its
-// largest entry lands in [64, 128)) so that its low part stays in the float16 normal range; the accumulator
-// is multiplied back (exactly) when the fc2 bias is added.  The low part of a small activation (< 0.125) can be
-// a float16 subnormal: absolute error <= 2^-25 per such product, below the float32 rounding of the sum.
+// Precision.  The split product of risvec_mfma.hpp; the weight scaling is per agent, undone when the fc2 bias is added.
 //
 // A operand.  The split fc2 weight is stored in FRAGMENT order (per group of 32 hidden features: the fc1 operand
 // of the next group, then two chunks [hi|lo][m][lane][8 halfs]), one contiguous stream per agent that goes
@@ -36,16 +30,11 @@
 // Workgroup = 8 wavefronts (2 per SIMD, 220 registers each incl. 128 accumulators) sharing one weight stream;
 // one workgroup per CU (123 KB of LDS).  The head weight rides in on the ring's free slot during the last group.
 #include "risvec_launch.hpp"
+#include "risvec_mfma.hpp"
 #include "risvec_step.hpp"
 
 namespace risvec {
 namespace {
-
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(1))) void gvoid_t;
-typedef __attribute__((address_space(3))) void lvoid_t;
 
 struct MlpArgs {
     int E, V, IN, F1, H;
@@ -62,13 +51,7 @@ struct MlpArgs {
     float* heads;            // [V,E,H]
 };
 
-constexpr float kLnEps = 1e-5f;
 constexpr int kIn1 = 6;      // input rows of G: up to 5 inputs + the bias row
-
-__device__ __forceinline__ void split16(const f32x8_t& y, half8_t& hi, half8_t& lo) {
-    hi = __builtin_convertvector(y, half8_t);
-    lo = __builtin_convertvector(y - __builtin_convertvector(hi, f32x8_t), half8_t);
-}
 
 constexpr int kMlpBlock = 512;       // 8 wavefronts = 2 per SIMD sharing one weight stream
 constexpr int kRing = 3;             // group slots in LDS: one being read, two in flight / landed
@@ -318,14 +301,8 @@ template <int MT>
 hipError_t launch_mlp(const MlpArgs& a, hipStream_t st) {
     const int F2 = 32 * MT;
     const size_t lds = (size_t)kRing * (8 * kWave + 4 * MT * kWave) * sizeof(uint4) + ((size_t)3 * F2 + 32 + kIn1 * kIn1) * sizeof(float);
-    auto kern = k_policy_mlp<MT>;
-    if (lds > 64 * 1024) {
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return err;
-    }
     const int rows = (kMlpBlock / kWave) * 32;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.E + rows - 1) / rows), (unsigned)a.V), dim3(kMlpBlock), lds, st, a);
-    return hipGetLastError();
+    return launch_dynamic_lds(k_policy_mlp<MT>, dim3((unsigned)((a.E + rows - 1) / rows), (unsigned)a.V), dim3(kMlpBlock), lds, st, a);
 }
 
 }  // namespace

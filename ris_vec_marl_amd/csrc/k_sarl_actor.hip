@@ -2,12 +2,8 @@
 // fc1 -> LayerNorm -> ReLU -> fc2 -> LayerNorm -> ReLU -> mu -> sigmoid for n_rows rows that share ONE weight set, every
 // product on the fp16 matrix cores at float32 accuracy and neither hidden layer ever written to memory.
 //
-// Orientation and precision are those of k_policy_mlp.hip (read its header): D = A.B with A = weights (rows = output
-// features) and B = activations (columns = the 32 rows of this wavefront), so a lane holds its row's features in
-// registers (C/D map of v_mfma_f32_32x32x16: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) and each
-// layer's output is the next MFMA's B operand as it stands; both operands split into float16 hi + lo, the weight
-// pre-multiplied by a power of two so that lo stays normal, the three significant partial products accumulated in
-// float32 (2^-22 relative per product), the scaling undone exactly where the bias is added.
+// Orientation, precision and register order are those of risvec_mfma.hpp (read its header): a wavefront owns 32 rows, a
+// lane holds its row's features in registers, and each layer's output is the next MFMA's B operand as it stands.
 //
 // What differs from k_policy_mlp:
 //  * fc1 has 80+ inputs, so it is a real MFMA product (K = in_dims + 1 padded to KS k-steps of 16: the bias is one more
@@ -32,17 +28,11 @@
 // Every s_barrier sits under wave-uniform control flow: all loop bounds come from kernel arguments and template
 // parameters, and rows at or beyond n_rows are computed on row 0's input and never stored.
 #include "risvec_launch.hpp"
+#include "risvec_mfma.hpp"
 #include "risvec_step.hpp"
 
 namespace risvec {
 namespace {
-
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) void gvoid_t;
-typedef __attribute__((address_space(3))) void lvoid_t;
 
 struct ActorArgs {
     long long n_rows;
@@ -56,15 +46,9 @@ struct ActorArgs {
     float* mu;               // [n_rows, A]
 };
 
-constexpr float kLnEps = 1e-5f;
 constexpr int kActBlock = 256;       // 4 wavefronts = 1 per SIMD
 constexpr int kRing = 3;             // item slots in LDS: one being read, two in flight / landed
 constexpr int kMaxHT = 3;            // n_actions <= 96
-
-__device__ __forceinline__ void split16(const f32x8_t& y, half8_t& hi, half8_t& lo) {
-    hi = __builtin_convertvector(y, half8_t);
-    lo = __builtin_convertvector(y - __builtin_convertvector(hi, f32x8_t), half8_t);
-}
 
 constexpr int actor_rows(int MT, int KS) { return (2 * KS + 1 + 4 * MT + 3) & ~3; }
 
@@ -193,11 +177,7 @@ k_sarl_actor(ActorArgs A) {
         for (int j = 0; j < 8; ++j) v[j] = y[8 * u + j];
         split16(v, bf[0], bf[1]);
     };
-    // A fragments are read two feature tiles (six MFMAs) ahead of their use, by hand: hipcc sinks LDS reads next
-    // to their first use and then waits lgkmcnt(0), which exposes the LDS latency in front of every third MFMA.
-    // The reads are inline asm (issued in program order), and each counted wait names the fragments it releases,
-    // so the MFMAs that consume them cannot be moved above it.  Compiler-generated LDS reads may interleave:
-    // counters retire in order, so extra reads can only make either side wait longer, never too little.
+    // k_policy_mlp.hip's mfma_chunk and its reasons, word for word (lifting it into risvec_mfma.hpp changes the schedule)
     auto mfma_chunk = [&](const uint4* sa, const half8_t (&bf)[2]) {
         const uint32_t base = (uint32_t)(size_t)(lvoid_t*)(sa + lane);
         half8_t ah[3], al[3];
@@ -253,6 +233,7 @@ k_sarl_actor(ActorArgs A) {
     }
 
     // ---- fc2 bias + LayerNorm + ReLU, in registers: this lane owns features 32m + (q & 3) + 8 (q >> 2) + 4h of its row
+    // (the twin of the block in k_policy_mlp.hip; keep the two in step)
     const float inv_f2 = 1.0f / (float)F2;
     {
         auto tile_of = [&](const float* tab, int m) {            // 16 per-feature parameters in C/D register order
@@ -377,7 +358,7 @@ k_sarl_actor(ActorArgs A) {
 constexpr int kKs[4] = {3, 6, 7, 9};
 
 int ks_built(int IN) {
-    const int ks = (IN + 1 + 15) / 16;
+    const int ks = ks_of(IN + 1);
     for (int k : kKs)
         if (ks <= k) return k;
     return 0;
@@ -386,14 +367,8 @@ int ks_built(int IN) {
 template <int MT, int KS>
 hipError_t launch_actor(const ActorArgs& a, hipStream_t st) {
     const size_t lds = (size_t)kRing * actor_rows(MT, KS) * kWave * sizeof(uint4);
-    auto kern = k_sarl_actor<MT, KS>;
-    if (lds > 64 * 1024) {
-        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (err != hipSuccess) return err;
-    }
     const long long rows = (kActBlock / kWave) * 32;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_rows + rows - 1) / rows)), dim3(kActBlock), lds, st, a);
-    return hipGetLastError();
+    return launch_dynamic_lds(k_sarl_actor<MT, KS>, dim3((unsigned)((a.n_rows + rows - 1) / rows)), dim3(kActBlock), lds, st, a);
 }
 
 template <int MT>

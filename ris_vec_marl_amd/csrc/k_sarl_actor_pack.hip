@@ -18,17 +18,13 @@
 // they are the same bits, which the forward kernel relies on.  No product feeds a sum anywhere in this file, so there
 // is nothing for the compiler to contract; the pragma below says so all the same.
 #include "risvec_launch.hpp"
+#include "risvec_pack.hpp"
 
 #pragma clang fp contract(off)
 
 namespace risvec {
 namespace {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-
-constexpr int kStatBlock = 1024;                 // 16 wavefronts: the one workgroup of the statistics launch
-constexpr int kStatWaves = kStatBlock / kWave;
-constexpr int kPackBlock = 256;
 constexpr int kMaxK1 = 129;                      // in_dims + 1 <= 129 rows of [W1^T ; b1]
 
 struct PackArgs {
@@ -43,25 +39,6 @@ struct PackArgs {
     double* mean;                                // workspace: [16 KS] row means of [W1^T ; b1] (rows > IN unused)
     double* mult;                                // workspace: [3] 2^s of fc1, fc2, mu
 };
-
-// the largest of v over the workgroup (order-independent); red: kStatWaves slots of LDS
-template <typename T>
-__device__ __forceinline__ T block_max(T v, T* red) {
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const T w = __shfl_xor(v, o, kWave);
-        v = w > v ? w : v;
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    T r = red[0];
-    for (int i = 1; i < kStatWaves; ++i) r = red[i] > r ? red[i] : r;
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ float max4(float m, const float4& v) {
-    return fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fmaxf(fabsf(v.y), fabsf(v.z))), fabsf(v.w));
-}
 
 // largest |x| over n4 float4 of p, for this thread's share
 __device__ __forceinline__ float amax_f4(const float4* p, int n4) {

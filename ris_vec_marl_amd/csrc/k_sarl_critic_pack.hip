@@ -23,6 +23,7 @@
 // elsewhere (a launch-wide choice).  No product feeds a sum anywhere in this file, so there is nothing for the compiler
 // to contract; the pragma below says so all the same.
 #include "risvec_launch.hpp"
+#include "risvec_pack.hpp"
 
 #pragma clang fp contract(off)
 
@@ -35,15 +36,9 @@
 namespace risvec {
 namespace {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-
-constexpr int kStatBlock = 1024;                 // 16 wavefronts per workgroup of the statistics launch
-constexpr int kStatWaves = kStatBlock / kWave;
 constexpr int kMaxBlocks = RISVEC_CRITIC_PACK_MAX_BLOCKS;   // workgroups that take the maxima of W2, Wav, W3; <= 64
-constexpr int kPackBlock = 256;
 constexpr int kMaxK1 = 129;                      // in_dims + 1 <= 129 rows of [W1^T ; b1]
 constexpr int kMeanSlots = 144;                  // 16 KS <= 144 doubles
-constexpr int kWaves = 4;                        // wavefronts of k_sarl_critic: each owns a quarter of a layer's tiles
 static_assert(kMaxBlocks >= 1 && kMaxBlocks <= kWave, "one slot per lane of a wavefront");
 
 // scales / factors / maxima are kept in the order of scales[4]: fc1, fc2, action_value, fc3
@@ -64,44 +59,6 @@ struct PackArgs {
     double* amax1;                               // workspace: [1] largest |centred fc1|
     float* amax;                                 // workspace: [3][kMaxBlocks] slices of fc2, action_value, fc3 (rows kFc2 - 1 ..)
 };
-
-// the largest of v over the workgroup (order-independent); red: kStatWaves slots of LDS
-template <typename T>
-__device__ __forceinline__ T block_max(T v, T* red) {
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const T w = __shfl_xor(v, o, kWave);
-        v = w > v ? w : v;
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    T r = red[0];
-    for (int i = 1; i < kStatWaves; ++i) r = red[i] > r ? red[i] : r;
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ float max4(float m, const float4& v) {
-    return fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fmaxf(fabsf(v.y), fabsf(v.z))), fabsf(v.w));
-}
-
-// largest |x| of this thread's share of slice b (of nb) of p[0 .. n): floats up to the first 16-byte boundary and
-// behind the last whole float4 belong to slice 0, the float4 between are dealt out in nb runs
-__device__ __forceinline__ float amax_slice(const float* p, long long n, int b, int nb) {
-    const int tid = threadIdx.x;
-    long long head = (4 - (long long)((reinterpret_cast<uintptr_t>(p) >> 2) & 3)) & 3;
-    head = head < n ? head : n;
-    const long long n4 = (n - head) / 4, tail = head + 4 * n4;
-    float m = 0.0f;
-    if (b == 0) {
-        if (tid < head) m = fabsf(p[tid]);
-        if (tid >= kWave && tail + (tid - kWave) < n) m = fabsf(p[tail + (tid - kWave)]);     // at most 3 floats
-    }
-    const float4* v = reinterpret_cast<const float4*>(p + head);
-    const long long per = (n4 + nb - 1) / nb, lo = per * b, hi = lo + per < n4 ? lo + per : n4;
-#pragma unroll 4
-    for (long long i = lo + tid; i < hi; i += kStatBlock) m = max4(m, v[i]);
-    return m;
-}
 
 __global__ void __launch_bounds__(kStatBlock)
 k_sarl_critic_pack_stats(PackArgs P) {
@@ -167,38 +124,7 @@ k_sarl_critic_pack_stats(PackArgs P) {
 __device__ __forceinline__ int shift_of(const PackArgs& P, int which, int lane) {
     if (which == kFc1)                           // a float64 operand: the quotient and the logarithm in float64
         return (int)fmin(fmax(floor(log2(64.0 / fmax(P.amax1[0], 1e-30))), -40.0), 40.0);
-    float a = lane < kMaxBlocks ? P.amax[(which - 1) * kMaxBlocks + lane] : 0.0f;
-    for (int o = kWave / 2; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, kWave));
-    return (int)fminf(fmaxf(floorf(log2f(64.0f / fmaxf(a, 1e-30f))), -40.0f), 40.0f);
-}
-
-// 8 scaled weights -> the hi and the lo halves: rows 2 pr and 2 pr + 1 of the stream
-__device__ __forceinline__ void store_pair(uint4* ws, long long pr, int lane, const float (&w)[8]) {
-    half8_t hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        hi[j] = (_Float16)w[j];
-        lo[j] = (_Float16)(w[j] - (float)hi[j]);
-    }
-    ws[(2 * pr) * kWave + lane] = __builtin_bit_cast(uint4, hi);
-    ws[(2 * pr + 1) * kWave + lane] = __builtin_bit_cast(uint4, lo);
-}
-
-// A fragment whose k index runs over an accumulator tile's rows: element j = X[f0 + 8 (j >> 2) + (j & 3)][n], where
-// X[f][n] = W[n * ld + f] (a Linear weight [out, in] read as [in, out]); f0 and ld multiples of 4
-__device__ __forceinline__ void acc_order_weights(const float* W, int ld, int n, int f0, bool vec, double mult, float (&w)[8]) {
-    const float* p = W + (size_t)n * ld + f0;
-    float v[8];
-    if (vec) {
-        const float4 lo4 = *reinterpret_cast<const float4*>(p);
-        const float4 hi4 = *reinterpret_cast<const float4*>(p + 8);
-        v[0] = lo4.x; v[1] = lo4.y; v[2] = lo4.z; v[3] = lo4.w; v[4] = hi4.x; v[5] = hi4.y; v[6] = hi4.z; v[7] = hi4.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = p[8 * (j >> 2) + (j & 3)];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) w[j] = (float)((double)v[j] * mult);
+    return shift_of_slots(lane < kMaxBlocks ? P.amax[(which - 1) * kMaxBlocks + lane] : 0.0f);
 }
 
 __global__ void __launch_bounds__(kPackBlock)
@@ -263,11 +189,12 @@ hipError_t launch_sarl_critic_pack(int IN, int F1, int F2, int F3, int A, const 
                                    const float* Wav, const float* W3, void* wstream, float* scales, void* workspace,
                                    hipStream_t st) {
     if (!sarl_critic_supported(IN, F1, F2, F3, A)) return hipErrorInvalidValue;
-    const int KS = (IN + 1 + 15) / 16, KSA = (A + 15) / 16, NG = F1 / 32, MT2 = F2 / 128, MT3 = F3 / 128;
+    const int KS = ks_of(IN + 1), KSA = ks_of(A), NG = F1 / 32, MT2 = F2 / 128, MT3 = F3 / 128;
+    const CriticLayout L = critic_layout(KS, KSA, NG, MT2, MT3);     // a block's pairs: half its rows
     double* wsp = static_cast<double*>(workspace);
     const bool vec = ((reinterpret_cast<uintptr_t>(W2) | reinterpret_cast<uintptr_t>(W3)) & 15u) == 0;
     PackArgs a{IN, F1, F2, F3, A, KS, KSA, NG, MT2, MT3,
-               kWaves * KSA * MT2, NG * KS, kWaves * 2 * NG * MT2, kWaves * 8 * MT2 * MT3, vec ? 1 : 0,
+               (int)((L.fc1 - L.av) / 2), (int)((L.fc2 - L.fc1) / 2), (int)((L.fc3 - L.fc2) / 2), (int)((L.rows - L.fc3) / 2), vec ? 1 : 0,
                W1, b1, W2, Wav, W3, static_cast<uint4*>(wstream), scales,
                wsp, wsp + kMeanSlots, reinterpret_cast<float*>(wsp + kMeanSlots + 2)};
     // the pairs of rows in all: half the rows of sarl_critic_stream_bytes()

@@ -105,6 +105,37 @@ hipError_t launch_sarl_actor_pack(int IN, int F1, int F2, int A, const float* W1
                                   const float* ln1b, const float* W2, const float* Wmu, void* wstream, float* scales,
                                   void* workspace, hipStream_t st);
 
+// k-steps of 16 that cover `width` inputs
+inline int ks_of(int width) { return (width + 15) / 16; }
+
+// Both critic kernels run a workgroup of this many wavefronts on one tile of 32 rows; each owns a quarter of every
+// layer's output tiles, and the weight streams are laid out per wavefront accordingly.
+constexpr int kCriticWaves = 4;
+
+// The weight stream of k_sarl_critic: rows of 1 KiB at which its four blocks start, in stream order, and their total.
+// Read by the kernel and by the launcher of its pack (a block's rows = the difference of two starts).
+struct CriticLayout { long long av, fc1, fc2, fc3, rows; };
+__host__ __device__ inline CriticLayout critic_layout(int KS, int KSA, int NG, int MT2, int MT3) {
+    CriticLayout l;
+    l.av = 0;
+    l.fc1 = l.av + (long long)kCriticWaves * KSA * MT2 * 2;
+    l.fc2 = l.fc1 + (long long)NG * KS * 2;
+    l.fc3 = l.fc2 + (long long)kCriticWaves * (2 * NG) * MT2 * 2;
+    l.rows = l.fc3 + (long long)kCriticWaves * (8 * MT2) * MT3 * 2;
+    return l;
+}
+
+// The same for the three blocks of one net's stream of k_marl_critic.
+struct MarlLayout { long long fc1, fc2, fc3, rows; };
+__host__ __device__ inline MarlLayout marl_layout(int KS, int NG, int MT2, int MT3) {
+    MarlLayout l;
+    l.fc1 = 0;
+    l.fc2 = l.fc1 + (long long)NG * KS * 2;
+    l.fc3 = l.fc2 + (long long)kCriticWaves * (2 * NG) * MT2 * 2;
+    l.rows = l.fc3 + (long long)kCriticWaves * (8 * MT2) * MT3 * 2;
+    return l;
+}
+
 // The DDPG critic forward and TD target in one launch (k_sarl_critic.hip).  sarl_critic_stream_bytes(): the size of its
 // weight stream for a supported shape (0 otherwise).  reward / done are read only when y is given; q and y are optional.
 bool sarl_critic_supported(int IN, int F1, int F2, int F3, int A);
@@ -165,6 +196,18 @@ void note_theta_by_index(bool by_index);
 const RisVecForce& forced_forms();
 // `rule` unless the override field forces the form on or off
 inline bool forced_or(int32_t field, bool rule) { return field == RISVEC_BY_RULE ? rule : field == RISVEC_FORCE_ON; }
+
+// Launch `kernel(args)` with lds_bytes of dynamic LDS; beyond 64 KiB the kernel's limit is raised first.
+template <typename Args>
+hipError_t launch_dynamic_lds(void (*kernel)(Args), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Args& args) {
+    if (lds_bytes > 64 * 1024) {
+        hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)lds_bytes);
+        if (err != hipSuccess) return err;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args);
+    return hipGetLastError();
+}
 
 inline Dims dims_of(const RisVecState& s) {
     return Dims{s.n_envs, s.n_veh, s.n_ris, s.control_bit, (long long)s.env_offset};

@@ -23,8 +23,8 @@ from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _native as N
-from .actor import _split_scaled, polyak_pairs, polyak_tau, soft_update_tensors
-from .critic import _WAVES, _by_wave, _frags, _from_wave, _unfrags
+from ._wstream import (_WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags, polyak_pairs, polyak_tau,
+                       soft_update_tensors)
 
 
 class MarlCriticGeom(NamedTuple):

@@ -107,7 +107,7 @@ class BatchedPolicy:
         return self._w2_split[1]
 
     @staticmethod
-    def _split_scaled(w: torch.Tensor, target: float, max_shift: Optional[torch.Tensor] = None):
+    def _split_scaled_per_agent(w: torch.Tensor, target: float, max_shift: Optional[torch.Tensor] = None):
         """(hi, lo, 2^-s): w 2^s with its largest entry in [target, 2 target) per agent, split into float16
         hi + lo (the scaling keeps lo in the float16 normal range; powers of two cancel exactly)."""
         amax = w.abs().amax(dim=tuple(range(1, w.dim()))).clamp_min(1e-30)
@@ -136,16 +136,16 @@ class BatchedPolicy:
             op1[:, :, IN + 1] = self.ln1_b.double()[:, 0]
             # the scaled LayerNorm-1 output (<= sqrt(F1) |ln1_w| + |ln1_b|) must stay inside float16
             bound = math.sqrt(F1) * self.ln1_w.abs().amax(dim=(1, 2)) + self.ln1_b.abs().amax(dim=(1, 2))
-            h1, l1, u1 = self._split_scaled(op1.float(), 16.0, torch.floor(torch.log2(3.0e4 / bound.clamp_min(1e-30))))
+            h1, l1, u1 = self._split_scaled_per_agent(op1.float(), 16.0, torch.floor(torch.log2(3.0e4 / bound.clamp_min(1e-30))))
             # (v, t, g, r, h, j) -> (v, g, t, h, r, j): lane = 32 h + r
             w1f = torch.stack([h1, l1], 1).reshape(V, 2, F1 // 32, 32, 2, 8).permute(0, 2, 1, 4, 3, 5).reshape(V, F1 // 32, 2, 64, 8)
-            h2, l2, u2 = self._split_scaled(self.W2, 64.0)
+            h2, l2, u2 = self._split_scaled_per_agent(self.W2, 64.0)
             # hidden feature f = 32 g + 16 u + 8 jh + 4 h + jl: (v, t, g, u, jh, h, jl, m, r) -> (v, g, u, t, m, h, r, jh, jl)
             frag = torch.stack([h2, l2], 1).reshape(V, 2, F1 // 32, 2, 2, 2, 4, F2 // 32, 32) \
                 .permute(0, 2, 3, 1, 7, 5, 8, 4, 6).contiguous()
             whp = torch.zeros(V, F2, 32, device=dev)
             whp[:, :, :4 + V] = self.Wh
-            hh, hl, uh = self._split_scaled(whp, 64.0)
+            hh, hl, uh = self._split_scaled_per_agent(whp, 64.0)
             # feature f = 32 m + 16 u + 8 jh + 4 h + jl: (v, t, m, u, jh, h, jl, r) -> (v, m, u, t, h, r, jh, jl)
             hfrag = torch.stack([hh, hl], 1).reshape(V, 2, F2 // 32, 2, 2, 2, 4, 32).permute(0, 2, 3, 1, 5, 7, 4, 6).contiguous()
             # the weight stream, per group of 32 hidden features: fc1 operand of the NEXT group (8 KiB slot), two chunks
