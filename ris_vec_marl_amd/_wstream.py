@@ -1,17 +1,13 @@
-"""What the weight streams of the hand-written MLP kernels share on the host: the scaled float16 hi + lo split, the MFMA
-fragment orders of the critics' streams, and the Polyak blend of a target network.  The device side of the same
-scheme is described in csrc/risvec_mfma.hpp and csrc/risvec_pack.hpp.  `actor`, `critic` and `marl_critic` import
-these names and keep them importable.
+"""How the weight streams of the hand-written MLP kernels are laid out, as far as they share it on the host: the scaled
+float16 hi + lo split and the MFMA fragment orders of the critics' streams.  The device side of the same scheme is
+described in csrc/risvec_mfma.hpp and csrc/risvec_pack.hpp.  Who owns the weights a stream is built from, and the Polyak
+blend of a target network, are `_weights`' subject; its blend functions stay importable from here.
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
-from typing import Mapping, Sequence, Tuple
-
 import torch
 
-from . import _native as N
+from ._weights import polyak_pairs, polyak_tau, soft_update_tensors  # noqa: F401
 
 _WAVES = 4                        # wavefronts of a workgroup: each owns a quarter of every layer's output features
 
@@ -64,51 +60,3 @@ def _by_wave(f: torch.Tensor, mt: int) -> torch.Tensor:
 
 def _from_wave(rows: torch.Tensor, mt: int, ks: int) -> torch.Tensor:
     return rows.reshape(_WAVES, ks, mt, 2, 64, 8).permute(0, 2, 1, 3, 4, 5).reshape(_WAVES * mt, ks, 2, 64, 8)
-
-
-def polyak_pairs(target, online, what: str):
-    """[(online tensor, target tensor)] in the order of `target._WEIGHTS` for `target.soft_update_from(online, tau)`:
-    `online` is an object of `target`'s class and shape or a mapping under the reference's key names.  Refuses what
-    `share_state_dict` refuses (KeyError for a missing key, ValueError for a tensor that is not contiguous float32 of
-    the right shape on the target's device) before anything is touched."""
-    names = {a: k for k, a in target._SD.items()}
-    if isinstance(online, Mapping):
-        for k in target._SD:
-            if k not in online:
-                raise KeyError("%s: %r is missing" % (what, k))
-        src = {a: online[names[a]] for a in target._WEIGHTS}
-    elif isinstance(online, type(target)):
-        src = {a: getattr(online, a) for a in target._WEIGHTS}
-    else:
-        raise ValueError("%s: online must be a %s of the same shape or a mapping of its weights under the reference's key names"
-                         % (what, type(target).__name__))
-    pairs = []
-    for a in target._WEIGHTS:
-        t, mine = src[a], getattr(target, a)
-        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != target.device
-                or not t.is_contiguous() or tuple(t.shape) != tuple(mine.shape)):
-            raise ValueError("%s: %s must be a contiguous float32 tensor of shape %s on %s (it is read in place)"
-                             % (what, names[a], tuple(mine.shape), target.device))
-        if t.data_ptr() == mine.data_ptr():
-            raise ValueError("%s: %s is the target's own tensor" % (what, names[a]))
-        pairs.append((t, mine))
-    return pairs
-
-
-def polyak_tau(tau, what: str) -> float:
-    tau = float(tau)
-    if not math.isfinite(tau) or not 0.0 <= tau <= 1.0:
-        raise ValueError("%s: tau must be finite and in [0, 1]" % what)
-    return tau
-
-
-def soft_update_tensors(pairs: Sequence[Tuple[torch.Tensor, torch.Tensor]], tau: float, device) -> None:
-    """target = tau * online + (1 - tau) * target for up to 32 (online, target) pairs of contiguous float32 device tensors in
-    ONE launch on the current stream (`risvec_soft_update`, csrc/k_soft_update.hip), in place, with the bits of that
-    expression on float32 tensors (`ddpg_torch.py:122-127`).  The targets' version counters are not advanced."""
-    N.require_hip(device)
-    n = len(pairs)
-    on = (C.c_void_p * n)(*(o.data_ptr() for o, _ in pairs))
-    tg = (C.c_void_p * n)(*(t.data_ptr() for _, t in pairs))
-    ne = (C.c_int64 * n)(*(t.numel() for _, t in pairs))
-    N.check(N.load().risvec_soft_update(n, on, tg, ne, tau, 1.0 - tau, N.stream(device)))

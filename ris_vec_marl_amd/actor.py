@@ -11,12 +11,14 @@ launches, actor and everything else.  No CPU compute path.
 from __future__ import annotations
 
 import math
-from typing import Mapping, NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _native as N
-from ._wstream import _split_scaled, centre_fc1, polyak_pairs, polyak_tau, soft_update_tensors
+from ._weights import (PACK_RULE, WeightSet, choose_mode, is_f32, out_f32, pack_out, pack_workspace, rows_of,
+                       soft_update_tensors, stream_pair)  # noqa: F401 (soft_update_tensors stays importable from here)
+from ._wstream import _split_scaled, centre_fc1
 
 _KS_BUILT = (3, 6, 7, 9)          # fc1 k-steps of 16 the kernel is instantiated for (csrc/k_sarl_actor.hip)
 
@@ -103,7 +105,7 @@ def pack_actor_weights_device(W1, b1, ln1_w, ln1_b, W2, Wmu, out=None, workspace
     one, except that the float64 row means of the centred fc1 weight are summed in another order."""
     lib = N.load()
     ws = (W1, b1, ln1_w, ln1_b, W2, Wmu)
-    if not all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.device == W1.device for t in ws):
+    if not (isinstance(W1, torch.Tensor) and all(is_f32(t, W1.device) for t in ws)):
         raise ValueError("pack_actor_weights_device: the weights must be contiguous float32 tensors on one device")
     dev = W1.device
     N.require_hip(dev)
@@ -118,16 +120,8 @@ def pack_actor_weights_device(W1, b1, ln1_w, ln1_b, W2, Wmu, out=None, workspace
     if need == 0:
         raise ValueError("no fused actor kernel for input_dims=%d fc1=%d fc2=%d n_actions=%d" % (IN, F1, F2, A))
     g = actor_geom(IN, F1, F2, A)
-    if out is None:
-        out = (torch.empty(g.items, g.rows, 64, 8, dtype=torch.float16, device=dev), torch.empty(3, device=dev))
-    stream, scales = out
-    N.in_place(stream, torch.float16, (g.items, g.rows, 64, 8), "pack_actor_weights_device: out[0]", dev)
-    N.in_place(scales, torch.float32, (3,), "pack_actor_weights_device: out[1]", dev)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
-            or not workspace.is_contiguous()):
-        raise ValueError("pack_actor_weights_device: workspace must be a contiguous uint8 tensor on %s" % dev)
+    stream, scales = pack_out(out, (g.items, g.rows, 64, 8), 3, "pack_actor_weights_device: out", dev)
+    workspace = pack_workspace(workspace, need, "pack_actor_weights_device", dev)
     N.check(lib.risvec_sarl_actor_pack(IN, F1, F2, A, *(t.data_ptr() for t in ws), stream.data_ptr(),
                                        stream.numel() * stream.element_size(), scales.data_ptr(), workspace.data_ptr(),
                                        workspace.numel(), N.stream(dev)))
@@ -160,7 +154,7 @@ def unpack_actor_weights(stream: torch.Tensor, scales: torch.Tensor, input_dims:
             "ln1_w": ln[:, :32].reshape(-1).double(), "ln1_b": ln[:, 32:64].reshape(-1).double()}
 
 
-class BatchedActor:
+class BatchedActor(WeightSet):
     """`ActorNetwork` (NET:95-141) for n rows at once: input_dims -> fc1 -> LayerNorm -> ReLU -> fc2 -> LayerNorm -> ReLU
     -> mu[n_actions] -> sigmoid.  `input_dims` is the flattened width, n_agents x per-agent width (NET:99)."""
 
@@ -169,6 +163,9 @@ class BatchedActor:
     _WEIGHTS = ("W1", "b1", "ln1_w", "ln1_b", "W2", "b2", "ln2_w", "ln2_b", "Wmu", "bmu")
     _SD = {"fc1.weight": "W1", "fc1.bias": "b1", "bn1.weight": "ln1_w", "bn1.bias": "ln1_b", "fc2.weight": "W2",
            "fc2.bias": "b2", "bn2.weight": "ln2_w", "bn2.bias": "ln2_b", "mu.weight": "Wmu", "mu.bias": "bmu"}
+    _PACKED = ("W1", "b1", "ln1_w", "ln1_b", "W2", "Wmu")     # what the weight stream is built from
+    _NOUN = "actor"
+    _pack_host, _pack_device = staticmethod(pack_actor_weights), staticmethod(pack_actor_weights_device)
 
     def __init__(self, input_dims: int, n_actions: int, fc1_dims: int = 512, fc2_dims: int = 256, device="cuda", seed: int = 0,
                  gemm: Optional[str] = None, pack: Optional[str] = None):
@@ -187,19 +184,15 @@ class BatchedActor:
         self.input_dims, self.n_actions, self.fc1_dims, self.fc2_dims = int(input_dims), int(n_actions), int(fc1_dims), int(fc2_dims)
         if min(self.input_dims, self.n_actions, self.fc1_dims, self.fc2_dims) < 1:
             raise ValueError("BatchedActor: every dimension must be >= 1")
-        fused_ok = bool(lib.risvec_sarl_actor_supported(self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions))
-        self.gemm = gemm if gemm is not None else ("fused" if fused_ok else "library")
-        if self.gemm not in self.GEMM_MODES or (self.gemm == "fused" and not fused_ok):
-            raise ValueError("gemm=%r is not available for input_dims=%d fc1=%d fc2=%d n_actions=%d (modes: %s; fused: "
-                             "input_dims <= 128, fc1 %% 32 == 0 <= 1024, fc2 in {128, 256}, n_actions <= 96)"
-                             % (gemm, self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions, ", ".join(self.GEMM_MODES)))
-        self.pack = pack if pack is not None else "host"
-        if self.pack not in self.PACK_MODES or (self.pack == "device" and not fused_ok):
-            raise ValueError("pack=%r is not available for input_dims=%d fc1=%d fc2=%d n_actions=%d (modes: %s; device: "
-                             "where the fused kernel is built, see gemm)"
-                             % (pack, self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions, ", ".join(self.PACK_MODES)))
+        dims = (self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions)
+        fused_ok = bool(lib.risvec_sarl_actor_supported(*dims))
+        shape = "input_dims=%d fc1=%d fc2=%d n_actions=%d" % dims
+        self.gemm = choose_mode("gemm", gemm, "fused" if fused_ok else "library", self.GEMM_MODES, fused_ok, shape,
+                                "fused: input_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256}, n_actions <= 96")
+        self.pack = choose_mode("pack", pack, "host", self.PACK_MODES, fused_ok, shape, PACK_RULE)
         self._packed = (None, None)                           # (key, (wstream, scales))
         self._pack_buffers = None                             # pack="device": ((wstream, scales), workspace), at first use
+        self.packs = 0                                        # how often the weight stream was rebuilt
         dev = self.device
         g = torch.Generator(device="cpu").manual_seed(seed)
 
@@ -212,97 +205,19 @@ class BatchedActor:
         self.ln1_w, self.ln1_b = torch.ones(self.fc1_dims, device=dev), torch.zeros(self.fc1_dims, device=dev)
         self.ln2_w, self.ln2_b = torch.ones(self.fc2_dims, device=dev), torch.zeros(self.fc2_dims, device=dev)
 
-    # ------------------------------------------------------------------ weights
-    def state_dict(self) -> dict:
-        """The reference's `ActorNetwork.state_dict()` keys (fc1.* fc2.* bn1.* bn2.* mu.*), CPU copies."""
-        return {k: getattr(self, a).detach().cpu().clone() for k, a in self._SD.items()}
-
-    def load_state_dict(self, sd: Mapping[str, object]) -> None:
-        """Take the weights of a reference `ActorNetwork.state_dict()` as it is (tensors or arrays; `actor` and
-        `target_actor` checkpoints alike).  Load checkpoints with `torch.load(..., weights_only=True)`."""
-        new = {}
-        for k, a in self._SD.items():
-            if k not in sd:
-                raise KeyError("load_state_dict: %r is missing" % k)
-            t = torch.as_tensor(sd[k], dtype=torch.float32)
-            if tuple(t.shape) != tuple(getattr(self, a).shape):
-                raise ValueError("load_state_dict: %s has shape %s, this actor's is %s"
-                                 % (k, tuple(t.shape), tuple(getattr(self, a).shape)))
-            new[a] = t
-        for a, t in new.items():
-            getattr(self, a).copy_(t.to(self.device))
-
-    def share_state_dict(self, sd: Mapping[str, torch.Tensor]) -> None:
-        """Use the learner's own tensors as this actor's weights, by reference (reference key names; typically
-        `agent.actor.state_dict()`): nothing is copied, now or later.  An in-place optimiser step on them is seen through
-        their version counters, and the next `forward` rebuilds the weight stream first -- with pack="device" in two
-        launches.  Tensors must be float32, contiguous, on this actor's device and of this actor's shapes."""
-        new = {}
-        for k, a in self._SD.items():
-            if k not in sd:
-                raise KeyError("share_state_dict: %r is missing" % k)
-            t, shape = sd[k], tuple(getattr(self, a).shape)
-            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device
-                    or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise ValueError("share_state_dict: %s must be a contiguous float32 tensor of shape %s on %s (it is used in "
-                                 "place; load_state_dict copies and converts)" % (k, shape, self.device))
-            new[a] = t.detach()                               # the same storage and version counter
-        for a, t in new.items():
-            setattr(self, a, t)
-
-    def soft_update_from(self, online, tau: float) -> None:
-        """`update_network_parameters` (`ddpg_torch.py:104-130`) for this (target) actor: every weight tensor becomes
-        tau * online + (1 - tau) * own, in place, in one launch, bit for bit what that expression gives on float32
-        tensors.  online: another `BatchedActor` of the same shape, or a mapping under the reference's key names (the
-        learner's `actor.state_dict()`; contiguous float32 tensors of this actor's shapes on this actor's device, read in
-        place).  tau in [0, 1]; tau = 1 is the constructor's hard copy (:35).  The write goes through raw pointers, so the
-        tensors' version counters are NOT advanced: the weight stream is marked stale here and the next `forward`
-        rebuilds it.  A refused argument changes nothing."""
-        tau = polyak_tau(tau, "soft_update_from")
-        pairs = polyak_pairs(self, online, "soft_update_from")
-        soft_update_tensors(pairs, tau, self.device)
-        self.mark_stale()
-
-    def mark_stale(self) -> None:
-        """Have the next `forward` rebuild the weight stream: for writers that do not advance the weights' version
-        counters."""
-        self._packed = (None, self._packed[1])
-
-    def _fused_weights(self):
-        """(wstream, scales) of `risvec_sarl_actor`, rebuilt when a weight tensor is replaced or updated in place."""
-        ws = (self.W1, self.b1, self.ln1_w, self.ln1_b, self.W2, self.Wmu)
-        key = tuple((t.data_ptr(), t._version) for t in ws)
-        if self._packed[0] != key:
-            if self.pack == "device":
-                if self._pack_buffers is None:
-                    g = actor_geom(self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions)
-                    need = int(N.load().risvec_sarl_actor_pack_workspace(self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions))
-                    self._pack_buffers = ((torch.zeros(g.items, g.rows, 64, 8, dtype=torch.float16, device=self.device),
-                                           torch.zeros(3, device=self.device)),
-                                          torch.zeros(need, dtype=torch.uint8, device=self.device))
-                out, workspace = self._pack_buffers
-                self._packed = (key, pack_actor_weights_device(*ws, out=out, workspace=workspace))
-            else:
-                self._packed = (key, pack_actor_weights(*ws))
-        return self._packed[1]
+    def _new_pack_buffers(self):
+        dims = (self.input_dims, self.fc1_dims, self.fc2_dims, self.n_actions)
+        g = actor_geom(*dims)
+        return (stream_pair((g.items, g.rows, 64, 8), 3, self.device, torch.zeros),
+                torch.zeros(int(N.load().risvec_sarl_actor_pack_workspace(*dims)), dtype=torch.uint8, device=self.device))
 
     # ------------------------------------------------------------------ forward
-    def _rows(self, obs) -> int:
-        dev = self.device
-        if (not isinstance(obs, torch.Tensor) or obs.dtype != torch.float32 or obs.device != dev or not obs.is_contiguous()
-                or obs.dim() not in (2, 3) or obs.shape[0] < 1 or obs.numel() != obs.shape[0] * self.input_dims):
-            raise ValueError("obs must be a contiguous float32 tensor [n, %d] or [n, V, %d / V] on %s"
-                             % (self.input_dims, self.input_dims, dev))
-        return int(obs.shape[0])
-
     def forward(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None, logits: Optional[torch.Tensor] = None) -> torch.Tensor:
         """NET:132-141 for every row: obs [n, input_dims] or [n, V, input_dims / V] (the rollout launch's observation, read in
         place) -> mu [n, n_actions] = sigmoid(logits).  `out`: a caller-owned [n, n_actions] tensor written in place
         (the one bound to `bind_sarl_rollout`); `logits`: receives the pre-sigmoid values."""
-        n, dev = self._rows(obs), self.device
-        if out is None:
-            out = torch.empty(n, self.n_actions, device=dev)
-        N.in_place(out, torch.float32, (n, self.n_actions), "forward: out", dev)
+        n, dev = rows_of(obs, self.input_dims, "obs", self.device), self.device
+        out = out_f32(out, (n, self.n_actions), "forward: out", dev)
         N.in_place(logits, torch.float32, (n, self.n_actions), "forward: logits", dev)
         if self.gemm == "library":
             lg = self.logits_torch(obs.view(n, self.input_dims))

@@ -14,13 +14,15 @@ launches each.  Nothing here differentiates: the gradient half of `learn()` stay
 from __future__ import annotations
 
 import math
-from typing import Mapping, NamedTuple, Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _native as N
-from ._wstream import (_WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags, centre_fc1, polyak_pairs, polyak_tau,
-                       soft_update_tensors)
+from ._weights import (PACK_RULE, WeightSet, choose_mode, is_f32, out_f32, pack_out, pack_workspace, polyak_pairs, polyak_tau,
+                       rows_of, soft_update_tensors, stream_pair, td_args, td_select)
+from ._wstream import _WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags, centre_fc1
+
 
 class CriticGeom(NamedTuple):
     """Layout of the weight stream of `risvec_sarl_critic` (include/risvec.h): fragment rows of 1 KiB in four blocks that
@@ -92,7 +94,7 @@ def pack_critic_weights_device(W1, b1, W2, Wav, W3, out=None, workspace=None) ->
     one, except that the float64 row means of the centred fc1 weight are summed in another order."""
     lib = N.load()
     ws = (W1, b1, W2, Wav, W3)
-    if not all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous() and t.device == W1.device for t in ws):
+    if not (isinstance(W1, torch.Tensor) and all(is_f32(t, W1.device) for t in ws)):
         raise ValueError("pack_critic_weights_device: the weights must be contiguous float32 tensors on one device")
     dev = W1.device
     N.require_hip(dev)
@@ -108,16 +110,8 @@ def pack_critic_weights_device(W1, b1, W2, Wav, W3, out=None, workspace=None) ->
     if need == 0:
         raise ValueError("no fused critic kernel for input_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d" % (IN, F1, F2, F3, A))
     g = critic_geom(IN, F1, F2, F3, A)
-    if out is None:
-        out = (torch.empty(g.rows, 64, 8, dtype=torch.float16, device=dev), torch.empty(4, device=dev))
-    stream, scales = out
-    N.in_place(stream, torch.float16, (g.rows, 64, 8), "pack_critic_weights_device: out[0]", dev)
-    N.in_place(scales, torch.float32, (4,), "pack_critic_weights_device: out[1]", dev)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
-            or not workspace.is_contiguous()):
-        raise ValueError("pack_critic_weights_device: workspace must be a contiguous uint8 tensor on %s" % dev)
+    stream, scales = pack_out(out, (g.rows, 64, 8), 4, "pack_critic_weights_device: out", dev)
+    workspace = pack_workspace(workspace, need, "pack_critic_weights_device", dev)
     N.check(lib.risvec_sarl_critic_pack(IN, F1, F2, F3, A, *(t.data_ptr() for t in ws), stream.data_ptr(),
                                         stream.numel() * stream.element_size(), scales.data_ptr(), workspace.data_ptr(),
                                         workspace.numel(), N.stream(dev)))
@@ -139,7 +133,7 @@ def unpack_critic_weights(stream: torch.Tensor, scales: torch.Tensor, input_dims
             "fc3": _unfrags(_from_wave(s[g.fc3:g.rows], g.mt3, 8 * g.mt2), "cd") * sc[3]}
 
 
-class BatchedCritic:
+class BatchedCritic(WeightSet):
     """`CriticNetwork` (NET:9-79) for n rows at once.  `input_dims` is the flattened state width, n_agents x per-agent
     width (NET:19); the output is q [n, 1]."""
 
@@ -153,6 +147,8 @@ class BatchedCritic:
            "bn1.weight": "ln1_w", "bn1.bias": "ln1_b", "bn2.weight": "ln2_w", "bn2.bias": "ln2_b", "bn3.weight": "ln3_w",
            "bn3.bias": "ln3_b", "action_value.weight": "Wav", "action_value.bias": "bav", "q.weight": "Wq", "q.bias": "bq"}
     _PACKED = ("W1", "b1", "W2", "Wav", "W3")                 # what the weight stream is built from
+    _NOUN = "critic"
+    _pack_host, _pack_device = staticmethod(pack_critic_weights), staticmethod(pack_critic_weights_device)
 
     def __init__(self, input_dims: int, n_actions: int, fc1_dims: int = 1024, fc2_dims: int = 512, fc3_dims: int = 256,
                  device="cuda", seed: int = 0, gemm: Optional[str] = None, pack: Optional[str] = None):
@@ -174,16 +170,12 @@ class BatchedCritic:
         if min(dims) < 1:
             raise ValueError("BatchedCritic: every dimension must be >= 1")
         fused_ok = bool(lib.risvec_sarl_critic_supported(*dims))
-        self.gemm = gemm if gemm is not None else ("fused" if fused_ok else "library")
-        if self.gemm not in self.GEMM_MODES or (self.gemm == "fused" and not fused_ok):
-            raise ValueError("gemm=%r is not available for input_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d (modes: %s; fused: "
-                             "input_dims <= 128, fc1 %% 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}, "
-                             "n_actions <= 96)" % ((gemm,) + dims + (", ".join(self.GEMM_MODES),)))
+        shape = "input_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d" % dims
+        self.gemm = choose_mode("gemm", gemm, "fused" if fused_ok else "library", self.GEMM_MODES, fused_ok, shape,
+                                "fused: input_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}, "
+                                "n_actions <= 96")
         self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
-        self.pack = pack if pack is not None else "host"
-        if self.pack not in self.PACK_MODES or (self.pack == "device" and not fused_ok):
-            raise ValueError("pack=%r is not available for input_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d (modes: %s; device: "
-                             "where the fused kernel is built, see gemm)" % ((pack,) + dims + (", ".join(self.PACK_MODES),)))
+        self.pack = choose_mode("pack", pack, "host", self.PACK_MODES, fused_ok, shape, PACK_RULE)
         self._packed = (None, None)                           # (key, (wstream, scales))
         self._pack_buffers = None                             # pack="device": ((wstream, scales), workspace), at first use
         self.packs = 0                                        # how often the weight stream was rebuilt
@@ -202,97 +194,17 @@ class BatchedCritic:
             setattr(self, "ln%d_w" % i, torch.ones(f, device=dev))
             setattr(self, "ln%d_b" % i, torch.zeros(f, device=dev))
 
-    # ------------------------------------------------------------------ weights
-    def state_dict(self) -> dict:
-        """The reference's `CriticNetwork.state_dict()` keys (fc1.* fc2.* fc3.* bn1.* bn2.* bn3.* action_value.* q.*), CPU
-        copies."""
-        return {k: getattr(self, a).detach().cpu().clone() for k, a in self._SD.items()}
-
-    def load_state_dict(self, sd: Mapping[str, object]) -> None:
-        """Take the weights of a reference `CriticNetwork.state_dict()` as it is (tensors or arrays; `critic` and
-        `target_critic` checkpoints alike).  Load checkpoints with `torch.load(..., weights_only=True)`."""
-        new = {}
-        for k, a in self._SD.items():
-            if k not in sd:
-                raise KeyError("load_state_dict: %r is missing" % k)
-            t = torch.as_tensor(sd[k], dtype=torch.float32)
-            if tuple(t.shape) != tuple(getattr(self, a).shape):
-                raise ValueError("load_state_dict: %s has shape %s, this critic's is %s"
-                                 % (k, tuple(t.shape), tuple(getattr(self, a).shape)))
-            new[a] = t
-        for a, t in new.items():
-            getattr(self, a).copy_(t.to(self.device))
-
-    def share_state_dict(self, sd: Mapping[str, torch.Tensor]) -> None:
-        """Use the learner's own tensors as this critic's weights, by reference (reference key names; typically
-        `agent.target_critic.state_dict()`): nothing is copied, now or later.  An in-place update of them is seen through
-        their version counters, and the next call rebuilds the weight stream first.  Tensors must be float32, contiguous,
-        on this critic's device and of this critic's shapes."""
-        new = {}
-        for k, a in self._SD.items():
-            if k not in sd:
-                raise KeyError("share_state_dict: %r is missing" % k)
-            t, shape = sd[k], tuple(getattr(self, a).shape)
-            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device
-                    or not t.is_contiguous() or tuple(t.shape) != shape):
-                raise ValueError("share_state_dict: %s must be a contiguous float32 tensor of shape %s on %s (it is used in "
-                                 "place; load_state_dict copies and converts)" % (k, shape, self.device))
-            new[a] = t.detach()                               # the same storage and version counter
-        for a, t in new.items():
-            setattr(self, a, t)
-
-    def soft_update_from(self, online, tau: float) -> None:
-        """`update_network_parameters` (`ddpg_torch.py:104-130`) for this (target) critic: every weight tensor becomes
-        tau * online + (1 - tau) * own, in place, in one launch, bit for bit what that expression gives on float32
-        tensors.  online: another `BatchedCritic` of the same shape, or a mapping under the reference's key names (the
-        learner's `critic.state_dict()`; contiguous float32 tensors of this critic's shapes on this critic's device, read
-        in place).  tau in [0, 1]; tau = 1 is the constructor's hard copy (:35).  The write goes through raw pointers, so
-        the tensors' version counters are NOT advanced: the weight stream is marked stale here and the next `forward` /
-        `td_target` rebuilds it.  A refused argument changes nothing."""
-        tau = polyak_tau(tau, "soft_update_from")
-        pairs = polyak_pairs(self, online, "soft_update_from")
-        soft_update_tensors(pairs, tau, self.device)
-        self.mark_stale()
-
-    def mark_stale(self) -> None:
-        """Have the next `forward` / `td_target` rebuild the weight stream: for writers that do not advance the weights'
-        version counters."""
-        self._packed = (None, self._packed[1])
-
-    def _fused_weights(self):
-        """(wstream, scales) of `risvec_sarl_critic`, rebuilt when a packed weight tensor is replaced or updated in place,
-        or after `mark_stale` (pack="host": library kernels into new tensors; pack="device": two launches into the
-        buffers of the first rebuild)."""
-        ws = tuple(getattr(self, a) for a in self._PACKED)
-        key = tuple((t.data_ptr(), t._version) for t in ws)
-        if self._packed[0] != key:
-            if self.pack == "device":
-                if self._pack_buffers is None:
-                    dims = (self.input_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims, self.n_actions)
-                    g = critic_geom(*dims)
-                    need = int(N.load().risvec_sarl_critic_pack_workspace(*dims))
-                    self._pack_buffers = ((torch.zeros(g.rows, 64, 8, dtype=torch.float16, device=self.device),
-                                           torch.zeros(4, device=self.device)),
-                                          torch.zeros(need, dtype=torch.uint8, device=self.device))
-                out, workspace = self._pack_buffers
-                self._packed = (key, pack_critic_weights_device(*ws, out=out, workspace=workspace))
-            else:
-                self._packed = (key, pack_critic_weights(*ws))
-            self.packs += 1
-        return self._packed[1]
+    def _new_pack_buffers(self):
+        dims = (self.input_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims, self.n_actions)
+        return (stream_pair((critic_geom(*dims).rows, 64, 8), 4, self.device, torch.zeros),
+                torch.zeros(int(N.load().risvec_sarl_critic_pack_workspace(*dims)), dtype=torch.uint8, device=self.device))
 
     # ------------------------------------------------------------------ forward
     def _rows(self, state, action) -> int:
-        dev = self.device
-        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float32 or state.device != dev
-                or not state.is_contiguous() or state.dim() not in (2, 3) or state.shape[0] < 1
-                or state.numel() != state.shape[0] * self.input_dims):
-            raise ValueError("state must be a contiguous float32 tensor [n, %d] or [n, V, %d / V] on %s"
-                             % (self.input_dims, self.input_dims, dev))
-        n = int(state.shape[0])
+        n = rows_of(state, self.input_dims, "state", self.device)
         if action is None:
-            raise ValueError("action must be a contiguous float32 tensor [n, %d] on %s" % (self.n_actions, dev))
-        N.in_place(action, torch.float32, (n, self.n_actions), "action", dev)
+            raise ValueError("action must be a contiguous float32 tensor [n, %d] on %s" % (self.n_actions, self.device))
+        N.in_place(action, torch.float32, (n, self.n_actions), "action", self.device)
         return n
 
     def _fused(self, n: int) -> bool:
@@ -311,9 +223,7 @@ class BatchedCritic:
         """NET:66-79 for every row: state [n, input_dims] or [n, V, input_dims / V], action [n, n_actions], both read in
         place -> q [n, 1].  `out`: a caller-owned [n, 1] tensor written in place."""
         n, dev = self._rows(state, action), self.device
-        if out is None:
-            out = torch.empty(n, 1, device=dev)
-        N.in_place(out, torch.float32, (n, 1), "forward: out", dev)
+        out = out_f32(out, (n, 1), "forward: out", dev)
         if not self._fused(n):
             return out.copy_(self.q_torch(state.view(n, self.input_dims), action))
         self._launch(n, state, action, None, None, 0.0, out, None)
@@ -328,24 +238,14 @@ class BatchedCritic:
         all read in place; `out`: a caller-owned [n] tensor for y; `q`: a caller-owned [n, 1] tensor that receives
         Q(state_, action_)."""
         n, dev = self._rows(state_, action_), self.device
-        if reward is None:
-            raise ValueError("td_target: reward must be a contiguous float32 tensor of shape (%d,) on %s" % (n, dev))
-        N.in_place(reward, torch.float32, (n,), "td_target: reward", dev)
-        if (not isinstance(done, torch.Tensor) or done.dtype not in (torch.bool, torch.uint8) or done.device != dev
-                or not done.is_contiguous() or tuple(done.shape) != (n,)):
-            raise ValueError("td_target: done must be a contiguous bool or uint8 tensor of shape (%d,) on %s" % (n, dev))
-        if not math.isfinite(float(gamma)):
-            raise ValueError("td_target: gamma must be finite")
-        if out is None:
-            out = torch.empty(n, device=dev)
-        N.in_place(out, torch.float32, (n,), "td_target: out", dev)
+        td_args(reward, done, gamma, n, dev)
+        out = out_f32(out, (n,), "td_target: out", dev)
         N.in_place(q, torch.float32, (n, 1), "td_target: q", dev)
         if not self._fused(n):
             qv = self.q_torch(state_.view(n, self.input_dims), action_)
             if q is not None:
                 q.copy_(qv)
-            return out.copy_(torch.where(done.view(torch.bool) if done.dtype == torch.uint8 else done, reward,
-                                         reward + float(gamma) * qv.view(n)))
+            return td_select(out, reward, done, gamma, qv.view(n))
         d8 = done.view(torch.uint8) if done.dtype == torch.bool else done
         self._launch(n, state_, action_, reward, d8, gamma, q, out)
         return out

@@ -23,8 +23,9 @@ from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _native as N
-from ._wstream import (_WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags, polyak_pairs, polyak_tau,
-                       soft_update_tensors)
+from ._weights import (PACK_RULE, WeightSet, choose_mode, is_f32, load_weight_sets, out_f32, pack_out, pack_workspace, polyak_pairs,
+                       polyak_tau, rows_of, share_weight_sets, soft_update_tensors, stream_pair, td_args, td_select)
+from ._wstream import _WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags
 
 
 class MarlCriticGeom(NamedTuple):
@@ -101,10 +102,8 @@ def pack_marl_critic_weights_device(weights: Sequence, out: Optional[Sequence] =
     if n_nets not in (1, 2) or any(len(ws) != 3 for ws in weights):
         raise ValueError("%s: weights is a sequence of 1 or 2 triples (W1, W2, W3), got %d nets" % (what, n_nets))
     flat = [t for ws in weights for t in ws]
-    if not all(isinstance(t, torch.Tensor) for t in flat):
-        raise ValueError("%s: the weights must be contiguous float32 tensors on one device" % what)
-    dev = flat[0].device
-    if not all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in flat):
+    dev = getattr(flat[0], "device", None)
+    if not all(is_f32(t, dev) for t in flat):
         raise ValueError("%s: the weights must be contiguous float32 tensors on one device" % what)
     if dev.type != "cuda":
         raise ValueError("%s: the weights must be on a HIP device (they are read in place; pack_marl_critic_weights runs "
@@ -125,24 +124,14 @@ def pack_marl_critic_weights_device(weights: Sequence, out: Optional[Sequence] =
     if need == 0:
         raise ValueError("no fused twin-critic kernel for state_dims + action_dims=%d fc1=%d fc2=%d fc3=%d" % (IN, F1, F2, F3))
     g = marl_critic_geom(*dims)
-    if out is None:
-        out = [(torch.empty(g.rows, 64, 8, dtype=torch.float16, device=dev), torch.empty(3, device=dev)) for _ in range(n_nets)]
     try:
-        out = [tuple(o) for o in out]
+        out = [None] * n_nets if out is None else [tuple(o) for o in out]
     except TypeError:
         raise ValueError("%s: out is a sequence of %d pairs (wstream, scales)" % (what, n_nets)) from None
-    if len(out) != n_nets or any(len(o) != 2 for o in out):
+    if len(out) != n_nets or any(o is not None and len(o) != 2 for o in out):
         raise ValueError("%s: out is a sequence of %d pairs (wstream, scales)" % (what, n_nets))
-    for c, (stream, scales) in enumerate(out):
-        if stream is None or scales is None:
-            raise ValueError("%s: out is a sequence of %d pairs (wstream, scales)" % (what, n_nets))
-        N.in_place(stream, torch.float16, (g.rows, 64, 8), "%s: out[%d][0]" % (what, c), dev)
-        N.in_place(scales, torch.float32, (3,), "%s: out[%d][1]" % (what, c), dev)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev
-            or not workspace.is_contiguous()):
-        raise ValueError("%s: workspace must be a contiguous uint8 tensor on %s" % (what, dev))
+    out = [pack_out(o, (g.rows, 64, 8), 3, "%s: out[%d]" % (what, c), dev) for c, o in enumerate(out)]
+    workspace = pack_workspace(workspace, need, what, dev)
     nets = (N.RisVecMarlCriticPackNet * n_nets)()
     for c, (ws, (stream, scales)) in enumerate(zip(weights, out)):
         nets[c] = N.RisVecMarlCriticPackNet(ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), stream.data_ptr(),
@@ -164,17 +153,21 @@ def _unpack(stream: torch.Tensor, scales: torch.Tensor, state_dims: int, action_
             "fc3": _unfrags(_from_wave(s[g.fc3:g.rows], g.mt3, 8 * g.mt2), "cd") * sc[2]}
 
 
-class _Net:
-    """One `CriticNetwork`'s weights (NET:29-32) under the attribute names `polyak_pairs` walks."""
+class _Net(WeightSet):
+    """One `CriticNetwork`'s weights (NET:29-32) and weight stream; `BatchedTwinCritic` rebuilds the stale streams of its
+    nets together."""
     _WEIGHTS = ("W1", "b1", "W2", "b2", "W3", "b3", "Wq", "bq")
     _SD = {"fc1.weight": "W1", "fc1.bias": "b1", "fc2.weight": "W2", "fc2.bias": "b2", "fc3.weight": "W3", "fc3.bias": "b3",
            "q.weight": "Wq", "q.bias": "bq"}
     _PACKED = ("W1", "W2", "W3")                              # what the weight stream is built from
+    _NOUN = "critic"
 
     def __init__(self, device):
         self.device = device
-        self.packed = (None, None)                            # (key, (wstream, scales))
-        self.pack_buffers = None                              # pack="device": (wstream, scales), at first use
+        self._packed = (None, None)                           # (key, (wstream, scales))
+        self._pack_buffers = None                             # pack="device": (wstream, scales), at first use
+
+    packed = property(lambda self: self._packed)              # the cache slot under the name it had before `WeightSet`
 
 
 class BatchedTwinCritic:
@@ -210,11 +203,9 @@ class BatchedTwinCritic:
         if self.n_nets not in (1, 2):
             raise ValueError("BatchedTwinCritic: n_nets must be 1 or 2")
         fused_ok = bool(lib.risvec_marl_critic_supported(*dims))
-        self.gemm = gemm if gemm is not None else ("fused" if fused_ok else "library")
-        if self.gemm not in self.GEMM_MODES or (self.gemm == "fused" and not fused_ok):
-            raise ValueError("gemm=%r is not available for state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (modes: %s; fused: "
-                             "state_dims + action_dims <= 128, fc1 %% 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, "
-                             "256})" % ((gemm,) + dims + (", ".join(self.GEMM_MODES),)))
+        self.gemm = choose_mode("gemm", gemm, "fused" if fused_ok else "library", self.GEMM_MODES, fused_ok, self._shape(),
+                                "fused: state_dims + action_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in "
+                                "{128, 256}")
         self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
         self._fused_ok = fused_ok
         self._pack = "host"                                   # see `pack`
@@ -236,6 +227,10 @@ class BatchedTwinCritic:
                 setattr(net, b, uni(fan_out, r=r))
             self.nets.append(net)
 
+    def _shape(self) -> str:
+        return "state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d" % (self.state_dims, self.action_dims, self.fc1_dims,
+                                                                      self.fc2_dims, self.fc3_dims)
+
     @property
     def pack(self) -> str:
         """How the fused kernel's weight streams are rebuilt after a weight update.  "host" (the default):
@@ -247,59 +242,31 @@ class BatchedTwinCritic:
 
     @pack.setter
     def pack(self, mode) -> None:
-        if mode not in self.PACK_MODES or (mode == "device" and not self._fused_ok):
-            raise ValueError("pack=%r is not available for state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (modes: %s; device: "
-                             "where the fused kernel is built, see gemm)"
-                             % (mode, self.state_dims, self.action_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims,
-                                ", ".join(self.PACK_MODES)))
-        if mode != self._pack:
+        if choose_mode("pack", mode, None, self.PACK_MODES, self._fused_ok, self._shape(), PACK_RULE) != self._pack:
             self._pack = mode
             self.mark_stale()
 
     # ------------------------------------------------------------------ weights
     def state_dict(self) -> list:
         """One dict per net under the reference's `CriticNetwork.state_dict()` keys (fc1.* fc2.* fc3.* q.*), CPU copies."""
-        return [{k: getattr(net, a).detach().cpu().clone() for k, a in self._SD.items()} for net in self.nets]
+        return [net.state_dict() for net in self.nets]
 
-    def _each(self, sds, what: str):
+    def _each(self, sds, what: str) -> list:
         if len(sds) != self.n_nets:
             raise ValueError("%s: %d weight sets given, this critic has %d nets" % (what, len(sds), self.n_nets))
-        for c, sd in enumerate(sds):
-            for k in self._SD:
-                if k not in sd:
-                    raise KeyError("%s: %r is missing in net %d" % (what, k, c + 1))
-        return zip(self.nets, sds)
+        return [(net, sd, "%s: net %d" % (what, c + 1)) for c, (net, sd) in enumerate(zip(self.nets, sds))]
 
     def load_state_dict(self, *sds: Mapping[str, object]) -> None:
         """Take the weights of `global_target_critic1.state_dict()`, `global_target_critic2.state_dict()` as they are
         (tensors or arrays; one mapping per net).  Load checkpoints with `torch.load(..., weights_only=True)`."""
-        new = []
-        for net, sd in self._each(sds, "load_state_dict"):
-            for k, a in self._SD.items():
-                t = torch.as_tensor(sd[k], dtype=torch.float32)
-                if tuple(t.shape) != tuple(getattr(net, a).shape):
-                    raise ValueError("load_state_dict: %s has shape %s, this critic's is %s"
-                                     % (k, tuple(t.shape), tuple(getattr(net, a).shape)))
-                new.append((net, a, t))
-        for net, a, t in new:
-            getattr(net, a).copy_(t.to(self.device))
+        load_weight_sets(self._each(sds, "load_state_dict"))
 
     def share_state_dict(self, *sds: Mapping[str, torch.Tensor]) -> None:
         """Use the learner's own tensors as the weights, by reference (one mapping per net under the reference's key
         names): nothing is copied, now or later.  An in-place update of them is seen through their version counters, and
         the next call rebuilds that net's weight stream first.  Tensors must be float32, contiguous, on this critic's
         device and of this critic's shapes."""
-        new = []
-        for net, sd in self._each(sds, "share_state_dict"):
-            for k, a in self._SD.items():
-                t, shape = sd[k], tuple(getattr(net, a).shape)
-                if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device
-                        or not t.is_contiguous() or tuple(t.shape) != shape):
-                    raise ValueError("share_state_dict: %s must be a contiguous float32 tensor of shape %s on %s (it is used "
-                                     "in place; load_state_dict copies and converts)" % (k, shape, self.device))
-                new.append((net, a, t.detach()))              # the same storage and version counter
-        for net, a, t in new:
-            setattr(net, a, t)
+        share_weight_sets(self._each(sds, "share_state_dict"))
 
     def soft_update_from(self, *online, tau: float) -> None:
         """`update_global_network_parameters` (`global_sac_critic.py:394-400`) for every net in ONE launch: each of the 8
@@ -312,11 +279,7 @@ class BatchedTwinCritic:
         tau = polyak_tau(tau, "soft_update_from")
         if len(online) == 1 and isinstance(online[0], BatchedTwinCritic):
             online = tuple(online[0].nets)
-        if len(online) != self.n_nets:
-            raise ValueError("soft_update_from: %d online weight sets given, this critic has %d nets" % (len(online), self.n_nets))
-        pairs = []
-        for c, (net, on) in enumerate(zip(self.nets, online)):
-            pairs += polyak_pairs(net, on, "soft_update_from: net %d" % (c + 1))
+        pairs = [p for net, on, what in self._each(online, "soft_update_from") for p in polyak_pairs(net, on, what)]
         soft_update_tensors(pairs, tau, self.device)
         self.mark_stale()
 
@@ -324,7 +287,7 @@ class BatchedTwinCritic:
         """Have the next `forward` / `td_target` rebuild the weight streams: for writers that do not advance the weights'
         version counters."""
         for net in self.nets:
-            net.packed = (None, net.packed[1])
+            net.mark_stale()
 
     def _fused_weights(self) -> list:
         """(wstream, scales) of every net; a net's are rebuilt when one of its packed weight tensors is replaced or updated
@@ -332,10 +295,9 @@ class BatchedTwinCritic:
         stale nets together in two launches, into the buffers of their first rebuild)."""
         stale = []
         for net in self.nets:
-            ws = tuple(getattr(net, a) for a in net._PACKED)
-            key = tuple((t.data_ptr(), t._version) for t in ws)
-            if net.packed[0] != key:
-                stale.append((net, key, ws))
+            s = net._stale()
+            if s is not None:
+                stale.append((net,) + s)
         if stale and self._pack == "device":
             dev = self.device
             if self._pack_workspace is None:
@@ -344,33 +306,22 @@ class BatchedTwinCritic:
                 self._pack_workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
             rows = marl_critic_geom(self.state_dims, self.action_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims).rows
             for net, _, _ in stale:
-                if net.pack_buffers is None:
-                    net.pack_buffers = (torch.zeros(rows, 64, 8, dtype=torch.float16, device=dev), torch.zeros(3, device=dev))
-            pack_marl_critic_weights_device([ws for _, _, ws in stale], out=[net.pack_buffers for net, _, _ in stale],
+                if net._pack_buffers is None:
+                    net._pack_buffers = stream_pair((rows, 64, 8), 3, dev, torch.zeros)
+            pack_marl_critic_weights_device([ws for _, _, ws in stale], out=[net._pack_buffers for net, _, _ in stale],
                                             workspace=self._pack_workspace)
             for net, key, _ in stale:
-                net.packed = (key, net.pack_buffers)
+                net._packed = (key, net._pack_buffers)
         else:
             for net, key, ws in stale:
-                net.packed = (key, pack_marl_critic_weights(*ws))
+                net._packed = (key, pack_marl_critic_weights(*ws))
         self.packs += len(stale)
-        return [net.packed[1] for net in self.nets]
+        return [net._packed[1] for net in self.nets]
 
     # ------------------------------------------------------------------ forward
     def _rows(self, state, action) -> int:
-        dev = self.device
-        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float32 or state.device != dev
-                or not state.is_contiguous() or state.dim() not in (2, 3) or state.shape[0] < 1
-                or state.numel() != state.shape[0] * self.state_dims):
-            raise ValueError("state must be a contiguous float32 tensor [n, %d] or [n, V, %d / V] on %s"
-                             % (self.state_dims, self.state_dims, dev))
-        n = int(state.shape[0])
-        if (not isinstance(action, torch.Tensor) or action.dtype != torch.float32 or action.device != dev
-                or not action.is_contiguous() or action.dim() not in (2, 3) or action.shape[0] != n
-                or action.numel() != n * self.action_dims):
-            raise ValueError("action must be a contiguous float32 tensor [%d, %d] or [%d, V, %d / V] on %s"
-                             % (n, self.action_dims, n, self.action_dims, dev))
-        return n
+        n = rows_of(state, self.state_dims, "state", self.device)
+        return rows_of(action, self.action_dims, "action", self.device, n)
 
     def _q_outs(self, q, n: int, what: str):
         """The caller's q buffers as a tuple of n_nets tensors [n, 1] (or None)."""
@@ -433,30 +384,19 @@ class BatchedTwinCritic:
         what would have to be copied is refused.  `out`: a caller-owned [n] tensor for y; `q`: caller-owned [n, 1]
         tensors (a pair; one when n_nets == 1) that receive Q_c(state_, action_)."""
         n, dev = self._rows(state_, action_), self.device
-        if reward is None:
-            raise ValueError("td_target: reward must be a contiguous float32 tensor of shape (%d,) on %s" % (n, dev))
-        N.in_place(reward, torch.float32, (n,), "td_target: reward", dev)
-        if (not isinstance(done, torch.Tensor) or done.dtype not in (torch.bool, torch.uint8) or done.device != dev
-                or not done.is_contiguous() or tuple(done.shape) != (n,)):
-            raise ValueError("td_target: done must be a contiguous bool or uint8 tensor of shape (%d,) on %s" % (n, dev))
-        if not math.isfinite(float(gamma)):
-            raise ValueError("td_target: gamma must be finite")
+        td_args(reward, done, gamma, n, dev)
         for name, t in (("logp_power", logp_power), ("logp_intent", logp_intent)):
-            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev
-                                  or not t.is_contiguous() or tuple(t.shape) not in ((n,), (n, 1))):
+            if t is not None and not (is_f32(t, dev, (n,)) or is_f32(t, dev, (n, 1))):
                 raise ValueError("td_target: %s must be a contiguous float32 tensor of shape (%d,) or (%d, 1) on %s"
                                  % (name, n, n, dev))
         if logp_power is not None or logp_intent is not None:
             if coef is None:
                 raise ValueError("td_target: logp_power / logp_intent need coef, a float32 tensor of 2 values on %s" % dev)
-            if (not isinstance(coef, torch.Tensor) or coef.dtype != torch.float32 or coef.device != dev
-                    or not coef.is_contiguous() or coef.numel() != 2):
+            if not is_f32(coef, dev) or coef.numel() != 2:
                 raise ValueError("td_target: coef must be a contiguous float32 tensor of 2 values on %s" % dev)
         else:
             coef = None
-        if out is None:
-            out = torch.empty(n, device=dev)
-        N.in_place(out, torch.float32, (n,), "td_target: out", dev)
+        out = out_f32(out, (n,), "td_target: out", dev)
         qs = self._q_outs(q, n, "td_target: q")
         if not self._fused(n):
             qv = self.q_torch(state_.view(n, self.state_dims), action_.view(n, self.action_dims))
@@ -470,8 +410,7 @@ class BatchedTwinCritic:
                 m = m - coef.view(2)[0] * logp_power.view(n)
             elif logp_intent is not None:
                 m = m - coef.view(2)[1] * logp_intent.view(n)
-            return out.copy_(torch.where(done.view(torch.bool) if done.dtype == torch.uint8 else done, reward,
-                                         reward + float(gamma) * m))
+            return td_select(out, reward, done, gamma, m)
         d8 = done.view(torch.uint8) if done.dtype == torch.bool else done
         self._launch(n, state_, action_, reward, d8, gamma, coef, logp_power, logp_intent, qs, out)
         return out

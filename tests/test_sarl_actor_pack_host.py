@@ -78,33 +78,3 @@ def test_python_surface():
         z = torch.zeros
         with pytest.raises(RuntimeError):
             ACT.pack_actor_weights_device(z(64, 21), z(64), z(64), z(64), z(128, 64), z(6, 128))
-
-
-def test_share_state_dict_takes_tensors_by_reference_or_refuses():
-    """Built without a device, as test_load_state_dict_rejects_a_wrong_shape does: the checks come before any use."""
-    a = ACT.BatchedActor.__new__(ACT.BatchedActor)
-    a.device = torch.device("cpu")
-    dims = dict(W1=(96, 80), b1=(96,), ln1_w=(96,), ln1_b=(96,), W2=(128, 96), b2=(128,), ln2_w=(128,), ln2_b=(128,),
-                Wmu=(56, 128), bmu=(56,))
-    for k, s in dims.items():
-        setattr(a, k, torch.zeros(*s))
-    net = {k: torch.nn.Parameter(torch.ones(dims[v])) for k, v in ACT.BatchedActor._SD.items()}   # a learner's parameters
-    sd = {k: v.detach() for k, v in net.items()}                                                   # what state_dict() returns
-    a.share_state_dict(sd)
-    for k, v in ACT.BatchedActor._SD.items():
-        assert getattr(a, v).data_ptr() == net[k].data_ptr() and not getattr(a, v).requires_grad
-    before = a.W2._version
-    with torch.no_grad():
-        net["fc2.weight"].add_(1.0)                           # an optimiser step: in place, under no_grad
-    assert a.W2._version > before and float(a.W2[0, 0]) == 2.0
-    kept = a.W2
-    for k, bad in (("fc2.weight", torch.ones(96, 128)), ("fc1.bias", torch.ones(96, dtype=torch.float64)),
-                   ("mu.weight", torch.ones(128, 56).T), ("bn1.weight", [1.0] * 96)):
-        assert k != "mu.weight" or (tuple(bad.shape) == (56, 128) and not bad.is_contiguous())
-        with pytest.raises(ValueError):
-            a.share_state_dict({**sd, k: bad})
-    assert a.W2 is kept                                       # a refused dict changes nothing
-    short = dict(sd)
-    del short["mu.bias"]
-    with pytest.raises(KeyError):
-        a.share_state_dict(short)
