@@ -933,6 +933,39 @@ size_t risvec_marl_critic_pack_workspace(int32_t state_dims, int32_t action_dims
 int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
                             const RisVecMarlCriticPackNet *nets, void *workspace, size_t workspace_bytes,
                             risvec_stream_t stream);
+/* Every agent's local twin target critics and local TD target of the multi-agent (SAC) learner (Agent.local_learn,
+ * Simulation-MARL-BCD/sac_agent.py:263-284, called once per agent by global_sac_critic.py:373-392) in ONE launch for n_rows
+ * rows and n_agents agents; grid (ceil(n_rows / 32), n_agents).  Agent j has n_nets in {1, 2} CriticNetworks of one shape
+ * on [obs_j (state_dims) | action_j (action_dims)], nets[j n_nets + c] = its net c, each prepared exactly as a net of
+ * risvec_marl_critic at (state_dims, action_dims) -- the same weight stream, built by the same pack -- and walked by the
+ * same code:
+ *     x   = [obs[row, j, 0:state_dims] | action_j]
+ *     action_j = action[row, j, 0:action_dims]                               explicit form: `action` given
+ *              = [onehot(idx) (n_agents) | power[row, j, 0:2]]               from the policy: `heads` and `power` given
+ *         idx  = the FIRST maximum of heads[j, row, 4 + i], i < n_agents, after entry i == j is REPLACED by FLT_MAX / -2
+ *                (sac_agent.py:270-272; it still wins where every other logit is lower; the lowest index wins a tie)
+ *     q_c = the net's forward as in risvec_marl_critic;  m = n_nets == 2 ? min(q_1, q_2) : q_1
+ *     t   = m - (coef[0] logp_power[row, j] + coef[1] logp_intent[row, j])   a term whose logp pointer is NULL is absent
+ *     y[j, row] = reward[row, j] + ((1 - done[row]) gamma) t                 a PRODUCT, not a select, every operation
+ *                 rounded on its own: a done row gives reward exactly for a finite t and NaN for an infinite one (:284)
+ * obs [n_rows, n_agents, state_dims], action [n_rows, n_agents, action_dims], heads [n_agents, n_rows, 4 + n_agents] (the
+ * policy's mu, log_std, intent logits), power [n_rows, n_agents, 2], reward, logp_power, logp_intent [n_rows, n_agents]
+ * float32, done [n_rows] uint8 (0 / 1), coef [2] float32 ON THE DEVICE; done and coef are shared by the agents.  All are
+ * read in place; the per-agent input never exists in memory.  q1, q2, y [n_agents, n_rows] are each optional (NULL: not
+ * written), at least one must be given.  Exactly one of action / heads is given; heads needs power and action_dims ==
+ * n_agents + 2; q2 needs n_nets == 2; y needs reward and done; a logp pointer needs coef and y.  nets is a HOST array of
+ * n_agents * n_nets descriptors, copied into the kernel's argument block.  One launch on `stream`, nothing else.
+ * Built for 1 <= n_agents <= 16 and the shapes of risvec_marl_critic at (state_dims, action_dims)
+ * (risvec_local_critics_supported, host only); other shapes return RISVEC_ERR_UNSUPPORTED.  Every other argument error
+ * returns RISVEC_ERR_ARG; all are reported before anything is launched and without touching a device.  NaN logits are not
+ * supported. */
+int risvec_local_critics_supported(int32_t n_agents, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                                   int32_t fc3);
+int risvec_local_critics(int32_t n_rows, int32_t n_agents, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                         int32_t fc3, int32_t n_nets, const RisVecMarlCriticNet *nets, const float *obs, const float *action,
+                         const float *heads, const float *power, const float *reward, const uint8_t *done, float gamma,
+                         const float *coef, const float *logp_power, const float *logp_intent, float *q1, float *q2, float *y,
+                         risvec_stream_t stream);
 /* The Polyak blend of update_network_parameters (Simulation-SARL/ddpg_torch.py:104-130) for n_tensors tensors in ONE
  * launch, in place:
  *     target[i][e] = fl32( fl32(tau * online[i][e]) + fl32(one_minus_tau * target[i][e]) )

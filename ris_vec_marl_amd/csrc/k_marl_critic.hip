@@ -20,25 +20,19 @@
 // and every wavefront reads them back as B operands with one ds_read_b128 per fragment.  The workgroup walks the nets
 // one after the other, keeps q_1 in its s_red slot and finishes with the epilogue.
 //
+// The net walk (the fc1 group walk, fc2, fc3, the q dot product, the s_red reduction) and the input-fragment store are
+// risvec_critic_walk.hpp's, instantiated here and by k_local_critics.hip.
+//
 // Every barrier sits under wave-uniform control flow: all loop bounds and the net count come from kernel arguments,
 // template parameters and the wavefront index.  Rows at or beyond n_rows are computed on row 0's input and never stored.
 // No global address depends on loaded data; every weight prefetch index is clamped to the last fragment of its block.
+#include "risvec_critic_walk.hpp"
 #include "risvec_launch.hpp"
 #include "risvec_mfma.hpp"
 #include "risvec_step.hpp"
 
 namespace risvec {
 namespace {
-
-struct MarlNetPtrs {
-    const uint4* ws;               // the weight stream: fragment rows of 64 x 16 bytes
-    const float* scales;           // [3] undo the fc1, fc2 and fc3 weight scalings
-    const float* b1;               // [F1]
-    const float* b2;               // [F2]
-    const float* b3;               // [F3]
-    const float* qw;               // [F3]
-    const float* qb;               // [1]
-};
 
 struct MarlCriticArgs {
     long long n_rows;
@@ -56,10 +50,6 @@ struct MarlCriticArgs {
     float* q2;                     // [n_rows] or NULL
     float* y;                      // [n_rows] or NULL
 };
-
-constexpr int kMcBlock = 256;        // 4 wavefronts = 1 per SIMD, all on the same 32 rows
-constexpr int kMcWaves = kCriticWaves;
-constexpr int kRedSlots = 2;
 
 template <int MT2, int MT3>
 __global__ void __launch_bounds__(kMcBlock)
@@ -89,93 +79,13 @@ k_marl_critic(MarlCriticArgs A) {
                 const int k = 16 * s + 8 * hh + j;
                 v[j] = k < S ? ps[k] : (k < W ? pa[k - S] : 0.0f);
             }
-            half8_t hi, lo;
-            split16(v, hi, lo);
-            s_in[(2 * s) * kWave + l] = __builtin_bit_cast(uint4, hi);
-            s_in[(2 * s + 1) * kWave + l] = __builtin_bit_cast(uint4, lo);
+            put_input(s_in, s, l, v);
         }
     }
     __syncthreads();
 
-    // One net: fc1 -> s_h, fc2 -> s_h, fc3 and the q dot product -> s_red[slot].  Called under wave-uniform control flow;
-    // ends on a barrier, after which s_h is free again and s_red[slot] is complete.
-    auto run_net = [&](const MarlNetPtrs& P, int slot) {
-        const float u1 = P.scales[0], u2 = P.scales[1], u3 = P.scales[2];
-        // ---- fc1, groups wave, wave + 4, .. (the group walk is the twin of k_sarl_critic.hip's; keep the two in step): bias,
-        // ReLU, and the split fragments of the group's 32 features go to LDS
-        const int ngw = NG > wave ? (NG - wave + kMcWaves - 1) / kMcWaves : 0;
-        if (ngw > 0) {                                        // wave-uniform; no barrier inside
-            const int nst = ngw * KS;
-            const uint4* w1 = P.ws + L.fc1 * kWave + lane;
-            half8_t ah[kAhead], al[kAhead];
-            int fg = wave, fs = 0;                            // (group, k-step) of the next fetch
-            auto fetch = [&](int i) {
-                const uint4* p = w1 + (size_t)(fg * KS + fs) * (2 * kWave);
-                ah[i] = ld_frag(p);
-                al[i] = ld_frag(p + kWave);
-                if (fs + 1 < KS) ++fs;
-                else if (fg + kMcWaves < NG) { fg += kMcWaves; fs = 0; }    // else: stay on the last fragment
-            };
-#pragma unroll
-            for (int i = 0; i < kAhead; ++i) fetch(i);
-            f32x16_t d;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) d[q] = 0.0f;
-            int g = wave, s = 0;
-            for (int i0 = 0; i0 < nst; i0 += kAhead) {
-#pragma unroll
-                for (int i = 0; i < kAhead; ++i) {
-                    if (i0 + i < nst) {
-                        const half8_t bh = ld_frag(s_in + (2 * s) * kWave + lane), bl = ld_frag(s_in + (2 * s + 1) * kWave + lane);
-                        d = mfma3(ah[i], al[i], bh, bl, d);
-                        fetch(i);
-                        if (++s == KS) {
-                            put_tile(s_h, g, bias_relu(d, u1, tile_of(P.b1, 32 * g, h)), lane);
-#pragma unroll
-                            for (int q = 0; q < 16; ++q) d[q] = 0.0f;
-                            s = 0;
-                            g += kMcWaves;
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-
-        // ---- fc2: output tiles [wave MT2, (wave + 1) MT2) over all 2 NG k-steps
-        f32x16_t acc[MT2];
-#pragma unroll
-        for (int m = 0; m < MT2; ++m)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[m][q] = 0.0f;
-        gemm_tiles<MT2>(acc, P.ws + (L.fc2 + (long long)wave * (2 * NG) * MT2 * 2) * kWave, s_h, 2 * NG, lane);
-        __syncthreads();                                      // every wavefront is past its fc2 MFMAs: s_h is free
-#pragma unroll
-        for (int m = 0; m < MT2; ++m) {
-            const int t = wave * MT2 + m;
-            put_tile(s_h, t, bias_relu(acc[m], u2, tile_of(P.b2, 32 * t, h)), lane);
-        }
-        __syncthreads();
-
-        // ---- fc3 + ReLU, then the 1-wide q layer as a dot product in registers
-        f32x16_t a3[MT3];
-#pragma unroll
-        for (int m = 0; m < MT3; ++m)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) a3[m][q] = 0.0f;
-        gemm_tiles<MT3>(a3, P.ws + (L.fc3 + (long long)wave * K3 * MT3 * 2) * kWave, s_h, K3, lane);
-        f32x16_t qs;
-#pragma unroll
-        for (int m = 0; m < MT3; ++m) {
-            const int f0 = 32 * (wave * MT3 + m);
-            const f32x16_t p = bias_relu(a3[m], u3, tile_of(P.b3, f0, h)) * tile_of(P.qw, f0, h);
-            qs = m == 0 ? p : qs + p;
-        }
-        float qp = sum16(qs);
-        qp += __shfl_xor(qp, 32, kWave);
-        if (h == 0) s_red[(slot * kMcWaves + wave) * 32 + r] = qp;
-        __syncthreads();                                      // every wavefront is past its fc3 MFMAs: s_h is free
-    };
+    // the net walk of risvec_critic_walk.hpp; called under wave-uniform control flow, ends on a barrier
+    auto run_net = [&](const MarlNetPtrs& P, int slot) { marl_run_net<MT2, MT3>(P, slot, s_in, s_h, s_red, L, KS, NG, wave, lane); };
     run_net(A.net[0], 0);
     const bool twin = A.n_nets == 2;                          // a kernel argument: uniform over the grid
     if (twin) run_net(A.net[1], 1);
@@ -183,10 +93,7 @@ k_marl_critic(MarlCriticArgs A) {
     if (wave == 0 && h == 0) {
         const long long e = e0 + r;
         if (e < A.n_rows) {
-            auto red = [&](int slot) {
-                const float* p = s_red + slot * kMcWaves * 32 + r;
-                return ((p[0] + p[32]) + p[64]) + p[96];
-            };
+            auto red = [&](int slot) { return marl_red(s_red, slot, r); };
             const float qv1 = red(0) + A.net[0].qb[0];
             float m = qv1;
             if (A.q1) A.q1[e] = qv1;
@@ -212,9 +119,7 @@ k_marl_critic(MarlCriticArgs A) {
 
 template <int MT2, int MT3>
 hipError_t launch_marl(const MarlCriticArgs& a, hipStream_t st) {
-    const int hsteps = std::max(2 * a.NG, 8 * MT2);
-    const size_t lds = (size_t)(a.KS + hsteps) * 2 * kWave * sizeof(uint4) + (size_t)kRedSlots * kMcWaves * 32 * sizeof(float);
-    return launch_dynamic_lds(k_marl_critic<MT2, MT3>, dim3((unsigned)((a.n_rows + 31) / 32)), dim3(kMcBlock), lds, st, a);
+    return launch_dynamic_lds(k_marl_critic<MT2, MT3>, dim3((unsigned)((a.n_rows + 31) / 32)), dim3(kMcBlock), marl_walk_lds_bytes(a.KS, a.NG, MT2), st, a);
 }
 
 template <int MT2>

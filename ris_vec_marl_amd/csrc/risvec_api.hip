@@ -1176,6 +1176,58 @@ int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1
                                                       (hipStream_t)stream));
 }
 
+int risvec_local_critics_supported(int32_t n_agents, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                                   int32_t fc3) {
+    return risvec::local_critics_supported(n_agents, state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;
+}
+
+int risvec_local_critics(int32_t n_rows, int32_t n_agents, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                         int32_t fc3, int32_t n_nets, const RisVecMarlCriticNet* nets, const float* obs, const float* action,
+                         const float* heads, const float* power, const float* reward, const uint8_t* done, float gamma,
+                         const float* coef, const float* logp_power, const float* logp_intent, float* q1, float* q2, float* y,
+                         risvec_stream_t stream) {
+    const char* fn = "risvec_local_critics";
+    if (n_rows < 1) return fail(RISVEC_ERR_ARG, "%s: n_rows=%d must be >= 1", fn, n_rows);
+    if (n_nets < 1 || n_nets > 2) return fail(RISVEC_ERR_ARG, "%s: n_nets=%d must be 1 or 2", fn, n_nets);
+    if (!risvec::local_critics_supported(n_agents, state_dims, action_dims, fc1, fc2, fc3))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: n_agents=%d state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (built for 1 <= "
+                    "n_agents <= %d, state_dims + action_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, "
+                    "fc3 = 128 or 256; use library kernels elsewhere)", fn, n_agents, state_dims, action_dims, fc1, fc2, fc3,
+                    risvec::kLocalCriticsMaxAgents);
+    if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
+    const long long need = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+    for (int c = 0; c < n_agents * n_nets; ++c) {
+        const RisVecMarlCriticNet& n = nets[c];
+        if (n.wstream_bytes != need)
+            return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream_bytes=%lld, this shape's weight stream has %lld", fn, c,
+                        (long long)n.wstream_bytes, need);
+        const struct { const void* p; const char* name; } ptrs[] = {{n.wstream, "wstream"}, {n.scales, "scales"}, {n.b1, "b1"},
+                                                                    {n.b2, "b2"}, {n.b3, "b3"}, {n.qw, "qw"}};
+        for (const auto& w : ptrs) {
+            if (!w.p) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is NULL", fn, c, w.name);
+            if (!aligned16(w.p)) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is not 16-byte aligned", fn, c, w.name);
+        }
+        if (!n.qb) return fail(RISVEC_ERR_ARG, "%s: nets[%d].qb is NULL", fn, c);
+    }
+    if (!obs) return fail(RISVEC_ERR_ARG, "%s: obs is NULL", fn);
+    if (action && heads) return fail(RISVEC_ERR_ARG, "%s: action and heads are both given (one of them builds the input)", fn);
+    if (!action && !heads) return fail(RISVEC_ERR_ARG, "%s: action and heads are both NULL", fn);
+    if (heads && !power) return fail(RISVEC_ERR_ARG, "%s: heads needs power", fn);
+    if (power && !heads) return fail(RISVEC_ERR_ARG, "%s: power needs heads", fn);
+    if (heads && action_dims != n_agents + 2)
+        return fail(RISVEC_ERR_ARG, "%s: heads needs action_dims == n_agents + 2, got action_dims=%d n_agents=%d", fn, action_dims,
+                    n_agents);
+    if (!q1 && !q2 && !y) return fail(RISVEC_ERR_ARG, "%s: q1, q2 and y are all NULL", fn);
+    if (q2 && n_nets != 2) return fail(RISVEC_ERR_ARG, "%s: q2 needs n_nets == 2", fn);
+    if (y && (!reward || !done)) return fail(RISVEC_ERR_ARG, "%s: y needs reward and done", fn);
+    if ((logp_power || logp_intent) && !coef) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need coef", fn);
+    if ((logp_power || logp_intent) && !y) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need y", fn);
+    if (!std::isfinite(gamma)) return fail(RISVEC_ERR_ARG, "%s: gamma=%g must be finite", fn, (double)gamma);
+    return finish(fn, risvec::launch_local_critics(n_rows, n_agents, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, obs,
+                                                   action, heads, power, reward, done, gamma, coef, logp_power, logp_intent, q1,
+                                                   q2, y, (hipStream_t)stream));
+}
+
 int risvec_soft_update(int32_t n_tensors, const float* const* online, float* const* target, const int64_t* numel, float tau,
                        float one_minus_tau, risvec_stream_t stream) {
     const char* fn = "risvec_soft_update";

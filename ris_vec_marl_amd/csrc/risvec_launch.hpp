@@ -168,6 +168,16 @@ long long marl_critic_pack_workspace(int S, int A, int F1, int F2, int F3, int n
 hipError_t launch_marl_critic_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
                                    void* workspace, hipStream_t st);
 
+// Every agent's local twin critics and local TD target in one launch (k_local_critics.hip): n_agents x n_nets nets of the
+// shape of k_marl_critic at (S, A), nets[j n_nets + c] = agent j's net c, on agent j's columns of the batch.  Exactly one of
+// action / heads is given (heads with power and A == n_agents + 2); q1, q2 and y [n_agents, n_rows] are optional.
+constexpr int kLocalCriticsMaxAgents = 16;
+bool local_critics_supported(int V, int S, int A, int F1, int F2, int F3);
+hipError_t launch_local_critics(long long n_rows, int V, int S, int A, int F1, int F2, int F3, int n_nets,
+                                const RisVecMarlCriticNet* nets, const float* obs, const float* action, const float* heads,
+                                const float* power, const float* reward, const uint8_t* done, float gamma, const float* coef,
+                                const float* logp_power, const float* logp_intent, float* q1, float* q2, float* y, hipStream_t st);
+
 // target = tau online + one_minus_tau target for n_tensors <= kSoftUpdateMax tensors in one launch (k_soft_update.hip);
 // the three arrays are host arrays, copied into the kernel's argument block.
 constexpr int kSoftUpdateMax = 32;
