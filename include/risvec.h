@@ -74,7 +74,7 @@ enum {
                                        what the geometry kernel produced -- not for arbitrary channel draws. */
     RISVEC_STEP_3GPP = 512,         /* risvec_step_kernel() only: the 3GPP member of the form (risvec_step_fused_3gpp*
                                        set it internally; every other step entry point rejects it) */
-    RISVEC_STEP_THETA_IDX_CURRENT = 1024 /* risvec_step_fused and the fused form of risvec_step_ring (control_bit = 3,
+    RISVEC_STEP_THETA_IDX_CURRENT = 1024, /* risvec_step_fused and the fused form of risvec_step_ring (control_bit = 3,
                                        state.theta_idx given): state.theta_idx holds the candidate index of EVERY element
                                        of state.theta (risvec_random_phase and every sweep that writes the tensor leave
                                        it so), so a kernel may read either.  Never changes the plan or the kernel name
@@ -84,6 +84,17 @@ enum {
                                        latency-shaped kernels' NT and ALT members.  Every other kernel -- the latency-shaped
                                        members with the default cache policy among them -- ignores the bit.  Unlike
                                        RISVEC_STEP_THETA_BY_INDEX the tensor is not stale. */
+    RISVEC_STEP_H_R_STEER_CURRENT = 2048 /* risvec_step_fused and the fused form of risvec_step_ring: state.h_r is exactly
+                                       what risvec_geometry wrote from the state.steer_ang / state.z_r now in the state, so
+                                       a kernel may rebuild rows instead of reading them.  Like
+                                       RISVEC_STEP_THETA_IDX_CURRENT it never changes the plan or the kernel name; where
+                                       the plan is the software pipeline (either cache policy, the ring form included)
+                                       and n_ris is a multiple of 16, its GEN member runs: the same float64 operations
+                                       risvec_geometry used, rounded to the same float32 elements and summed in the same
+                                       order -- every output bit for bit, 8 n_ris bytes per vehicle not read
+                                       (risvec_last_h_r_rebuilt() tells; the walk stays the pipeline's).  Ignored everywhere else: the latency family,
+                                       the generic kernels, n_ris % 16 != 0, steer_ang or z_r NULL.  Not accepted
+                                       together with RISVEC_STEP_STEER. */
 };
 
 /* risvec_bcd flags */
@@ -191,6 +202,10 @@ typedef struct RisVecState {
        32 bytes); written by every control_bit = 3 sweep, read with RISVEC_BCD_REUSE_IDX / RISVEC_STEP_THETA_BY_INDEX
        (may be NULL) */
     uint8_t *theta_idx;
+    /* The float64 angle (ENV:248) every h_r row is a function of, written by risvec_geometry next to z_r when non-NULL
+       (ang_r is its float32 image): with z_r it is all a kernel needs to rebuild a row bit for bit
+       (RISVEC_STEP_H_R_STEER_CURRENT, risvec_h_r_from_steer). */
+    double *steer_ang;      /* [E,V]   f64 (may be NULL)                                  */
 } RisVecState;
 
 /* Parameters of the single-agent (SARL) environment variant,
@@ -243,6 +258,9 @@ int risvec_last_theta_by_index(void);
  * parity of its `counter` argument, so that a launch starts on the lines the launch before read last; the results and
  * the kernel name do not depend on the walk.  Every other pipeline launch (non-temporal, SARL, gain) walks forward. */
 int risvec_last_pipe_walk(void);
+/* 1 when the calling thread's last step launch rebuilt the h_r rows from state.steer_ang / state.z_r instead of reading
+ * them (RISVEC_STEP_H_R_STEER_CURRENT where the plan has a GEN member), else 0. */
+int risvec_last_h_r_rebuilt(void);
 const char *risvec_last_error(void);
 
 /* Forms of a step call, for risvec_step_kernel(): risvec_step, risvec_step_fused, risvec_step_ring (cached / fused),
@@ -302,6 +320,11 @@ int risvec_mobility(const RisVecState *s, const RisVecParams *p, const float *u_
 
 /* compute_parms (ENV:241-253): pos -> dist_r, ang_r, pl, h_r. */
 int risvec_geometry(const RisVecState *s, const RisVecParams *p, risvec_stream_t stream);
+
+/* The h_r rows as the GEN members of the fused step rebuild them: out [E,V,M] c64 (16-byte aligned) from
+ * state.steer_ang / state.z_r, by the routine risvec_geometry itself runs.  n_ris must be a multiple of 16.  After
+ * risvec_geometry, `out` equals state.h_r bit for bit; tests compare the two. */
+int risvec_h_r_from_steer(const RisVecState *s, float *out, risvec_stream_t stream);
 
 /* update_channel_gains, "free" model (ENV:263-273): theta, h_r, b, pl -> gain. */
 int risvec_gain(const RisVecState *s, const RisVecParams *p, risvec_stream_t stream);

@@ -29,6 +29,7 @@ STEP_STEER = 64
 STEP_REUSE_IDX = 128
 STEP_THETA_BY_INDEX = 256
 STEP_THETA_IDX_CURRENT = 1024     # state.theta_idx matches state.theta: a kernel may read either (fused forms)
+STEP_H_R_STEER_CURRENT = 2048     # state.h_r is what risvec_geometry wrote from steer_ang / z_r: a kernel may rebuild rows
 STEP_3GPP = 512          # risvec_step_kernel(): the 3GPP member of the form (the 3GPP entry points set it themselves)
 BCD_REUSE_COLSUM, BCD_REUSE_SSUM, BCD_REUSE_IDX, BCD_NO_THETA = 1, 2, 4, 8
 FORM_CACHED, FORM_FUSED, FORM_CACHED_RING, FORM_FUSED_RING, FORM_FUSED_MULTI = range(5)
@@ -79,7 +80,7 @@ class RisVecState(C.Structure):
         ("data_buf", _FP), ("mec_q", _FP),
         ("rate", _FP), ("data_t", _FP), ("data_p", _FP), ("reward", _FP), ("over_power", _FP),
         ("obs", _FP), ("metrics", _FP), ("power_w", _FP), ("c_col", _FP), ("s_sum", _FP), ("over_data", _FP), ("z_r", _FP),
-        ("theta_idx", _FP),
+        ("theta_idx", _FP), ("steer_ang", _FP),
     ]
 
 
@@ -176,6 +177,8 @@ _PROTOS = {
     "risvec_last_kernel": (C.c_char_p, []),
     "risvec_last_theta_by_index": (C.c_int, []),
     "risvec_last_pipe_walk": (C.c_int, []),
+    "risvec_last_h_r_rebuilt": (C.c_int, []),
+    "risvec_h_r_from_steer": (C.c_int, [C.POINTER(RisVecState), _FP, _FP]),
     "risvec_step_kernel": (C.c_char_p, [C.POINTER(RisVecState), C.c_uint32, C.c_int32]),
     "risvec_force_forms": (C.c_int, [C.POINTER(RisVecForce)]),
     "risvec_default_params": (None, [C.POINTER(RisVecParams)]),
@@ -374,6 +377,12 @@ def last_pipe_walk() -> int:
     """0 / 1: the calling thread's last software-pipeline launch walked its envs forward / backward
     (risvec_last_pipe_walk)."""
     return int(load().risvec_last_pipe_walk())
+
+
+def last_h_r_rebuilt() -> int:
+    """1 if the calling thread's last step launch rebuilt the h_r rows from steer_ang / z_r instead of reading them
+    (risvec_last_h_r_rebuilt)."""
+    return int(load().risvec_last_h_r_rebuilt())
 
 
 def step_kernel(state, flags: int = 0, form: int = FORM_FUSED):

@@ -191,13 +191,13 @@ k_mobility(Dims d, RisVecParams P, double* __restrict__ pos, int32_t* __restrict
 // |arg| reaches ~800 rad at m = 255, so everything is float64 until the final rounding.  A thread
 // evaluates two sincospi - the chunk's first element and the per-element rotation w =
 // exp(-j pi ang) - and walks the chunk with z <- z w (16 rotations: ~2e-15 accumulated error),
-// instead of one sincospi per element.  A chunk is 128 contiguous bytes of the row.
-constexpr int kGeoChunk = 16;
-
+// instead of one sincospi per element.  A chunk is 128 contiguous bytes of the row.  The chunk's arithmetic is
+// steer_chunk() (risvec_dev.hpp, with kGeoChunk): the fused step's GEN members rebuild the same bits from steer_ang / z_r.
 template <bool STAGED>
 __global__ void __launch_bounds__(kBlock)
 k_geometry(Dims d, const double* __restrict__ pos, float* __restrict__ dist_r,
-           float* __restrict__ ang_r, float* __restrict__ pl, float* __restrict__ h_r, double* __restrict__ z_r) {
+           float* __restrict__ ang_r, float* __restrict__ pl, float* __restrict__ h_r, double* __restrict__ z_r,
+           double* __restrict__ steer_ang) {
     const int nchunk = (d.M + kGeoChunk - 1) / kGeoChunk;
     long long idx = (long long)blockIdx.x * kBlock + threadIdx.x;
     const bool in_range = idx < (long long)d.E * d.V * nchunk;
@@ -218,12 +218,13 @@ k_geometry(Dims d, const double* __restrict__ pos, float* __restrict__ dist_r,
                                  + (kBsZ - kRisZ) * (kBsZ - kRisZ));        // ENV:175-176
         pl[ev] = (float)((kRo * kRo) / (pow(dist, kAlpha1) * pow(d_br, kAlpha2)));   // ENV:270-272
     }
-    double zs, zc, ws, wc;
-    sincospi(ang * (double)m0, &zs, &zc);          // z = exp(-j pi ang m0) = (zc, -zs)
+    double ws, wc;
     sincospi(ang, &ws, &wc);                       // w = exp(-j pi ang)    = (wc, -ws)
-    double zr = zc, zi = -zs;
     const double wr = wc, wi = -ws;
     if (z_r && m0 == 0 && in_range) reinterpret_cast<double2*>(z_r)[ev] = make_double2(wr, wi);   // h_r[e,v,m] = w^m
+    if (steer_ang && m0 == 0 && in_range) steer_ang[ev] = ang;             // the float64 angle the rows are a function of
+    float4 q[kGeoChunk / 2];                       // the chunk: z = exp(-j pi ang m0), then z <- z w
+    steer_chunk(ang, wr, wi, m0, q);
     float* out = h_r + (ev * d.M + m0) * 2;
     if constexpr (STAGED) {
         // M % 16 == 0: every lane owns one full 128-byte chunk and the block's 256 chunks are contiguous
@@ -233,12 +234,7 @@ k_geometry(Dims d, const double* __restrict__ pos, float* __restrict__ dist_r,
         __shared__ float4 s_stage[kBlock * 9];
         float4* row = s_stage + threadIdx.x * 9;
 #pragma unroll
-        for (int k = 0; k < kGeoChunk; k += 2) {
-            const double ar = zr, ai = zi;
-            const double br = ar * wr - ai * wi, bi = ar * wi + ai * wr;        // next element
-            zr = br * wr - bi * wi; zi = br * wi + bi * wr;                     // the one after
-            row[k / 2] = make_float4((float)ar, (float)ai, (float)br, (float)bi);
-        }
+        for (int k = 0; k < kGeoChunk / 2; ++k) row[k] = q[k];
         __syncthreads();
         const long long block_first = (long long)blockIdx.x * kBlock;          // first chunk of this block
         const long long n_chunks = (long long)d.E * d.V * nchunk;
@@ -253,14 +249,12 @@ k_geometry(Dims d, const double* __restrict__ pos, float* __restrict__ dist_r,
     const bool vec = (d.M & 1) == 0;               // even M: rows are 16-byte aligned, pairs never straddle
 #pragma unroll
     for (int k = 0; k < kGeoChunk; k += 2) {
-        const double ar = zr, ai = zi;
-        const double br = ar * wr - ai * wi, bi = ar * wi + ai * wr;        // next element
-        zr = br * wr - bi * wi; zi = br * wi + bi * wr;                     // the one after
+        const float4 p = q[k / 2];
         if (m0 + k + 1 < d.M) {
-            if (vec) *reinterpret_cast<float4*>(out + 2 * k) = make_float4((float)ar, (float)ai, (float)br, (float)bi);
-            else { out[2 * k] = (float)ar; out[2 * k + 1] = (float)ai; out[2 * k + 2] = (float)br; out[2 * k + 3] = (float)bi; }
+            if (vec) *reinterpret_cast<float4*>(out + 2 * k) = p;
+            else { out[2 * k] = p.x; out[2 * k + 1] = p.y; out[2 * k + 2] = p.z; out[2 * k + 3] = p.w; }
         } else if (m0 + k < d.M) {
-            out[2 * k] = (float)ar; out[2 * k + 1] = (float)ai;
+            out[2 * k] = p.x; out[2 * k + 1] = p.y;
         }
     }
 }
@@ -347,10 +341,10 @@ hipError_t launch_geometry(const RisVecState& s, const RisVecParams&, hipStream_
     const long long n = (long long)s.n_envs * s.n_veh * ((s.n_ris + kGeoChunk - 1) / kGeoChunk);
     if (s.n_ris % kGeoChunk == 0)
         hipLaunchKernelGGL(k_geometry<true>, dim3(blocks_for(n)), dim3(kBlock), 0, st, dims_of(s), s.pos,
-                           s.dist_r, s.ang_r, s.pl, s.h_r, s.z_r);
+                           s.dist_r, s.ang_r, s.pl, s.h_r, s.z_r, s.steer_ang);
     else
         hipLaunchKernelGGL(k_geometry<false>, dim3(blocks_for(n)), dim3(kBlock), 0, st, dims_of(s), s.pos,
-                           s.dist_r, s.ang_r, s.pl, s.h_r, s.z_r);
+                           s.dist_r, s.ang_r, s.pl, s.h_r, s.z_r, s.steer_ang);
     return hipGetLastError();
 }
 

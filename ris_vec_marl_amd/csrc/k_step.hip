@@ -322,6 +322,10 @@ static hipError_t launch_step_vp(const RisVecState& s, const RisVecParams& p, co
 //     the NT and ALT members of 3. (always EMAX envs per wavefront) k_step_fused_lat<..,EMAX,NT|ALT,TK>
 //   Everywhere else the bit is ignored: the default-policy members of 3. (one memory round trip, not byte-bound: a table
 //   fill in front of their first use for nothing), the steering, generic and 3GPP kernels.
+//   RISVEC_STEP_H_R_STEER_CURRENT selects nothing either.  Where the plan is the pipeline of 4. or its ring form (either
+//   cache policy), M % 16 == 0 and the state carries steer_ang and z_r, launch_step runs the pipeline's GEN member
+//   k_step_fused_gen<V,M,Core,TK?> (k_step_gen.hip): the rows are rebuilt by steer_chunk(), not read; the walk is the
+//   pipeline's (the order of a wavefront's groups).  Everywhere else the bit is ignored.
 //
 // Why (us per step; profiles/):
 //   * beyond 1.29 IC many short wavefronts with every request up front are what the best pure reader looks like: 1-4 %
@@ -521,7 +525,8 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
     const StepPlan pl = plan_step(s, flags, form);
     if (pl.family == StepPlan::NONE) return hipErrorNotSupported;
     StepArgs a = make_step_args(s, action, partner, n_groups, arrivals, seed, counter,
-                                flags & ~(uint32_t)(RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX | RISVEC_STEP_THETA_IDX_CURRENT));
+                                flags & ~(uint32_t)(RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX | RISVEC_STEP_THETA_IDX_CURRENT |
+                                                    RISVEC_STEP_H_R_STEER_CURRENT));
     if (ring) a.ring = *ring;                                  // the transition store rides in the step kernel
     // theta is kept by index (the API checked the shape), or the indices are known to match the tensor and the plan is one
     // of the byte-bound kernels with a by-index instantiation: the software pipeline (either cache policy, the ring form
@@ -534,18 +539,24 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
         a.theta_k = s.theta_idx;
         a.theta_k_stride = theta_idx_stride(s.n_ris);
     }
+    // h_r is known to be what risvec_geometry wrote from steer_ang / z_r, and the plan is the software pipeline at a shape
+    // whose rows are whole 16-element chunks: its GEN member rebuilds the rows instead of reading them (same bits).
+    const bool gen = (flags & RISVEC_STEP_H_R_STEER_CURRENT) && pl.family == StepPlan::PIPE && pl.M % 16 == 0 &&
+                     s.steer_ang != nullptr && s.z_r != nullptr;
     hipError_t err;
     if (pl.family == StepPlan::LAT) err = launch_step_fused_lat(s, p, a, pl, 1, RisVecTraj{}, st);
     else if (pl.family == StepPlan::PIPE) {
         // The pipeline with the default cache policy walks the envs forward on even steps and backward on odd ones (the
         // parity ALT uses): a launch then starts on the lines the launch before read last (EXPERIMENTS.md 2026-10-19).  Same kernel
-        // name, same results; RisVecForce::pipe_rev pins the direction.
+        // name, same results; RisVecForce::pipe_rev pins the direction.  The GEN member keeps the walk (the order of a
+        // wavefront's groups) for what it still reads.
         const bool rev = pl.pol == 0 && forced_or(forced_forms().pipe_rev, (a.counter & 1u) != 0);
-        err = launch_step_fused_pipe(s, p, a, pl, rev, st);
+        err = gen ? launch_step_fused_gen(s, p, a, pl, rev, st) : launch_step_fused_pipe(s, p, a, pl, rev, st);
     }
     else err = with_vp(s.n_veh, [&](auto vp) { return launch_step_vp<vp>(s, p, a, pl, st); });
     note_kernel("%s", pl.name);
     note_theta_by_index(a.theta_k != nullptr);
+    note_h_r_rebuilt(gen);
     return err;
 }
 

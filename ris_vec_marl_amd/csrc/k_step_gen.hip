@@ -1,0 +1,318 @@
+// K34-GEN, the software pipeline's member that REBUILDS the h_r rows instead of reading them
+// (RISVEC_STEP_H_R_STEER_CURRENT).  compute_parms makes every row of h_r a pure function of one float64 angle per
+// vehicle (k_geometry, k_env.hip); while that is still what state.h_r holds, the 8M bytes of a row need not be moved:
+// steer_chunk() (risvec_dev.hpp) -- the routine k_geometry itself ran -- gives the same float32 elements from
+// state.steer_ang (8 bytes) and state.z_r (16 bytes).  Everything behind the float4 is k_step_fused_pipe's, operation for
+// operation: lane gl accumulates its NIT pairs with cfma from zero in `it` order, treduce<K, G/2>, the same s_img slot,
+// the same core.  Only where the float4 comes from changes, so every output is the reading form's bit for bit.
+//
+// The rotation chain inside a chunk is sequential (each step rounds), so a lane cannot start in the middle of one:
+// lanes own WHOLE chunks.  One pass of the wavefront makes 64 chunks = 1024 consecutive elements of the group's rows
+// (kWave / NCH rows, NCH = M / 16 chunks per row), parks each chunk's eight float4 in a per-wavefront LDS stage (chunk
+// stride padded to 144 B against bank conflicts, as k_geometry's s_stage), and the consumer lanes read their float4 from
+// the stage in the pipeline's layout (ds_read_b128 at compile-time offsets).  A group is NCH passes.  Same-wave LDS
+// accesses execute in order, so __builtin_amdgcn_wave_barrier() between the stage's writes, its reads and the next
+// pass's writes only pins the compiler; no workgroup barrier.
+//
+// What a pass needs from memory -- the angle and w of the lane's chunk, theta of the envs the pass completes -- is
+// requested one outer iteration ahead (across the group boundary), step()'s per-lane inputs one group ahead as in the
+// reading form.
+#include "risvec_pipe.hpp"
+
+namespace risvec {
+
+template <int V, int M>
+struct GenShape : PipeShape<V, M> {
+    using S = PipeShape<V, M>;
+    static_assert(M % kGeoChunk == 0, "rows are rebuilt in whole 16-element chunks");
+    static_assert(S::EPW * V == kWave, "a group is 64 rows");
+    static constexpr int NCH = M / kGeoChunk;                  // chunks per row = passes per group
+    static_assert(NCH <= kWave, "a pass must cover at least one row");
+    static constexpr int RPP = kWave / NCH;                    // rows per pass
+    static constexpr int RPU = S::PC * S::VPP;                 // rows per unit (units partition the group's rows in order)
+    static_assert(RPP % RPU == 0, "a pass must hold whole units");
+    static constexpr int UPP = RPP / RPU;                      // units per pass
+    // an outer iteration = SP passes = whole envs, so which chunk of an env a unit is stays a compile-time constant
+    static constexpr int SP = UPP >= S::CHUNKS ? 1 : S::CHUNKS / UPP;
+    static constexpr int EPO = SP * UPP / S::CHUNKS;           // envs per outer iteration
+    static constexpr int NO = NCH / SP;                        // outer iterations per group
+    static_assert(SP * UPP % S::CHUNKS == 0 && NCH % SP == 0 && NO * EPO == S::EPW, "outer iterations must tile the group");
+    static constexpr int STAGE = kWave * (kGeoChunk / 2 + 1);  // float4 per wavefront: 64 chunks of 8 (+1 pad)
+};
+
+// what one outer iteration reads from memory
+template <int SP, int EPO, int NIT, bool TK>
+struct GenFeed {
+    double ang[SP];
+    double2 w[SP];
+    float4 t[EPO][NIT];
+};
+template <int SP, int EPO, int NIT>
+struct GenFeed<SP, EPO, NIT, true> {
+    double ang[SP];
+    double2 w[SP];
+    unsigned k[EPO][NIT];
+};
+
+// per_wave > 0: a wavefront owns the CONTIGUOUS groups [wid * per_wave, (wid + 1) * per_wave); per_wave = 0: groups
+// wid, wid + nw, ...  TK: theta by index, as in k_step_fused_pipe.
+// rev: the wavefront serves the SAME groups, last first -- the pipeline's alternating walk (launch_step: the parity of the
+// step counter), kept so that what a launch touched last (theta or its indices, step()'s inputs: all that is still read)
+// is what the next launch asks for first.  Only the order of the groups turns: nothing inside a group depends on the
+// direction, so it is a run-time argument here, not an instantiation.
+template <int V, int M, class Core, bool TK>
+__global__ void __launch_bounds__(kBlock)
+k_step_fused_gen(Dims d, typename Core::Params P, typename Core::Args A, const double* __restrict__ steer_ang,
+                 const double* __restrict__ z_r, int n_groups_total, int per_wave, int rev) {
+    using In = typename Core::In;
+    using S = GenShape<V, M>;
+    constexpr int VP = S::VP, EPW = S::EPW, NP = S::NP, G = S::G, NIT = S::NIT, VPP = S::VPP;
+    constexpr int PC = S::PC, CHUNKS = S::CHUNKS, K = S::K;
+    constexpr int NCH = S::NCH, RPP = S::RPP, RPU = S::RPU, UPP = S::UPP, SP = S::SP, EPO = S::EPO, NO = S::NO;
+    static_assert(std::is_same<typename Core::Args, StepArgs>::value, "the GEN members step on StepArgs");
+    using Feed = GenFeed<SP, EPO, NIT, TK>;
+    __shared__ float s_img[kBlock / kWave][kWave * 2];
+    __shared__ float2 s_ph[TK ? kBlock / kWave : 1][16];
+    __shared__ float4 s_stage[kBlock / kWave][S::STAGE];
+
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int gl = lane % G, gv = lane / G;
+    const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / kWave) + wave);
+    const int nw = gridDim.x * (kBlock / kWave);
+    const float4* __restrict__ t4 = reinterpret_cast<const float4*>(A.theta);
+    const float4* __restrict__ b4 = reinterpret_cast<const float4*>(A.b);
+    const double2* __restrict__ z2 = reinterpret_cast<const double2*>(z_r);
+    const int e_last = d.E - 1;
+    const int row_last = d.E * V - 1;
+    float4 bq[NIT];
+    int pcl[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int p = gl + it * G;
+        const float4 x = b4[p < NP ? p : NP - 1];
+        bq[it] = p < NP ? x : make_float4(0.f, 0.f, 0.f, 0.f);
+        // (ragged rows, NP % G != 0: the lanes past the end of a row take its last float4, against a zero b -- an exact
+        // +0 in the sums, as in the reading form)
+        pcl[it] = (NP % G == 0 || p < NP) ? p : NP - 1;
+    }
+    // producer: this lane's chunk of a pass -- row lane / NCH of the pass, elements m0 ...
+    const int p_row = lane / NCH, p_m0 = (lane % NCH) * kGeoChunk;
+    float4* __restrict__ stage = s_stage[wave];
+    float4* __restrict__ p_dst = stage + lane * (kGeoChunk / 2 + 1);
+    // consumer: float4 `pcl[it]` of row gv of a unit's lane-group pass, as an index into the stage (8 float4 per chunk,
+    // chunk stride 9); the unit and the row-in-unit add compile-time offsets
+    const float4* c_src[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+        const int f = gv * NP + pcl[it];
+        c_src[it] = stage + (f >> 3) * (kGeoChunk / 2 + 1) + (f & 7);
+    }
+
+    // the requests of outer iteration `o` of group `grp` (tail: the last row / env again, masked later)
+    auto load_feed = [&](Feed& f, int grp, int o) {
+#pragma unroll
+        for (int sp = 0; sp < SP; ++sp) {
+            int row = grp * kWave + (o * SP + sp) * RPP + p_row;
+            row = row < row_last ? row : row_last;
+            f.ang[sp] = steer_ang[row];
+            f.w[sp] = z2[row];
+        }
+#pragma unroll
+        for (int ie = 0; ie < EPO; ++ie) {
+            int e = grp * EPW + o * EPO + ie;
+            e = e < e_last ? e : e_last;
+            if constexpr (TK) {
+                const uint8_t* __restrict__ kb = A.theta_k + (long long)e * A.theta_k_stride;
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) f.k[ie][it] = *reinterpret_cast<const uint16_t*>(kb + 2 * pcl[it]);
+            } else {
+                const float4* __restrict__ tb = t4 + (long long)e * NP;
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) f.t[ie][it] = tb[pcl[it]];
+            }
+        }
+    };
+
+    const int stride = per_wave > 0 ? 1 : nw;
+    int grp = per_wave > 0 ? wid * per_wave : wid;
+    int grp_end = per_wave > 0 ? grp + per_wave : n_groups_total;
+    grp_end = grp_end < n_groups_total ? grp_end : n_groups_total;
+    if constexpr (TK) {
+        RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b), "s"(n_groups_total),
+                                "s"(per_wave), "s"(d.E));
+    } else {
+        RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave), "s"(d.E));
+    }
+    if (grp >= grp_end) return;                            // whole wave: no cross-lane op is skipped
+    const int grp_first = grp;
+    if (rev) {                                             // a few scalar adds: a wavefront owns a handful of groups
+        while (grp + stride < grp_end) grp += stride;
+    }
+    const int step = rev ? -stride : stride;
+    Feed cur;
+    load_feed(cur, grp, 0);
+    if constexpr (TK) {
+        theta_table_fill(s_ph[wave], lane);
+        __builtin_amdgcn_wave_barrier();
+    }
+    const int v_mine = lane % VP;
+
+    auto do_group = [&](int g_cur, const In& in, In& in_nx) {
+        // (unconditional prefetches, as in the reading form: a wave on its last group asks for group 0's)
+        const int g_nx = g_cur + step;
+        const int nxt = (g_nx >= grp_first && g_nx < grp_end) ? g_nx : 0;
+        const int e_mine = g_cur * EPW + lane / VP;
+        const bool active = e_mine < d.E;
+        Core::hold(in);
+
+#pragma unroll 1
+        for (int o = 0; o < NO; ++o) {
+            Feed nx;
+            if (o + 1 < NO) load_feed(nx, g_cur, o + 1);
+            else load_feed(nx, nxt, 0);
+            float2 w0[NIT], w1[NIT];
+#pragma unroll
+            for (int sp = 0; sp < SP; ++sp) {
+                float4 q[kGeoChunk / 2];
+                steer_chunk(cur.ang[sp], cur.w[sp].x, cur.w[sp].y, p_m0, q);
+#pragma unroll
+                for (int k = 0; k < kGeoChunk / 2; ++k) p_dst[k] = q[k];
+                __builtin_amdgcn_wave_barrier();           // the stage's writes -> its reads (same wave: in order)
+#pragma unroll
+                for (int ul = 0; ul < UPP; ++ul) {
+                    const int uo = sp * UPP + ul;          // unit within the outer iteration
+                    const int c = uo % CHUNKS, ie = uo / CHUNKS;
+                    if (c == 0) {
+#pragma unroll
+                        for (int it = 0; it < NIT; ++it) {
+                            float2 t0, t1;
+                            if constexpr (TK) {
+                                t0 = s_ph[wave][cur.k[ie][it] & 15u];
+                                t1 = s_ph[wave][(cur.k[ie][it] >> 8) & 15u];
+                            } else {
+                                t0 = make_float2(cur.t[ie][it].x, cur.t[ie][it].y);
+                                t1 = make_float2(cur.t[ie][it].z, cur.t[ie][it].w);
+                            }
+                            w0[it] = cmul(t0, make_float2(bq[it].x, bq[it].y));
+                            w1[it] = cmul(t1, make_float2(bq[it].z, bq[it].w));
+                        }
+                    }
+                    float val[8];
+#pragma unroll
+                    for (int pc = 0; pc < PC; ++pc) {
+                        float2 acc = make_float2(0.f, 0.f);
+#pragma unroll
+                        for (int it = 0; it < NIT; ++it) {
+                            const float4 h = c_src[it][((ul * RPU + pc * VPP) * NCH) * (kGeoChunk / 2 + 1)];
+                            acc = cfma(make_float2(h.x, h.y), w0[it], acc);
+                            acc = cfma(make_float2(h.z, h.w), w1[it], acc);
+                        }
+                        val[2 * pc] = acc.x;
+                        val[2 * pc + 1] = acc.y;
+                    }
+                    treduce<K, G / 2>(val, gl);
+                    if (gl % S::WSTRIDE == 0) {
+                        const int j = gl / S::WSTRIDE;             // value index = (row-in-unit, re/im)
+                        const int v = (c * PC + (j >> 1)) * VPP + gv;
+                        const int i = o * EPO + ie;                // env of the group
+                        s_img[wave][(i * VP + v) * 2 + (j & 1)] = val[0];
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();           // the stage's reads -> the next pass's writes
+            }
+            cur = nx;
+        }
+        in_nx = Core::load(d, A, nxt * EPW + lane / VP, v_mine, nxt * EPW + lane / VP < d.E);
+
+        __builtin_amdgcn_wave_barrier();
+        const float2 img = *reinterpret_cast<const float2*>(&s_img[wave][lane * 2]);
+        Core::template run<VP>(d, P, A, e_mine, v_mine, active, img, in);
+        __builtin_amdgcn_wave_barrier();
+    };
+
+    In inA = Core::load(d, A, grp * EPW + lane / VP, v_mine, grp * EPW + lane / VP < d.E), inB;
+    while (true) {
+        do_group(grp, inA, inB);
+        grp += step;
+        if (grp < grp_first || grp >= grp_end) break;
+        do_group(grp, inB, inA);
+        grp += step;
+        if (grp < grp_first || grp >= grp_end) break;
+    }
+}
+
+// Wavefronts per CU: no register ring, and 38.5 KiB of LDS per workgroup (the stage), so four workgroups fit a CU.  The
+// float64 chain of a pass is long and dependent (one sincospi, 15 rotations): four wavefronts per SIMD cover its
+// latency where the reading form's two covered a stream.
+constexpr int kGenWavesPerCu = 16;
+
+template <int V, int M, class Core>
+static hipError_t launch_gen(const RisVecState& s, const typename Core::Params& p, const typename Core::Args& a, bool rev,
+                             hipStream_t st) {
+    using S = GenShape<V, M>;
+    const int n_groups = (s.n_envs + S::EPW - 1) / S::EPW;
+    const int wpb = kBlock / kWave;
+    const int forced_waves = forced_forms().pipe_waves;
+    long long want_waves = forced_waves > 0 ? forced_waves : (long long)num_cus() * kGenWavesPerCu;
+    if (want_waves > n_groups) want_waves = n_groups;
+    const long long per_wave = (n_groups + want_waves - 1) / want_waves;
+    want_waves = (n_groups + per_wave - 1) / per_wave;
+    const unsigned grid = (unsigned)((want_waves + wpb - 1) / wpb);
+    const int contiguous = forced_waves > 0 ? (int)per_wave : 0;
+    auto go = [&](auto knl) {
+        hipLaunchKernelGGL(knl, dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, s.steer_ang, s.z_r, n_groups, contiguous,
+                           rev ? 1 : 0);
+    };
+    if (a.theta_k != nullptr) go(k_step_fused_gen<V, M, Core, true>);
+    else go(k_step_fused_gen<V, M, Core, false>);
+    return hipGetLastError();
+}
+
+// the shapes whose rows are whole chunks have GEN members; the others keep reading
+template <int V, int M, bool WHOLE = (M % kGeoChunk == 0)>
+struct GenMember {
+    static hipError_t launch(const RisVecState&, const RisVecParams&, const StepArgs&, bool, bool, hipStream_t) {
+        return hipErrorNotSupported;
+    }
+};
+template <int V, int M>
+struct GenMember<V, M, true> {
+    static hipError_t launch(const RisVecState& s, const RisVecParams& p, const StepArgs& a, bool ring, bool rev, hipStream_t st) {
+        return ring ? launch_gen<V, M, MarlRingCore<V>>(s, p, a, rev, st) : launch_gen<V, M, MarlCore>(s, p, a, rev, st);
+    }
+};
+
+hipError_t launch_step_fused_gen(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
+                                 bool rev, hipStream_t st) {
+    note_pipe_walk(rev ? 1 : 0);
+#define RISVEC_X(VV, MM, DD, EMIN, EMAX, T) \
+    if (pl.V == VV && pl.M == MM) return GenMember<VV, MM>::launch(s, p, a, pl.ring, rev, st);
+    RISVEC_FIXED_SHAPES(RISVEC_X)
+#undef RISVEC_X
+    return hipErrorNotSupported;
+}
+
+// risvec_h_r_from_steer: one thread per chunk, straight to memory
+__global__ void __launch_bounds__(kBlock)
+k_h_r_from_steer(Dims d, const double* __restrict__ steer_ang, const double* __restrict__ z_r, float* __restrict__ out) {
+    const int nchunk = d.M / kGeoChunk;
+    const long long idx = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= (long long)d.E * d.V * nchunk) return;
+    const long long ev = idx / nchunk;
+    const int m0 = (int)(idx % nchunk) * kGeoChunk;
+    const double2 w = reinterpret_cast<const double2*>(z_r)[ev];
+    float4 q[kGeoChunk / 2];
+    steer_chunk(steer_ang[ev], w.x, w.y, m0, q);
+    float4* dst = reinterpret_cast<float4*>(out + (ev * d.M + m0) * 2);
+#pragma unroll
+    for (int k = 0; k < kGeoChunk / 2; ++k) dst[k] = q[k];
+}
+
+hipError_t launch_h_r_from_steer(const RisVecState& s, float* out, hipStream_t st) {
+    const long long n = (long long)s.n_envs * s.n_veh * (s.n_ris / kGeoChunk);
+    hipLaunchKernelGGL(k_h_r_from_steer, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, dims_of(s),
+                       s.steer_ang, s.z_r, out);
+    return hipGetLastError();
+}
+
+}  // namespace risvec

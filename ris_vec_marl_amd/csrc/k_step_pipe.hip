@@ -411,6 +411,7 @@ hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, c
 }
 
 int last_pipe_walk() { return g_pipe_walk; }
+void note_pipe_walk(int walk) { g_pipe_walk = walk; }
 
 template <class Core, class P, class A>
 static hipError_t launch_core(const RisVecState& s, const P& p, const A& a, hipStream_t st) {

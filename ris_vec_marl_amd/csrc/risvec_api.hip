@@ -15,6 +15,7 @@ namespace {
 thread_local char g_err[512] = "";
 thread_local char g_kernel[160] = "";
 thread_local int g_theta_by_index = 0;
+thread_local int g_h_r_rebuilt = 0;
 RisVecForce g_force{};                  // risvec_force_forms(): all RISVEC_BY_RULE
 
 int fail(int code, const char* fmt, ...) {
@@ -108,9 +109,17 @@ int check_step(const char* fn, const RisVecState* s, const float* action, const 
     return RISVEC_OK;
 }
 
-// RISVEC_STEP_THETA_IDX_CURRENT, accepted by risvec_step_fused and the fused form of risvec_step_ring only (check_step
-// refuses it as an unknown bit everywhere else): checks what it needs and returns the flags check_step sees
+// RISVEC_STEP_THETA_IDX_CURRENT and RISVEC_STEP_H_R_STEER_CURRENT, accepted by risvec_step_fused and the fused form of
+// risvec_step_ring only (check_step refuses them as unknown bits everywhere else): checks what they need and returns the
+// flags check_step sees
 int check_idx_current(const char* fn, const RisVecState* s, bool fused, uint32_t* flags) {
+    if (*flags & RISVEC_STEP_H_R_STEER_CURRENT) {
+        if (!fused) return fail(RISVEC_ERR_ARG, "%s: RISVEC_STEP_H_R_STEER_CURRENT is a hint to the fused forms (this one reads no h_r)", fn);
+        if (*flags & RISVEC_STEP_STEER)
+            return fail(RISVEC_ERR_ARG, "%s: RISVEC_STEP_H_R_STEER_CURRENT and RISVEC_STEP_STEER exclude each other", fn);
+        OPT_PTR(s->steer_ang, "state.steer_ang"); OPT_PTR(s->z_r, "state.z_r");
+        *flags &= ~(uint32_t)RISVEC_STEP_H_R_STEER_CURRENT;
+    }
     if (!(*flags & RISVEC_STEP_THETA_IDX_CURRENT)) return RISVEC_OK;
     if (!fused) return fail(RISVEC_ERR_ARG, "%s: RISVEC_STEP_THETA_IDX_CURRENT is a hint to the fused forms (this one reads no theta)", fn);
     REQ_PTR(s->theta_idx, "state.theta_idx");
@@ -196,9 +205,12 @@ void note_kernel(const char* fmt, ...) {
     vsnprintf(g_kernel, sizeof(g_kernel), fmt, ap);
     va_end(ap);
     g_theta_by_index = 0;
+    g_h_r_rebuilt = 0;
 }
 
 void note_theta_by_index(bool by_index) { g_theta_by_index = by_index ? 1 : 0; }
+
+void note_h_r_rebuilt(bool rebuilt) { g_h_r_rebuilt = rebuilt ? 1 : 0; }
 
 const RisVecForce& forced_forms() { return g_force; }
 }  // namespace risvec
@@ -212,6 +224,8 @@ const char* risvec_last_kernel(void) { return g_kernel; }
 int risvec_last_theta_by_index(void) { return g_theta_by_index; }
 
 int risvec_last_pipe_walk(void) { return risvec::last_pipe_walk(); }
+
+int risvec_last_h_r_rebuilt(void) { return g_h_r_rebuilt; }
 
 const char* risvec_last_error(void) { return g_err; }
 
@@ -317,7 +331,7 @@ int risvec_geometry(const RisVecState* s, const RisVecParams* p, risvec_stream_t
     const char* fn = "risvec_geometry";
     if (int rc = check_common(fn, s, p)) return rc;
     REQ_PTR(s->pos, "state.pos"); REQ_PTR(s->dist_r, "state.dist_r"); REQ_PTR(s->ang_r, "state.ang_r");
-    OPT_PTR(s->z_r, "state.z_r");
+    OPT_PTR(s->z_r, "state.z_r"); OPT_PTR(s->steer_ang, "state.steer_ang");
     REQ_PTR(s->pl, "state.pl"); REQ_PTR(s->h_r, "state.h_r");
     OPT_PTR(s->c_col, "state.c_col");
     if (int rc = finish(fn, risvec::launch_geometry(*s, *p, (hipStream_t)stream))) return rc;
@@ -326,6 +340,15 @@ int risvec_geometry(const RisVecState* s, const RisVecParams* p, risvec_stream_t
         return finish(fn, risvec::launch_colsum(*s, (hipStream_t)stream));
     }
     return RISVEC_OK;
+}
+
+int risvec_h_r_from_steer(const RisVecState* s, float* out, risvec_stream_t stream) {
+    const char* fn = "risvec_h_r_from_steer";
+    if (int rc = check_common(fn, s, nullptr, false)) return rc;
+    REQ_PTR(s->steer_ang, "state.steer_ang"); REQ_PTR(s->z_r, "state.z_r"); REQ_PTR(out, "out");
+    if (s->n_ris % 16 != 0)
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: n_ris=%d is not a multiple of 16 (rows are rebuilt in 16-element chunks)", fn, s->n_ris);
+    return finish(fn, risvec::launch_h_r_from_steer(*s, out, (hipStream_t)stream));
 }
 
 int risvec_gain(const RisVecState* s, const RisVecParams* p, risvec_stream_t stream) {

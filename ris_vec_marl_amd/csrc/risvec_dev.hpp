@@ -175,4 +175,30 @@ __device__ __forceinline__ float2 phasor_of_angle(float angle) {
     return make_float2((float)c, (float)s);
 }
 
+// One 16-element chunk of a steering row, h_r[e,v,m0 .. m0+15] = exp(-j pi ang m), as float32 pairs: out[k] holds
+// elements m0 + 2k and m0 + 2k + 1.  THE definition of the row -- k_geometry (k_env.hip) writes it to state.h_r, and the
+// GEN members of the fused step (k_step_gen.hip) rebuild it from state.steer_ang / state.z_r instead of reading it, and
+// must get the same bits.  One sincospi at the head of the chunk, then 15 float64 rotations by w = exp(-j pi ang) =
+// (wr, wi), each element rounded once to float32.  Every product and sum is spelled out: which of the two products of
+// `a * b - c * d` is fused is otherwise the compiler's choice, and two inlined copies could choose differently.  The
+// association below is the one the compiler had chosen for k_geometry (read off its gfx950 code): the w-real product is
+// fused and the w-imaginary product rounded first, except in the first rotation of every pair after the chunk's first,
+// where it is the other way round.
+constexpr int kGeoChunk = 16;
+
+__device__ __forceinline__ void steer_chunk(double ang, double wr, double wi, int m0, float4 (&out)[kGeoChunk / 2]) {
+#pragma clang fp contract(off)
+    double zs, zc;
+    sincospi(__dmul_rn(ang, (double)m0), &zs, &zc);          // z = exp(-j pi ang m0) = (zc, -zs)
+    double ar = zc, ai = -zs;
+#pragma unroll
+    for (int k = 0; k < kGeoChunk; k += 2) {
+        const double br = k == 0 ? fma(ar, wr, -__dmul_rn(ai, wi)) : fma(-ai, wi, __dmul_rn(ar, wr));   // next element
+        const double bi = fma(ai, wr, __dmul_rn(ar, wi));
+        out[k / 2] = make_float4((float)ar, (float)ai, (float)br, (float)bi);
+        ar = fma(br, wr, -__dmul_rn(bi, wi));                                                           // the one after
+        ai = fma(bi, wr, __dmul_rn(br, wi));
+    }
+}
+
 }  // namespace risvec

@@ -200,6 +200,10 @@ hipError_t launch_theta_from_index(const RisVecState& s, hipStream_t st);
 void note_kernel(const char* fmt, ...);
 // risvec_last_theta_by_index(): note_kernel() clears it, the step launcher sets it after naming its kernel
 void note_theta_by_index(bool by_index);
+// risvec_last_h_r_rebuilt(): likewise
+void note_h_r_rebuilt(bool rebuilt);
+// state.steer_ang / state.z_r -> out [E,V,M] c64 by steer_chunk(), M % 16 == 0 (k_step_gen.hip)
+hipError_t launch_h_r_from_steer(const RisVecState& s, float* out, hipStream_t st);
 
 // risvec_force_forms(): the test / A/B override of the dispatch rules.  Read by the step selector (plan_step) and
 // launch_colsum only.

@@ -783,8 +783,13 @@ bool theta_by_index_supported(int V, int M);
 // rev: walk the envs backwards (k_step_fused_pipe<..., REV>; forward where the plan has no such kernel: NT)
 hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
                                   bool rev, hipStream_t st);
+// the pipeline's GEN member (k_step_gen.hip): h_r rebuilt from s.steer_ang / s.z_r; the plan's shape has M % 16 == 0.
+// rev: serve each wavefront's groups last first (the pipeline's walk)
+hipError_t launch_step_fused_gen(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
+                                 bool rev, hipStream_t st);
 // 0 / 1: the walk the calling thread's last software-pipeline launch took (risvec_last_pipe_walk)
 int last_pipe_walk();
+void note_pipe_walk(int walk);
 hipError_t launch_gain_pipe(const RisVecState& s, hipStream_t st);
 hipError_t launch_step_fused_lat(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
                                  int n_steps, const RisVecTraj& tj, hipStream_t st);

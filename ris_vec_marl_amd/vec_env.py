@@ -90,6 +90,10 @@ class VecEnviron(ParamAttrs):
         self._t: Dict[str, torch.Tensor] = {}
         self._colsum_valid = False     # c_col matches h_r (set by compute_parms / rebuild_colsum)
         self._steer_valid = False      # h_r is the steering vector compute_parms wrote, z_r its base
+        # tensors["h_r"]._version when compute_parms() last wrote it together with steer_ang (-1: never, or a checkpoint
+        # without steer_ang was loaded): while it has not moved, h_r is exactly what the kernel wrote from steer_ang / z_r
+        # and the fused step is told so (RISVEC_STEP_H_R_STEER_CURRENT)
+        self._h_r_steer_version = -1
         self._ssum_sweeps = 0          # >0: s_sum = sum theta.c of the CURRENT theta, left by that many
                                        # consecutive sweeps (0 = unknown; refreshed every 64 sweeps)
         self._idx_valid = False        # theta_idx = candidate index of every CURRENT theta element (left by a sweep)
@@ -154,6 +158,7 @@ class VecEnviron(ParamAttrs):
         t["z_r"] = z(E, V, 2, dt=torch.float64)        # steering base exp(-j pi angle) per vehicle: h_r[e,v,m] = z^m
         # candidate index of every theta element as the last BCD sweep left it: [E, 32 ceil(M/32)] bytes
         t["theta_idx"] = z(E, (M + 31) // 32 * 32, dt=torch.uint8)
+        t["steer_ang"] = z(E, V, dt=torch.float64)     # the float64 angle every h_r row is a function of (ang_r: its float32)
         s = N.RisVecState()
         s.abi_version = N.ABI_VERSION
         s.struct_bytes = C.sizeof(N.RisVecState)
@@ -161,7 +166,7 @@ class VecEnviron(ParamAttrs):
         s.env_offset = self.env_offset
         for k in ("pos", "dir", "vel", "dist_r", "ang_r", "pl", "h_r", "theta", "b", "gain", "data_buf",
                   "mec_q", "rate", "data_t", "data_p", "reward", "over_power", "obs", "metrics", "power_w", "c_col",
-                  "s_sum", "over_data", "z_r", "theta_idx"):
+                  "s_sum", "over_data", "z_r", "theta_idx", "steer_ang"):
             setattr(s, k, t[k].data_ptr())
         s.h_d = None
         self._cstate = s
@@ -215,6 +220,8 @@ class VecEnviron(ParamAttrs):
             if min(x[0] for x in cands) < 0.96 * max(x[0] for x in cands):
                 break                                  # both levels seen: the faster one is known
         us, keep = min(cands, key=lambda x: x[0])
+        if self._h_r_steer_version == t["h_r"]._version:
+            self._h_r_steer_version = keep._version    # the record follows the allocation
         t["h_r"] = keep
         self._cstate.h_r = keep.data_ptr()
         self.placement = dict(candidates=len(cands), step_kernel_us=[round(x[0], 1) for x in cands], kept_us=round(us, 1))
@@ -313,6 +320,7 @@ class VecEnviron(ParamAttrs):
         N.check(N.load().risvec_geometry(C.byref(self._cstate), C.byref(self._p()), N.stream(self.device)))
         self._colsum_valid = True
         self._steer_valid = True       # h_r[e,v,m] = z_r[e,v]^m from here on
+        self._h_r_steer_version = self._t["h_r"]._version   # kernels write through raw pointers: no bump
         self._ssum_sweeps = 0          # c changed: the cached sum is stale (the candidate indices are not)
 
     def rebuild_colsum(self) -> None:
@@ -381,6 +389,20 @@ class VecEnviron(ParamAttrs):
         if self._idx_current and self._t["theta"]._version == self._idx_current_version:
             return N.STEP_THETA_IDX_CURRENT
         return 0
+
+    def _h_r_steer_flag(self) -> int:
+        """RISVEC_STEP_H_R_STEER_CURRENT while h_r is known to be what compute_parms() wrote from the steer_ang / z_r now
+        in the state: nothing announced a write (rebuild_colsum / invalidate_colsum clear `_steer_valid`) and nothing
+        wrote the tensor or its complex view through torch (that moves `_version`).  Asked on the launch path of the RIS
+        cascade only -- channel_model "free": under a 3GPP model the launchers have already taken the other branch --
+        and only at shapes whose rows are whole 16-element chunks (the others have no rebuilding kernel, and a launch that
+        is a few microseconds long should not pay for the question)."""
+        if self._steer_valid and self._t["h_r"]._version == self._h_r_steer_version:
+            return N.STEP_H_R_STEER_CURRENT
+        return 0
+
+    def _h_r_is_steer(self) -> bool:
+        return self._h_r_steer_flag() != 0
 
     def _bcd_flags(self, reuse_colsum: Optional[bool], step: bool) -> int:
         reuse_c = self._colsum_valid if reuse_colsum is None else bool(reuse_colsum)
@@ -574,6 +596,7 @@ class VecEnviron(ParamAttrs):
         pa, pp, pn, par = N.ptr(a), N.ptr(pt), N.ptr(ng), N.ptr(ar)
         pfd = C.byref(fd) if fd is not None else None
         either = fused and not bcd and not steer       # a launch that may be told "theta_idx matches theta"
+        rows = either and self.M % 16 == 0             # ... and "h_r is what compute_parms() wrote"
 
         def launch() -> None:
             model = self._model(fused, steer, fd) if fused else None
@@ -591,6 +614,8 @@ class VecEnviron(ParamAttrs):
                     flags = self._theta_mode(flags, fused, bcd, steer)
                 elif either:
                     flags |= self._idx_current_flag()
+                    if rows:
+                        flags |= self._h_r_steer_flag()
                 rc = fn(cs, C.byref(self._p()), pa, pp, pn, par, seed, self._steps, flags, stream)
                 if rc:
                     N.check(rc)
@@ -849,6 +874,7 @@ class VecEnviron(ParamAttrs):
         fn3 = N.load().risvec_step_fused_3gpp
         pa, pp, pn, par, pmask = N.ptr(a), N.ptr(pt), N.ptr(ng), N.ptr(ar), N.ptr(mk)
         fz = 1 if fused else 0
+        rows = fused and self.M % 16 == 0
         pfd = C.byref(fd) if fd is not None else None
 
         def launch(done: bool = False, use_mask: bool = True) -> None:
@@ -867,6 +893,8 @@ class VecEnviron(ParamAttrs):
                     self._sync_theta()
                     if not self.lazy_theta:
                         fl |= self._idx_current_flag()
+                        if rows:
+                            fl |= self._h_r_steer_flag()
                 rc = fn(cs, C.byref(self._p()), C.byref(ring), pa, pp, pn, par, seed, self._steps, fl, fz, stream)
             if rc:
                 N.check(rc)
@@ -933,7 +961,7 @@ class VecEnviron(ParamAttrs):
         return False
 
     # ------------------------------------------------------------------ checkpoint
-    _STATE_KEYS = ("pos", "dir", "vel", "dist_r", "ang_r", "pl", "h_r", "z_r", "theta", "gain", "data_buf", "mec_q",
+    _STATE_KEYS = ("pos", "dir", "vel", "dist_r", "ang_r", "pl", "h_r", "z_r", "steer_ang", "theta", "gain", "data_buf", "mec_q",
                    "rate", "data_t", "data_p", "reward", "over_power", "over_data", "obs", "metrics", "power_w")
 
     def state_dict(self) -> Dict[str, object]:
@@ -941,7 +969,7 @@ class VecEnviron(ParamAttrs):
         sd: Dict[str, object] = {k: t[k].detach().cpu().clone() for k in self._STATE_KEYS}
         sd["counters"] = dict(epoch=self._epoch, moves=self._moves, steps=self._steps, chan=self._chan,
                               seed=self.seed, env_offset=self.env_offset, steer_valid=self._steer_valid,
-                              obs_stale=self._obs_stale)
+                              h_r_steer=self._h_r_is_steer(), obs_stale=self._obs_stale)
         return sd
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
@@ -956,12 +984,16 @@ class VecEnviron(ParamAttrs):
                                  % (key, int(c[key]), key, int(mine)))
         t = self.tensors
         for k in self._STATE_KEYS:
-            if k in sd:                # power_w joined the checkpoint in round 2
+            if k in sd:                # power_w joined the checkpoint in round 2, steer_ang with the rebuilt rows
                 t[k].copy_(sd[k])
         self._colsum_valid = False
         self._theta_changed()
         self._epoch, self._moves, self._steps, self._chan = c["epoch"], c["moves"], c["steps"], c["chan"]
         self._steer_valid = bool(c.get("steer_valid", False))      # z_r travels with h_r
+        # ... and so does steer_ang, from the checkpoints that have it: without it the rows cannot be rebuilt until the next
+        # compute_parms() (the copy above moved h_r's version either way)
+        rebuildable = self._steer_valid and bool(c.get("h_r_steer", False)) and "steer_ang" in sd
+        self._h_r_steer_version = t["h_r"]._version if rebuildable else -1
         self._obs_stale = bool(c.get("obs_stale", self._steps == 0))
         self._sarl_obs_mark = None
 
