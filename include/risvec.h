@@ -261,6 +261,10 @@ int risvec_last_pipe_walk(void);
 /* 1 when the calling thread's last step launch rebuilt the h_r rows from state.steer_ang / state.z_r instead of reading
  * them (RISVEC_STEP_H_R_STEER_CURRENT where the plan has a GEN member), else 0. */
 int risvec_last_h_r_rebuilt(void);
+/* Groups of 64 rows that one wavefront served in the calling thread's last step launch when that launch was a GEN member
+ * (risvec_last_h_r_rebuilt() == 1), else 0.  1 = the member without a group loop ran: the launcher picks it exactly when
+ * every wavefront owns one group.  Results and kernel name do not depend on it. */
+int risvec_last_gen_groups_per_wave(void);
 const char *risvec_last_error(void);
 
 /* Forms of a step call, for risvec_step_kernel(): risvec_step, risvec_step_fused, risvec_step_ring (cached / fused),

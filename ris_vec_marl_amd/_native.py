@@ -178,6 +178,7 @@ _PROTOS = {
     "risvec_last_theta_by_index": (C.c_int, []),
     "risvec_last_pipe_walk": (C.c_int, []),
     "risvec_last_h_r_rebuilt": (C.c_int, []),
+    "risvec_last_gen_groups_per_wave": (C.c_int, []),
     "risvec_h_r_from_steer": (C.c_int, [C.POINTER(RisVecState), _FP, _FP]),
     "risvec_step_kernel": (C.c_char_p, [C.POINTER(RisVecState), C.c_uint32, C.c_int32]),
     "risvec_force_forms": (C.c_int, [C.POINTER(RisVecForce)]),
@@ -383,6 +384,12 @@ def last_h_r_rebuilt() -> int:
     """1 if the calling thread's last step launch rebuilt the h_r rows from steer_ang / z_r instead of reading them
     (risvec_last_h_r_rebuilt)."""
     return int(load().risvec_last_h_r_rebuilt())
+
+
+def last_gen_groups_per_wave() -> int:
+    """Groups per wavefront of the calling thread's last step launch if it was a GEN member (1: the one-group member),
+    else 0 (risvec_last_gen_groups_per_wave)."""
+    return int(load().risvec_last_gen_groups_per_wave())
 
 
 def step_kernel(state, flags: int = 0, form: int = FORM_FUSED):

@@ -17,6 +17,18 @@
 // What a pass needs from memory -- the angle and w of the lane's chunk, theta of the envs the pass completes -- is
 // requested one outer iteration ahead (across the group boundary), step()'s per-lane inputs one group ahead as in the
 // reading form.
+//
+// The kernel is bound by vector issue, not by bytes (EXPERIMENTS.md 2026-10-19 b), so what a wavefront issues beside the
+// arithmetic of the result is kept out of it:
+//   * step() reads some 25 pointers of StepArgs and 25 fields of RisVecParams.  Loaded at kernel entry they are live
+//     across the pass loop, more than the scalar registers hold, and the compiler parked them in the lanes of a vector
+//     register (v_writelane / v_readlane, a wait state each).  The passes need none of them, so step() reads them from
+//     the kernel-argument segment AFTER the last pass (late_args below): the kernel takes its arguments as one struct so
+//     that a field's place in the segment is its offsetof.
+//   * ONE: the member for launches in which every wavefront owns one group (the headline: 4 096 groups on 4 096
+//     wavefronts).  No group loop, no second set of step() inputs, no request for "the next group".
+#include <cstddef>
+
 #include "risvec_pipe.hpp"
 
 namespace risvec {
@@ -54,16 +66,41 @@ struct GenFeed<SP, EPO, NIT, true> {
     unsigned k[EPO][NIT];
 };
 
+// The kernel's ONLY parameter, so that the kernel-argument segment is this struct and a field sits at its offsetof.
 // per_wave > 0: a wavefront owns the CONTIGUOUS groups [wid * per_wave, (wid + 1) * per_wave); per_wave = 0: groups
-// wid, wid + nw, ...  TK: theta by index, as in k_step_fused_pipe.
+// wid, wid + nw, ...
 // rev: the wavefront serves the SAME groups, last first -- the pipeline's alternating walk (launch_step: the parity of the
 // step counter), kept so that what a launch touched last (theta or its indices, step()'s inputs: all that is still read)
 // is what the next launch asks for first.  Only the order of the groups turns: nothing inside a group depends on the
 // direction, so it is a run-time argument here, not an instantiation.
-template <int V, int M, class Core, bool TK>
+template <class Core>
+struct GenArgs {
+    Dims d;
+    typename Core::Params P;
+    typename Core::Args A;
+    const double* steer_ang;
+    const double* z_r;
+    int n_groups_total, per_wave, rev;
+};
+
+// The kernel's arguments again, as the segment holds them: the address is taken anew and passed through an empty asm, so
+// the compiler cannot tell these loads from others and issues them HERE (scalar loads: the constant address space
+// survives the cast), not at kernel entry next to the ones the prologue makes from the parameter itself.
+template <class Core>
+__device__ __forceinline__ const GenArgs<Core>& late_args() {
+    static_assert(offsetof(GenArgs<Core>, d) == 0 && std::is_trivially_copyable<GenArgs<Core>>::value,
+                  "the kernel-argument segment must be the struct itself");
+    typedef const __attribute__((address_space(4))) GenArgs<Core>* SegPtr;
+    SegPtr seg = (SegPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(seg));
+    return *(const GenArgs<Core>*)seg;
+}
+
+// TK: theta by index, as in k_step_fused_pipe.  ONE: every wavefront owns one group (group `wid`; per_wave and rev are
+// not read).
+template <int V, int M, class Core, bool TK, bool ONE>
 __global__ void __launch_bounds__(kBlock)
-k_step_fused_gen(Dims d, typename Core::Params P, typename Core::Args A, const double* __restrict__ steer_ang,
-                 const double* __restrict__ z_r, int n_groups_total, int per_wave, int rev) {
+k_step_fused_gen(GenArgs<Core> KA) {
     using In = typename Core::In;
     using S = GenShape<V, M>;
     constexpr int VP = S::VP, EPW = S::EPW, NP = S::NP, G = S::G, NIT = S::NIT, VPP = S::VPP;
@@ -75,13 +112,18 @@ k_step_fused_gen(Dims d, typename Core::Params P, typename Core::Args A, const d
     __shared__ float2 s_ph[TK ? kBlock / kWave : 1][16];
     __shared__ float4 s_stage[kBlock / kWave][S::STAGE];
 
+    // the prologue's view of the arguments: what is named here is loaded at entry.  step() goes through late_args().
+    const Dims& d = KA.d;
+    const typename Core::Args& A = KA.A;
+    const double* __restrict__ steer_ang = KA.steer_ang;
+    const int n_groups_total = KA.n_groups_total;
+
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int gl = lane % G, gv = lane / G;
     const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / kWave) + wave);
-    const int nw = gridDim.x * (kBlock / kWave);
     const float4* __restrict__ t4 = reinterpret_cast<const float4*>(A.theta);
     const float4* __restrict__ b4 = reinterpret_cast<const float4*>(A.b);
-    const double2* __restrict__ z2 = reinterpret_cast<const double2*>(z_r);
+    const double2* __restrict__ z2 = reinterpret_cast<const double2*>(KA.z_r);
     const int e_last = d.E - 1;
     const int row_last = d.E * V - 1;
     float4 bq[NIT];
@@ -133,111 +175,156 @@ k_step_fused_gen(Dims d, typename Core::Params P, typename Core::Args A, const d
         }
     };
 
-    const int stride = per_wave > 0 ? 1 : nw;
-    int grp = per_wave > 0 ? wid * per_wave : wid;
-    int grp_end = per_wave > 0 ? grp + per_wave : n_groups_total;
-    grp_end = grp_end < n_groups_total ? grp_end : n_groups_total;
-    if constexpr (TK) {
-        RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b), "s"(n_groups_total),
-                                "s"(per_wave), "s"(d.E));
-    } else {
-        RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave), "s"(d.E));
-    }
-    if (grp >= grp_end) return;                            // whole wave: no cross-lane op is skipped
-    const int grp_first = grp;
-    if (rev) {                                             // a few scalar adds: a wavefront owns a handful of groups
-        while (grp + stride < grp_end) grp += stride;
-    }
-    const int step = rev ? -stride : stride;
-    Feed cur;
-    load_feed(cur, grp, 0);
-    if constexpr (TK) {
-        theta_table_fill(s_ph[wave], lane);
-        __builtin_amdgcn_wave_barrier();
-    }
-    const int v_mine = lane % VP;
-
-    auto do_group = [&](int g_cur, const In& in, In& in_nx) {
-        // (unconditional prefetches, as in the reading form: a wave on its last group asks for group 0's)
-        const int g_nx = g_cur + step;
-        const int nxt = (g_nx >= grp_first && g_nx < grp_end) ? g_nx : 0;
-        const int e_mine = g_cur * EPW + lane / VP;
-        const bool active = e_mine < d.E;
-        Core::hold(in);
-
-#pragma unroll 1
-        for (int o = 0; o < NO; ++o) {
-            Feed nx;
-            if (o + 1 < NO) load_feed(nx, g_cur, o + 1);
-            else load_feed(nx, nxt, 0);
-            float2 w0[NIT], w1[NIT];
+    // outer iteration `o` of a group on the feed `cur`: SP passes, each a stage of 64 chunks made and consumed
+    auto do_outer = [&](int o, const Feed& cur) {
+        float2 w0[NIT], w1[NIT];
 #pragma unroll
-            for (int sp = 0; sp < SP; ++sp) {
-                float4 q[kGeoChunk / 2];
-                steer_chunk(cur.ang[sp], cur.w[sp].x, cur.w[sp].y, p_m0, q);
+        for (int sp = 0; sp < SP; ++sp) {
+            float4 q[kGeoChunk / 2];
+            steer_chunk(cur.ang[sp], cur.w[sp].x, cur.w[sp].y, p_m0, q);
 #pragma unroll
-                for (int k = 0; k < kGeoChunk / 2; ++k) p_dst[k] = q[k];
-                __builtin_amdgcn_wave_barrier();           // the stage's writes -> its reads (same wave: in order)
+            for (int k = 0; k < kGeoChunk / 2; ++k) p_dst[k] = q[k];
+            __builtin_amdgcn_wave_barrier();           // the stage's writes -> its reads (same wave: in order)
 #pragma unroll
-                for (int ul = 0; ul < UPP; ++ul) {
-                    const int uo = sp * UPP + ul;          // unit within the outer iteration
-                    const int c = uo % CHUNKS, ie = uo / CHUNKS;
-                    if (c == 0) {
+            for (int ul = 0; ul < UPP; ++ul) {
+                const int uo = sp * UPP + ul;          // unit within the outer iteration
+                const int c = uo % CHUNKS, ie = uo / CHUNKS;
+                if (c == 0) {
 #pragma unroll
-                        for (int it = 0; it < NIT; ++it) {
-                            float2 t0, t1;
-                            if constexpr (TK) {
-                                t0 = s_ph[wave][cur.k[ie][it] & 15u];
-                                t1 = s_ph[wave][(cur.k[ie][it] >> 8) & 15u];
-                            } else {
-                                t0 = make_float2(cur.t[ie][it].x, cur.t[ie][it].y);
-                                t1 = make_float2(cur.t[ie][it].z, cur.t[ie][it].w);
-                            }
-                            w0[it] = cmul(t0, make_float2(bq[it].x, bq[it].y));
-                            w1[it] = cmul(t1, make_float2(bq[it].z, bq[it].w));
+                    for (int it = 0; it < NIT; ++it) {
+                        float2 t0, t1;
+                        if constexpr (TK) {
+                            t0 = s_ph[wave][cur.k[ie][it] & 15u];
+                            t1 = s_ph[wave][(cur.k[ie][it] >> 8) & 15u];
+                        } else {
+                            t0 = make_float2(cur.t[ie][it].x, cur.t[ie][it].y);
+                            t1 = make_float2(cur.t[ie][it].z, cur.t[ie][it].w);
                         }
-                    }
-                    float val[8];
-#pragma unroll
-                    for (int pc = 0; pc < PC; ++pc) {
-                        float2 acc = make_float2(0.f, 0.f);
-#pragma unroll
-                        for (int it = 0; it < NIT; ++it) {
-                            const float4 h = c_src[it][((ul * RPU + pc * VPP) * NCH) * (kGeoChunk / 2 + 1)];
-                            acc = cfma(make_float2(h.x, h.y), w0[it], acc);
-                            acc = cfma(make_float2(h.z, h.w), w1[it], acc);
-                        }
-                        val[2 * pc] = acc.x;
-                        val[2 * pc + 1] = acc.y;
-                    }
-                    treduce<K, G / 2>(val, gl);
-                    if (gl % S::WSTRIDE == 0) {
-                        const int j = gl / S::WSTRIDE;             // value index = (row-in-unit, re/im)
-                        const int v = (c * PC + (j >> 1)) * VPP + gv;
-                        const int i = o * EPO + ie;                // env of the group
-                        s_img[wave][(i * VP + v) * 2 + (j & 1)] = val[0];
+                        w0[it] = cmul(t0, make_float2(bq[it].x, bq[it].y));
+                        w1[it] = cmul(t1, make_float2(bq[it].z, bq[it].w));
                     }
                 }
-                __builtin_amdgcn_wave_barrier();           // the stage's reads -> the next pass's writes
+                float val[8];
+#pragma unroll
+                for (int pc = 0; pc < PC; ++pc) {
+                    float2 acc = make_float2(0.f, 0.f);
+#pragma unroll
+                    for (int it = 0; it < NIT; ++it) {
+                        const float4 h = c_src[it][((ul * RPU + pc * VPP) * NCH) * (kGeoChunk / 2 + 1)];
+                        acc = cfma(make_float2(h.x, h.y), w0[it], acc);
+                        acc = cfma(make_float2(h.z, h.w), w1[it], acc);
+                    }
+                    val[2 * pc] = acc.x;
+                    val[2 * pc + 1] = acc.y;
+                }
+                treduce<K, G / 2>(val, gl);
+                if (gl % S::WSTRIDE == 0) {
+                    const int j = gl / S::WSTRIDE;             // value index = (row-in-unit, re/im)
+                    const int v = (c * PC + (j >> 1)) * VPP + gv;
+                    const int i = o * EPO + ie;                // env of the group
+                    s_img[wave][(i * VP + v) * 2 + (j & 1)] = val[0];
+                }
             }
-            cur = nx;
+            __builtin_amdgcn_wave_barrier();           // the stage's reads -> the next pass's writes
         }
-        in_nx = Core::load(d, A, nxt * EPW + lane / VP, v_mine, nxt * EPW + lane / VP < d.E);
-
-        __builtin_amdgcn_wave_barrier();
-        const float2 img = *reinterpret_cast<const float2*>(&s_img[wave][lane * 2]);
-        Core::template run<VP>(d, P, A, e_mine, v_mine, active, img, in);
-        __builtin_amdgcn_wave_barrier();
     };
 
-    In inA = Core::load(d, A, grp * EPW + lane / VP, v_mine, grp * EPW + lane / VP < d.E), inB;
-    while (true) {
-        do_group(grp, inA, inB);
-        grp += step;
-        if (grp < grp_first || grp >= grp_end) break;
-        do_group(grp, inB, inA);
-        grp += step;
-        if (grp < grp_first || grp >= grp_end) break;
+    const int v_mine = lane % VP;
+
+    if constexpr (ONE) {
+        if constexpr (TK) {
+            RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
+                                    "s"(n_groups_total), "s"(d.E));
+        } else {
+            RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E));
+        }
+        const int grp = wid;
+        if (grp >= n_groups_total) return;                     // whole wave: no cross-lane op is skipped
+        Feed cur;
+        load_feed(cur, grp, 0);
+        if constexpr (TK) {
+            theta_table_fill(s_ph[wave], lane);
+            __builtin_amdgcn_wave_barrier();
+        }
+        const int e_mine = grp * EPW + lane / VP;
+        const bool active = e_mine < d.E;
+        const In in = Core::load(d, A, e_mine, v_mine, active);
+        Core::hold(in);
+        // the last outer iteration is peeled: nothing is requested behind it
+#pragma unroll 1
+        for (int o = 0; o + 1 < NO; ++o) {
+            Feed nx;
+            load_feed(nx, grp, o + 1);
+            do_outer(o, cur);
+            cur = nx;
+        }
+        do_outer(NO - 1, cur);
+
+        const GenArgs<Core>& L = late_args<Core>();
+        __builtin_amdgcn_wave_barrier();
+        const float2 img = *reinterpret_cast<const float2*>(&s_img[wave][lane * 2]);
+        Core::template run<VP>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
+    } else {
+        const int per_wave = KA.per_wave;
+        const int nw = gridDim.x * (kBlock / kWave);
+        const int stride = per_wave > 0 ? 1 : nw;
+        int grp = per_wave > 0 ? wid * per_wave : wid;
+        int grp_end = per_wave > 0 ? grp + per_wave : n_groups_total;
+        grp_end = grp_end < n_groups_total ? grp_end : n_groups_total;
+        if constexpr (TK) {
+            RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
+                                    "s"(n_groups_total), "s"(per_wave), "s"(d.E));
+        } else {
+            RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave),
+                                    "s"(d.E));
+        }
+        if (grp >= grp_end) return;                            // whole wave: no cross-lane op is skipped
+        const int grp_first = grp;
+        if (KA.rev) {                                          // a few scalar adds: a wavefront owns a handful of groups
+            while (grp + stride < grp_end) grp += stride;
+        }
+        const int step = KA.rev ? -stride : stride;
+        Feed cur;
+        load_feed(cur, grp, 0);
+        if constexpr (TK) {
+            theta_table_fill(s_ph[wave], lane);
+            __builtin_amdgcn_wave_barrier();
+        }
+
+        auto do_group = [&](int g_cur, const In& in, In& in_nx) {
+            // (unconditional prefetches, as in the reading form: a wave on its last group asks for group 0's)
+            const int g_nx = g_cur + step;
+            const int nxt = (g_nx >= grp_first && g_nx < grp_end) ? g_nx : 0;
+            const int e_mine = g_cur * EPW + lane / VP;
+            const bool active = e_mine < d.E;
+            Core::hold(in);
+
+#pragma unroll 1
+            for (int o = 0; o < NO; ++o) {
+                Feed nx;
+                if (o + 1 < NO) load_feed(nx, g_cur, o + 1);
+                else load_feed(nx, nxt, 0);
+                do_outer(o, cur);
+                cur = nx;
+            }
+            const GenArgs<Core>& L = late_args<Core>();
+            in_nx = Core::load(L.d, L.A, nxt * EPW + lane / VP, v_mine, nxt * EPW + lane / VP < L.d.E);
+
+            __builtin_amdgcn_wave_barrier();
+            const float2 img = *reinterpret_cast<const float2*>(&s_img[wave][lane * 2]);
+            Core::template run<VP>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
+            __builtin_amdgcn_wave_barrier();
+        };
+
+        In inA = Core::load(d, A, grp * EPW + lane / VP, v_mine, grp * EPW + lane / VP < d.E), inB;
+        while (true) {
+            do_group(grp, inA, inB);
+            grp += step;
+            if (grp < grp_first || grp >= grp_end) break;
+            do_group(grp, inB, inA);
+            grp += step;
+            if (grp < grp_first || grp >= grp_end) break;
+        }
     }
 }
 
@@ -245,6 +332,9 @@ k_step_fused_gen(Dims d, typename Core::Params P, typename Core::Args A, const d
 // float64 chain of a pass is long and dependent (one sincospi, 15 rotations): four wavefronts per SIMD cover its
 // latency where the reading form's two covered a stream.
 constexpr int kGenWavesPerCu = 16;
+
+// risvec_last_gen_groups_per_wave(): the groups per wavefront of the calling thread's last GEN launch
+static thread_local int g_gen_per_wave = 0;
 
 template <int V, int M, class Core>
 static hipError_t launch_gen(const RisVecState& s, const typename Core::Params& p, const typename Core::Args& a, bool rev,
@@ -259,14 +349,23 @@ static hipError_t launch_gen(const RisVecState& s, const typename Core::Params& 
     want_waves = (n_groups + per_wave - 1) / per_wave;
     const unsigned grid = (unsigned)((want_waves + wpb - 1) / wpb);
     const int contiguous = forced_waves > 0 ? (int)per_wave : 0;
-    auto go = [&](auto knl) {
-        hipLaunchKernelGGL(knl, dim3(grid), dim3(kBlock), 0, st, dims_of(s), p, a, s.steer_ang, s.z_r, n_groups, contiguous,
-                           rev ? 1 : 0);
-    };
-    if (a.theta_k != nullptr) go(k_step_fused_gen<V, M, Core, true>);
-    else go(k_step_fused_gen<V, M, Core, false>);
+    const GenArgs<Core> ka{dims_of(s), p, a, s.steer_ang, s.z_r, n_groups, contiguous, rev ? 1 : 0};
+    auto go = [&](auto knl) { hipLaunchKernelGGL(knl, dim3(grid), dim3(kBlock), 0, st, ka); };
+    // one group per wavefront (then the grid covers the groups, whichever way they are dealt): the member without a
+    // group loop
+    const bool one = per_wave == 1;
+    if (a.theta_k != nullptr) {
+        if (one) go(k_step_fused_gen<V, M, Core, true, true>);
+        else go(k_step_fused_gen<V, M, Core, true, false>);
+    } else {
+        if (one) go(k_step_fused_gen<V, M, Core, false, true>);
+        else go(k_step_fused_gen<V, M, Core, false, false>);
+    }
+    g_gen_per_wave = (int)per_wave;
     return hipGetLastError();
 }
+
+int last_gen_launch_groups_per_wave() { return g_gen_per_wave; }
 
 // the shapes whose rows are whole chunks have GEN members; the others keep reading
 template <int V, int M, bool WHOLE = (M % kGeoChunk == 0)>

@@ -227,6 +227,8 @@ int risvec_last_pipe_walk(void) { return risvec::last_pipe_walk(); }
 
 int risvec_last_h_r_rebuilt(void) { return g_h_r_rebuilt; }
 
+int risvec_last_gen_groups_per_wave(void) { return g_h_r_rebuilt ? risvec::last_gen_launch_groups_per_wave() : 0; }
+
 const char* risvec_last_error(void) { return g_err; }
 
 const char* risvec_step_kernel(const RisVecState* s, uint32_t flags, int32_t form) {

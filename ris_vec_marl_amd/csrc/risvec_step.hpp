@@ -790,6 +790,8 @@ hipError_t launch_step_fused_gen(const RisVecState& s, const RisVecParams& p, co
 // 0 / 1: the walk the calling thread's last software-pipeline launch took (risvec_last_pipe_walk)
 int last_pipe_walk();
 void note_pipe_walk(int walk);
+// groups per wavefront of the calling thread's last launch_step_fused_gen (1: the one-group member ran)
+int last_gen_launch_groups_per_wave();
 hipError_t launch_gain_pipe(const RisVecState& s, hipStream_t st);
 hipError_t launch_step_fused_lat(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
                                  int n_steps, const RisVecTraj& tj, hipStream_t st);
