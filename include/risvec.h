@@ -1009,6 +1009,63 @@ int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_hea
                         const float *ln_w, const float *ln_b, const float *Wh, const float *bh, float *heads,
                         risvec_stream_t stream);
 
+/* ---- the optimiser step: clip_grad_norm_ -> torch.optim.Adam.step() -> the Polyak blend, for many networks ----------
+ * A GROUP is one network: one clip_grad_norm_ scope and one torch.optim.Adam instance of the reference
+ * (global_sac_critic.py:364-370 and :246-249, sac_agent.py:296-303).  One call serves n_groups groups over n_tensors
+ * tensors in two launches (k_adam_sqsum, k_adam_step), or in one (k_adam_step) without RISVEC_ADAM_CLIP.  The
+ * descriptors live in DEVICE memory that the caller owns, so neither count is bounded by a kernel's argument block; the
+ * caller also passes the HOST arrays it uploaded them from, which is what this entry point checks.
+ *
+ * A workgroup owns one chunk of RISVEC_ADAM_CHUNK consecutive elements of one tensor.  Tensors are listed group by group
+ * (tensors[i].group never decreases; every group has a tensor); tensors[i].first_block is the sum of
+ * ceil(numel / RISVEC_ADAM_CHUNK) over the tensors before i, groups[g].first_block / n_blocks the range of group g, and
+ * block_tensor[b] the tensor of workgroup b (n_blocks int32 in device memory).
+ *
+ * With RISVEC_ADAM_CLIP, partials[b] (n_blocks doubles) takes the sum of fl32(grad^2) over workgroup b's chunk, added up
+ * in float64; every workgroup of k_adam_step then adds its group's partials in one fixed order, so the result is the
+ * same bits in all of them and from run to run (no atomics), and
+ *     norm = fl32(sqrt(sum))    coef = min(max_norm / (norm + 1e-6), 1)   in float32, NaN kept (error_if_nonfinite=False)
+ * norms[g] = norm is clip_grad_norm_'s return value.  A group with max_norm < 0 is not clipped (coef = 1).  Per element,
+ * every operation rounded to float32 on its own, never fused:
+ *     g = grad * coef;  if (weight_decay != 0) g = g + weight_decay * param          (coupled L2 decay)
+ *     m = m + (g - m) * fl32(1 - beta1)
+ *     v = v * fl32(beta2) + (fl32(1 - beta2) * g) * g
+ *     param = param - (step_size * m) / (sqrt(v) / bc2_sqrt + eps)
+ *     target = fl32(tau * param) + fl32(one_minus_tau * target)       with RISVEC_ADAM_BLEND, where target != NULL
+ * step_size = fl32(lr / (1 - beta1^t)) and bc2_sqrt = fl32(sqrt(1 - beta2^t)), both formed in double.  `/` and sqrt are
+ * correctly rounded.  With RISVEC_ADAM_WRITE_GRAD, grad * coef is written back as clip_grad_norm_ does in place.
+ * A descriptor whose pointers all share their offset from a 16-byte boundary is served 16 bytes at a time.
+ *
+ * A NULL table, a table that is not 16-byte aligned, counts out of range, a block layout that does not follow from the
+ * numels, a NULL / misaligned / aliased tensor pointer, non-finite lr / eps / tau, weight_decay < 0, beta1 / beta2
+ * outside [0, 1), t < 1 and too small a workspace return RISVEC_ERR_ARG (counts: RISVEC_ERR_SHAPE), all before any
+ * device is touched. */
+#define RISVEC_ADAM_CHUNK 4096
+enum { RISVEC_ADAM_CLIP = 1, RISVEC_ADAM_WRITE_GRAD = 2, RISVEC_ADAM_BLEND = 4 };
+typedef struct RisVecAdamTensor {
+    float *param, *grad, *exp_avg, *exp_avg_sq;
+    float *target;         /* may be NULL */
+    int64_t numel;
+    int32_t group;
+    int32_t first_block;
+    int64_t reserved;      /* 64 bytes */
+} RisVecAdamTensor;
+typedef struct RisVecAdamGroup {
+    double lr;
+    float weight_decay;
+    float max_norm;        /* < 0: this group is not clipped */
+    int32_t first_block;
+    int32_t n_blocks;
+    int64_t reserved;      /* 32 bytes */
+} RisVecAdamGroup;
+/* bytes of `partials` for a call of n_blocks workgroups (0 for n_blocks < 1) */
+size_t risvec_adam_workspace(int32_t n_blocks);
+int risvec_adam_step(int32_t n_tensors, int32_t n_groups, int32_t n_blocks, const RisVecAdamTensor *tensors,
+                     const RisVecAdamGroup *groups, const int32_t *block_tensor, const RisVecAdamTensor *tensors_host,
+                     const RisVecAdamGroup *groups_host, double beta1, double beta2, double eps, int64_t t, float tau,
+                     float one_minus_tau, uint32_t flags, double *partials, size_t partials_bytes, float *norms,
+                     risvec_stream_t stream);
+
 /* ---- f4: the per-episode metrics sink --------------------------------------------------
  * The driver sums the `last_*` scalars, the clipped per-user rewards and the equivalent powers step by
  * step in Python floats and turns them into per-episode scalars for TensorBoard (marl_train_bcd.py,

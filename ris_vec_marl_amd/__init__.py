@@ -18,6 +18,7 @@ from .critic import (BatchedCritic, ddpg_soft_update, ddpg_td_target, pack_criti
                      unpack_critic_weights)
 from .marl_critic import BatchedTwinCritic, pack_marl_critic_weights, pack_marl_critic_weights_device
 from .local_critics import BatchedLocalCritics
+from .optim import BatchedAdam
 from .metrics import EpisodeMeter, ScalarSink
 from . import dist
 
@@ -26,4 +27,4 @@ __all__ = ["EnvParams", "apply_yaml_config", "load_yaml", "reference_lanes", "po
            "sarl_observe", "OUNoise", "SarlReplayBuffer", "NomaConfig", "NomaGrouper", "anneal_topk", "VecReplayBuffer",
            "marshal_actions", "BatchedPolicy", "BatchedActor", "pack_actor_weights_device", "BatchedCritic",
            "ddpg_td_target", "ddpg_soft_update", "pack_critic_weights", "pack_critic_weights_device", "unpack_critic_weights", "BatchedTwinCritic",
-           "pack_marl_critic_weights", "pack_marl_critic_weights_device", "BatchedLocalCritics", "EpisodeMeter", "ScalarSink", "dist"]
+           "pack_marl_critic_weights", "pack_marl_critic_weights_device", "BatchedLocalCritics", "BatchedAdam", "EpisodeMeter", "ScalarSink", "dist"]

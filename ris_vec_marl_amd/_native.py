@@ -165,6 +165,19 @@ class RisVecMarlCriticPackNet(C.Structure):
     _fields_ = [("W1", _FP), ("W2", _FP), ("W3", _FP), ("wstream", _FP), ("wstream_bytes", C.c_int64), ("scales", _FP)]
 
 
+class RisVecAdamTensor(C.Structure):
+    _fields_ = [("param", _FP), ("grad", _FP), ("exp_avg", _FP), ("exp_avg_sq", _FP), ("target", _FP), ("numel", C.c_int64),
+                ("group", C.c_int32), ("first_block", C.c_int32), ("reserved", C.c_int64)]
+
+
+class RisVecAdamGroup(C.Structure):
+    _fields_ = [("lr", C.c_double), ("weight_decay", C.c_float), ("max_norm", C.c_float), ("first_block", C.c_int32),
+                ("n_blocks", C.c_int32), ("reserved", C.c_int64)]
+
+
+ADAM_CHUNK = 4096        # RISVEC_ADAM_CHUNK: elements per workgroup of the optimiser kernels
+ADAM_CLIP, ADAM_WRITE_GRAD, ADAM_BLEND = 1, 2, 4
+
 NOMA_MAX_VEH = 16
 NOMA_HAS_LAST, NOMA_UNSTICK_USED, NOMA_HAS_GROUPS = 1, 2, 4
 
@@ -262,6 +275,9 @@ _PROTOS = {
     "risvec_local_critics_supported": (C.c_int, [C.c_int32] * 6),
     "risvec_local_critics": (C.c_int, [C.c_int32] * 8 + [_FP] * 7 + [C.c_float] + [_FP] * 7),
     "risvec_soft_update": (C.c_int, [C.c_int32, _FP, _FP, _FP, C.c_float, C.c_float, _FP]),
+    "risvec_adam_workspace": (C.c_size_t, [C.c_int32]),
+    "risvec_adam_step": (C.c_int, [C.c_int32] * 3 + [_FP] * 5 + [C.c_double] * 3 + [C.c_int64, C.c_float, C.c_float, C.c_uint32,
+                                   _FP, C.c_size_t, _FP, _FP]),
     "risvec_policy_heads": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "risvec_policy_sample": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, C.c_uint64, C.c_uint32,
                                        C.c_float, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),

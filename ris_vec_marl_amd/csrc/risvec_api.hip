@@ -1276,6 +1276,98 @@ int risvec_soft_update(int32_t n_tensors, const float* const* online, float* con
     return finish(fn, risvec::launch_soft_update(n_tensors, online, target, numel, tau, one_minus_tau, (hipStream_t)stream));
 }
 
+size_t risvec_adam_workspace(int32_t n_blocks) { return n_blocks < 1 ? 0 : (size_t)n_blocks * sizeof(double); }
+
+int risvec_adam_step(int32_t n_tensors, int32_t n_groups, int32_t n_blocks, const RisVecAdamTensor* tensors,
+                     const RisVecAdamGroup* groups, const int32_t* block_tensor, const RisVecAdamTensor* tensors_host,
+                     const RisVecAdamGroup* groups_host, double beta1, double beta2, double eps, int64_t t, float tau,
+                     float one_minus_tau, uint32_t flags, double* partials, size_t partials_bytes, float* norms,
+                     risvec_stream_t stream) {
+    const char* fn = "risvec_adam_step";
+    static_assert(sizeof(RisVecAdamTensor) == 64 && sizeof(RisVecAdamGroup) == 32, "descriptor layout");
+    if (n_tensors < 1 || n_tensors > (1 << 20))
+        return fail(RISVEC_ERR_SHAPE, "%s: n_tensors=%d outside [1, 2^20]", fn, n_tensors);
+    if (n_groups < 1 || n_groups > n_tensors)
+        return fail(RISVEC_ERR_SHAPE, "%s: n_groups=%d outside [1, n_tensors=%d]", fn, n_groups, n_tensors);
+    if (n_blocks < n_tensors) return fail(RISVEC_ERR_SHAPE, "%s: n_blocks=%d is below n_tensors=%d", fn, n_blocks, n_tensors);
+    REQ_PTR(tensors, "tensors"); REQ_PTR(groups, "groups"); REQ_PTR(block_tensor, "block_tensor");
+    if (!tensors_host) return fail(RISVEC_ERR_ARG, "%s: tensors_host is NULL", fn);
+    if (!groups_host) return fail(RISVEC_ERR_ARG, "%s: groups_host is NULL", fn);
+    if (flags & ~(uint32_t)(RISVEC_ADAM_CLIP | RISVEC_ADAM_WRITE_GRAD | RISVEC_ADAM_BLEND))
+        return fail(RISVEC_ERR_ARG, "%s: flags 0x%x: only CLIP / WRITE_GRAD / BLEND are accepted", fn, flags);
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(RISVEC_ERR_ARG, "%s: beta1=%g outside [0, 1)", fn, beta1);
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(RISVEC_ERR_ARG, "%s: beta2=%g outside [0, 1)", fn, beta2);
+    if (!std::isfinite(eps) || eps < 0.0) return fail(RISVEC_ERR_ARG, "%s: eps=%g must be finite and >= 0", fn, eps);
+    if (t < 1) return fail(RISVEC_ERR_ARG, "%s: t=%lld must be >= 1", fn, (long long)t);
+    const bool blend = (flags & RISVEC_ADAM_BLEND) != 0, clip = (flags & RISVEC_ADAM_CLIP) != 0;
+    if (blend && (!std::isfinite(tau) || !std::isfinite(one_minus_tau)))
+        return fail(RISVEC_ERR_ARG, "%s: tau=%g and one_minus_tau=%g must be finite", fn, (double)tau, (double)one_minus_tau);
+    int group = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        const RisVecAdamTensor& d = tensors_host[i];
+        if (d.numel < 1 || d.numel > (1LL << 40))
+            return fail(RISVEC_ERR_SHAPE, "%s: tensors[%d].numel=%lld outside [1, 2^40]", fn, i, (long long)d.numel);
+        if ((d.group != group && d.group != group + 1) || (i == 0 && d.group != 0) || d.group >= n_groups)
+            return fail(RISVEC_ERR_ARG, "%s: tensors[%d].group=%d (tensors are listed group by group from 0, none empty, "
+                        "n_groups=%d)", fn, i, d.group, n_groups);
+        group = d.group;
+    }
+    if (group != n_groups - 1) return fail(RISVEC_ERR_ARG, "%s: %d groups have tensors, n_groups=%d", fn, group + 1, n_groups);
+    long long blocks = 0;
+    group = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        const RisVecAdamTensor& d = tensors_host[i];
+        const bool opens = i == 0 || d.group != group;
+        group = d.group;
+        if (opens && groups_host[group].first_block != blocks)
+            return fail(RISVEC_ERR_ARG, "%s: groups[%d].first_block=%d, its tensors start at workgroup %lld", fn, group,
+                        groups_host[group].first_block, blocks);
+        if (d.first_block != blocks)
+            return fail(RISVEC_ERR_ARG, "%s: tensors[%d].first_block=%d, the numels before it give %lld", fn, i, d.first_block,
+                        blocks);
+        const struct { const float* p; const char* name; } ptrs[] = {{d.param, "param"}, {d.grad, "grad"}, {d.exp_avg, "exp_avg"},
+                                                                     {d.exp_avg_sq, "exp_avg_sq"}, {d.target, "target"}};
+        for (int k = 0; k < 5; ++k) {
+            if (!ptrs[k].p && k < 4) return fail(RISVEC_ERR_ARG, "%s: tensors[%d].%s is NULL", fn, i, ptrs[k].name);
+            if (reinterpret_cast<uintptr_t>(ptrs[k].p) & 3u)
+                return fail(RISVEC_ERR_ARG, "%s: tensors[%d].%s is not 4-byte aligned", fn, i, ptrs[k].name);
+            for (int j = 0; j < k; ++j)
+                if (ptrs[k].p && ptrs[k].p == ptrs[j].p)
+                    return fail(RISVEC_ERR_ARG, "%s: tensors[%d].%s and .%s are the same tensor", fn, i, ptrs[j].name, ptrs[k].name);
+        }
+        blocks += (d.numel + RISVEC_ADAM_CHUNK - 1) / RISVEC_ADAM_CHUNK;
+        if (blocks > 0x7fffffffLL) return fail(RISVEC_ERR_SHAPE, "%s: more than 2^31 - 1 workgroups", fn);
+        const bool closes = i + 1 == n_tensors || tensors_host[i + 1].group != group;
+        if (closes && groups_host[group].n_blocks != blocks - groups_host[group].first_block)
+            return fail(RISVEC_ERR_ARG, "%s: groups[%d].n_blocks=%d, its tensors take %lld workgroups", fn, group,
+                        groups_host[group].n_blocks, blocks - groups_host[group].first_block);
+    }
+    if (blocks != n_blocks) return fail(RISVEC_ERR_SHAPE, "%s: n_blocks=%d, the numels give %lld", fn, n_blocks, blocks);
+    for (int g = 0; g < n_groups; ++g) {
+        const RisVecAdamGroup& G = groups_host[g];
+        if (!std::isfinite(G.lr) || G.lr < 0.0) return fail(RISVEC_ERR_ARG, "%s: groups[%d].lr=%g must be finite and >= 0", fn, g, G.lr);
+        if (!std::isfinite(G.weight_decay) || G.weight_decay < 0.f)
+            return fail(RISVEC_ERR_ARG, "%s: groups[%d].weight_decay=%g must be finite and >= 0", fn, g, (double)G.weight_decay);
+        if (std::isnan(G.max_norm)) return fail(RISVEC_ERR_ARG, "%s: groups[%d].max_norm is NaN (< 0 disables clipping)", fn, g);
+    }
+    if (clip) {
+        REQ_PTR(partials, "partials");
+        if (!norms) return fail(RISVEC_ERR_ARG, "%s: norms is NULL", fn);
+        if (reinterpret_cast<uintptr_t>(norms) & 3u) return fail(RISVEC_ERR_ARG, "%s: norms is not 4-byte aligned", fn);
+        if (partials_bytes < risvec_adam_workspace(n_blocks))
+            return fail(RISVEC_ERR_ARG, "%s: partials_bytes=%zu, this call needs %zu (risvec_adam_workspace)", fn, partials_bytes,
+                        risvec_adam_workspace(n_blocks));
+    }
+    risvec::AdamLaunch a{};
+    a.tensors = tensors; a.groups = groups; a.block_tensor = block_tensor; a.partials = partials; a.norms = norms;
+    a.bc1 = 1.0 - std::pow(beta1, (double)t);                 // torch/optim/adam.py: 1 - beta1 ** step, in double
+    a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)t));
+    a.omb1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
+    a.tau = tau; a.omt = one_minus_tau;
+    a.n_tensors = n_tensors; a.n_groups = n_groups; a.n_blocks = n_blocks; a.flags = flags;
+    return finish(fn, risvec::launch_adam_step(a, (hipStream_t)stream));
+}
+
 int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_heads, const float* g, const float* b2,
                         const float* ln_w, const float* ln_b, const float* Wh, const float* bh, float* heads,
                         risvec_stream_t stream) {

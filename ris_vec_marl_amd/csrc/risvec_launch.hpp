@@ -184,6 +184,22 @@ constexpr int kSoftUpdateMax = 32;
 hipError_t launch_soft_update(int n_tensors, const float* const* online, float* const* target, const int64_t* numel,
                               float tau, float one_minus_tau, hipStream_t st);
 
+// clip_grad_norm_ + Adam + the target blend of n_groups networks over n_tensors tensors in two launches, one without
+// RISVEC_ADAM_CLIP (k_adam.hip).  All pointers are device memory; a workgroup owns kAdamChunk elements of one tensor.
+constexpr int kAdamChunk = RISVEC_ADAM_CHUNK;
+struct AdamLaunch {
+    const RisVecAdamTensor* tensors;
+    const RisVecAdamGroup* groups;
+    const int32_t* block_tensor;
+    double* partials;
+    float* norms;
+    double bc1;
+    float omb1, b2, omb2, bc2_sqrt, eps, tau, omt;
+    int n_tensors, n_groups, n_blocks;
+    uint32_t flags;
+};
+hipError_t launch_adam_step(const AdamLaunch& a, hipStream_t st);
+
 int episode_partial_rows(int E);
 hipError_t launch_episode_clear(int E, int V, double* acc, hipStream_t st);
 hipError_t launch_episode_accumulate(int E, int V, const float* metrics, const float* reward, const float* power_w,
