@@ -80,6 +80,11 @@ def td_args(reward, done, gamma, n: int, device) -> None:
     if reward is None:
         raise ValueError("td_target: reward must be a contiguous float32 tensor of shape (%d,) on %s" % (n, device))
     N.in_place(reward, torch.float32, (n,), "td_target: reward", device)
+    done_gamma_args(done, gamma, n, device)
+
+
+def done_gamma_args(done, gamma, n: int, device) -> None:
+    """The checks of `td_target`'s done [n], read in place, and gamma."""
     if (not isinstance(done, torch.Tensor) or done.dtype not in (torch.bool, torch.uint8) or done.device != device
             or not done.is_contiguous() or tuple(done.shape) != (n,)):
         raise ValueError("td_target: done must be a contiguous bool or uint8 tensor of shape (%d,) on %s" % (n, device))
@@ -125,16 +130,28 @@ def polyak_tau(tau, what: str) -> float:
     return tau
 
 
+SOFT_UPDATE_MAX = 32                                          # tensors per `risvec_soft_update` launch (kSoftUpdateMax)
+
+
+def soft_update_runs(n: int) -> list:
+    """The slices of n pairs that `soft_update_tensors` launches one by one: at most SOFT_UPDATE_MAX pairs each."""
+    return [slice(k, min(k + SOFT_UPDATE_MAX, n)) for k in range(0, max(n, 1), SOFT_UPDATE_MAX)]
+
+
 def soft_update_tensors(pairs: Sequence[Tuple[torch.Tensor, torch.Tensor]], tau: float, device) -> None:
-    """target = tau * online + (1 - tau) * target for up to 32 (online, target) pairs of contiguous float32 device tensors in
-    ONE launch on the current stream (`risvec_soft_update`, csrc/k_soft_update.hip), in place, with the bits of that
-    expression on float32 tensors (`ddpg_torch.py:122-127`).  The targets' version counters are not advanced."""
+    """target = tau * online + (1 - tau) * target for (online, target) pairs of contiguous float32 device tensors, up to 32
+    pairs in ONE launch on the current stream (`risvec_soft_update`, csrc/k_soft_update.hip) and more in runs of 32, in
+    place, with the bits of that expression on float32 tensors (`ddpg_torch.py:122-127`).  The targets' version counters
+    are not advanced."""
     N.require_hip(device)
-    n = len(pairs)
-    on = (C.c_void_p * n)(*(o.data_ptr() for o, _ in pairs))
-    tg = (C.c_void_p * n)(*(t.data_ptr() for _, t in pairs))
-    ne = (C.c_int64 * n)(*(t.numel() for _, t in pairs))
-    N.check(N.load().risvec_soft_update(n, on, tg, ne, tau, 1.0 - tau, N.stream(device)))
+    lib, stream = N.load(), N.stream(device)
+    for run in soft_update_runs(len(pairs)):
+        part = pairs[run]
+        n = len(part)
+        on = (C.c_void_p * n)(*(o.data_ptr() for o, _ in part))
+        tg = (C.c_void_p * n)(*(t.data_ptr() for _, t in part))
+        ne = (C.c_int64 * n)(*(t.numel() for _, t in part))
+        N.check(lib.risvec_soft_update(n, on, tg, ne, tau, 1.0 - tau, stream))
 
 
 # ---------------------------------------------------------------------- one network's weights and its weight stream

@@ -139,11 +139,6 @@ hipError_t launch_local(const LocalCriticsArgs& a, hipStream_t st) {
                               marl_walk_lds_bytes(a.KS, a.NG, MT2), st, a);
 }
 
-template <int MT2>
-hipError_t launch_local_f3(int F3, const LocalCriticsArgs& a, hipStream_t st) {
-    return F3 == 256 ? launch_local<MT2, 2>(a, st) : launch_local<MT2, 1>(a, st);
-}
-
 }  // namespace
 
 bool local_critics_supported(int V, int S, int A, int F1, int F2, int F3) {
@@ -159,19 +154,12 @@ hipError_t launch_local_critics(long long n_rows, int V, int S, int A, int F1, i
     LocalCriticsArgs c{};
     c.n_rows = n_rows; c.V = V; c.S = S; c.NA = A; c.KS = ks_of(S + A); c.NG = F1 / 32; c.n_nets = n_nets; c.gamma = gamma;
     c.obs = obs; c.action = action; c.heads = heads; c.power = power;
-    for (int i = 0; i < kLocalCriticsMaxAgents * 2; ++i) {
-        const RisVecMarlCriticNet& n = nets[i < V * n_nets ? i : 0];      // the unused slots repeat the first net
-        c.net[i] = MarlNetPtrs{static_cast<const uint4*>(n.wstream), n.scales, n.b1, n.b2, n.b3, n.qw, n.qb};
-    }
+    for (int i = 0; i < kLocalCriticsMaxAgents * 2; ++i)
+        c.net[i] = marl_net_ptrs(nets[i < V * n_nets ? i : 0]);   // the unused slots repeat the first net
     c.reward = reward; c.done = done; c.coef = coef; c.lp = logp_power; c.li = logp_intent;
     c.q1 = q1; c.q2 = q2; c.y = y;
     note_kernel("k_local_critics<%d,%d>x%dx%d", F2 / 128, F3 / 128, V, n_nets);
-    switch (F2) {
-        case 128: return launch_local_f3<1>(F3, c, st);
-        case 256: return launch_local_f3<2>(F3, c, st);
-        case 512: return launch_local_f3<4>(F3, c, st);
-    }
-    return hipErrorInvalidValue;
+    return dispatch_mt2_mt3(F2, F3, [&](auto mt2, auto mt3) { return launch_local<decltype(mt2)::value, decltype(mt3)::value>(c, st); });
 }
 
 }  // namespace risvec

@@ -122,11 +122,6 @@ hipError_t launch_marl(const MarlCriticArgs& a, hipStream_t st) {
     return launch_dynamic_lds(k_marl_critic<MT2, MT3>, dim3((unsigned)((a.n_rows + 31) / 32)), dim3(kMcBlock), marl_walk_lds_bytes(a.KS, a.NG, MT2), st, a);
 }
 
-template <int MT2>
-hipError_t launch_marl_f3(int F3, const MarlCriticArgs& a, hipStream_t st) {
-    return F3 == 256 ? launch_marl<MT2, 2>(a, st) : launch_marl<MT2, 1>(a, st);
-}
-
 }  // namespace
 
 bool marl_critic_supported(int S, int A, int F1, int F2, int F3) {
@@ -147,19 +142,11 @@ hipError_t launch_marl_critic(long long n_rows, int S, int A, int F1, int F2, in
     MarlCriticArgs c{};
     c.n_rows = n_rows; c.S = S; c.NA = A; c.KS = ks_of(S + A); c.NG = F1 / 32; c.n_nets = n_nets;
     c.state = state; c.action = action;
-    for (int i = 0; i < 2; ++i) {
-        const RisVecMarlCriticNet& n = nets[i < n_nets ? i : 0];      // the unused slot of a single net repeats net 1
-        c.net[i] = MarlNetPtrs{static_cast<const uint4*>(n.wstream), n.scales, n.b1, n.b2, n.b3, n.qw, n.qb};
-    }
+    for (int i = 0; i < 2; ++i) c.net[i] = marl_net_ptrs(nets[i < n_nets ? i : 0]);      // a single net fills both slots
     c.reward = reward; c.done = done; c.gamma = gamma; c.coef = coef; c.lp = logp_power; c.li = logp_intent;
     c.q1 = q1; c.q2 = q2; c.y = y;
     note_kernel("k_marl_critic<%d,%d>x%d", F2 / 128, F3 / 128, n_nets);
-    switch (F2) {
-        case 128: return launch_marl_f3<1>(F3, c, st);
-        case 256: return launch_marl_f3<2>(F3, c, st);
-        case 512: return launch_marl_f3<4>(F3, c, st);
-    }
-    return hipErrorInvalidValue;
+    return dispatch_mt2_mt3(F2, F3, [&](auto mt2, auto mt3) { return launch_marl<decltype(mt2)::value, decltype(mt3)::value>(c, st); });
 }
 
 }  // namespace risvec

@@ -278,11 +278,6 @@ hipError_t launch_critic(const CriticArgs& a, hipStream_t st) {
     return launch_dynamic_lds(k_sarl_critic<MT2, MT3>, dim3((unsigned)((a.n_rows + 31) / 32)), dim3(kCrBlock), lds, st, a);
 }
 
-template <int MT2>
-hipError_t launch_critic_f3(int F3, const CriticArgs& a, hipStream_t st) {
-    return F3 == 256 ? launch_critic<MT2, 2>(a, st) : launch_critic<MT2, 1>(a, st);
-}
-
 }  // namespace
 
 bool sarl_critic_supported(int IN, int F1, int F2, int F3, int A) {
@@ -304,12 +299,7 @@ hipError_t launch_sarl_critic(long long n_rows, int IN, int F1, int F2, int F3, 
     CriticArgs c{n_rows, IN, A, ks_of(IN + 1), ks_of(A), F1 / 32, x, a, static_cast<const uint4*>(wstream), scales, ln1w, ln1b,
                  b2, ln2w, ln2b, bav, b3, ln3w, ln3b, qw, qb, reward, done, gamma, q, y};
     note_kernel("k_sarl_critic<%d,%d>", F2 / 128, F3 / 128);
-    switch (F2) {
-        case 128: return launch_critic_f3<1>(F3, c, st);
-        case 256: return launch_critic_f3<2>(F3, c, st);
-        case 512: return launch_critic_f3<4>(F3, c, st);
-    }
-    return hipErrorInvalidValue;
+    return dispatch_mt2_mt3(F2, F3, [&](auto mt2, auto mt3) { return launch_critic<decltype(mt2)::value, decltype(mt3)::value>(c, st); });
 }
 
 }  // namespace risvec

@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "risvec_launch.hpp"
 #include "risvec_sarl.hpp"
@@ -28,16 +29,85 @@ int fail(int code, const char* fmt, ...) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-#define REQ_PTR(ptr, name)                                                                   \
+// `pre`: what stands in front of a field's name, "" or an Indexed("nets", c).s
+#define REQ_PTR_IN(pre, ptr, name)                                                           \
     do {                                                                                     \
-        if ((ptr) == nullptr) return fail(RISVEC_ERR_ARG, "%s: %s is NULL", fn, name);       \
-        if (!aligned16(ptr)) return fail(RISVEC_ERR_ARG, "%s: %s is not 16-byte aligned", fn, name); \
+        if ((ptr) == nullptr) return fail(RISVEC_ERR_ARG, "%s: %s%s is NULL", fn, pre, name); \
+        if (!aligned16(ptr)) return fail(RISVEC_ERR_ARG, "%s: %s%s is not 16-byte aligned", fn, pre, name); \
+    } while (0)
+#define REQ_PTR(ptr, name) REQ_PTR_IN("", ptr, name)
+// float data that is read float by float wherever it does not start on 16 bytes: float alignment is all it needs
+#define OPT_F32_IN(pre, ptr, name)                                                           \
+    do {                                                                                     \
+        if (reinterpret_cast<uintptr_t>(ptr) & 3u)                                           \
+            return fail(RISVEC_ERR_ARG, "%s: %s%s is not 4-byte aligned", fn, pre, name);    \
+    } while (0)
+#define REQ_F32_IN(pre, ptr, name)                                                           \
+    do {                                                                                     \
+        if ((ptr) == nullptr) return fail(RISVEC_ERR_ARG, "%s: %s%s is NULL", fn, pre, name); \
+        OPT_F32_IN(pre, ptr, name);                                                          \
     } while (0)
 #define OPT_PTR(ptr, name)                                                                   \
     do {                                                                                     \
         if ((ptr) != nullptr && !aligned16(ptr))                                             \
             return fail(RISVEC_ERR_ARG, "%s: %s is not 16-byte aligned", fn, name);          \
     } while (0)
+
+// "nets[3]." and its like
+struct Indexed {
+    char s[32];
+    Indexed(const char* array, int i) { snprintf(s, sizeof(s), "%s[%d].", array, i); }
+};
+
+// n_envs and n_veh, as a state carries them or as an entry point without a state takes them
+int check_envs_veh(const char* fn, int32_t n_envs, int32_t n_veh) {
+    if (n_envs < 1) return fail(RISVEC_ERR_SHAPE, "%s: n_envs=%d must be >= 1", fn, n_envs);
+    if (n_veh < 1 || n_veh > RISVEC_MAX_VEH)
+        return fail(RISVEC_ERR_SHAPE, "%s: n_veh=%d outside [1,%d]", fn, n_veh, RISVEC_MAX_VEH);
+    return RISVEC_OK;
+}
+
+// A weight stream of another shape than the call's.  `have` is printed as its type has it: int64_t where the argument is
+// one, size_t in the pack entry points.
+template <typename T>
+int check_wstream_bytes(const char* fn, const char* pre, T have, long long want) {
+    if (have == (T)want) return RISVEC_OK;
+    if (std::is_signed<T>::value)
+        return fail(RISVEC_ERR_ARG, "%s: %swstream_bytes=%lld, this shape's weight stream has %lld", fn, pre, (long long)have, want);
+    return fail(RISVEC_ERR_ARG, "%s: %swstream_bytes=%zu, this shape's weight stream has %lld", fn, pre, (size_t)have, want);
+}
+
+// The workspace of a pack entry point: `need` bytes for this `what` ("shape" or "call"), as `ws_fn` states them
+int check_workspace_bytes(const char* fn, size_t have, size_t need, const char* what, const char* ws_fn) {
+    if (have < need)
+        return fail(RISVEC_ERR_ARG, "%s: workspace_bytes=%zu, this %s needs %zu (%s)", fn, have, what, need, ws_fn);
+    return RISVEC_OK;
+}
+
+// The net table of risvec_marl_critic (count = n_nets) and risvec_local_critics (count = n_agents * n_nets)
+int check_critic_nets(const char* fn, const RisVecMarlCriticNet* nets, int count, long long need_bytes) {
+    for (int c = 0; c < count; ++c) {
+        const RisVecMarlCriticNet& n = nets[c];
+        const Indexed pre("nets", c);
+        if (int rc = check_wstream_bytes(fn, pre.s, n.wstream_bytes, need_bytes)) return rc;
+        REQ_PTR_IN(pre.s, n.wstream, "wstream"); REQ_PTR_IN(pre.s, n.scales, "scales"); REQ_PTR_IN(pre.s, n.b1, "b1");
+        REQ_PTR_IN(pre.s, n.b2, "b2"); REQ_PTR_IN(pre.s, n.b3, "b3"); REQ_PTR_IN(pre.s, n.qw, "qw");
+        if (!n.qb) return fail(RISVEC_ERR_ARG, "%s: %sqb is NULL", fn, pre.s);
+    }
+    return RISVEC_OK;
+}
+
+// The outputs and the TD epilogue of the same two: at least one output, and every input that an output asks for
+int check_critic_outputs(const char* fn, int n_nets, const float* reward, const uint8_t* done, float gamma, const float* coef,
+                         const float* logp_power, const float* logp_intent, const float* q1, const float* q2, const float* y) {
+    if (!q1 && !q2 && !y) return fail(RISVEC_ERR_ARG, "%s: q1, q2 and y are all NULL", fn);
+    if (q2 && n_nets != 2) return fail(RISVEC_ERR_ARG, "%s: q2 needs n_nets == 2", fn);
+    if (y && (!reward || !done)) return fail(RISVEC_ERR_ARG, "%s: y needs reward and done", fn);
+    if ((logp_power || logp_intent) && !coef) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need coef", fn);
+    if ((logp_power || logp_intent) && !y) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need y", fn);
+    if (!std::isfinite(gamma)) return fail(RISVEC_ERR_ARG, "%s: gamma=%g must be finite", fn, (double)gamma);
+    return RISVEC_OK;
+}
 
 // every entry point opens with this; `params` = false for the ones that take no RisVecParams (p is NULL there)
 int check_common(const char* fn, const RisVecState* s, const RisVecParams* p, bool params = true) {
@@ -49,9 +119,7 @@ int check_common(const char* fn, const RisVecState* s, const RisVecParams* p, bo
     if (p && (p->abi_version != RISVEC_ABI_VERSION || p->struct_bytes != sizeof(RisVecParams)))
         return fail(RISVEC_ERR_ARG, "%s: RisVecParams ABI mismatch (version %u/%u, bytes %u/%zu)", fn,
                     p->abi_version, (unsigned)RISVEC_ABI_VERSION, p->struct_bytes, sizeof(RisVecParams));
-    if (s->n_envs < 1) return fail(RISVEC_ERR_SHAPE, "%s: n_envs=%d must be >= 1", fn, s->n_envs);
-    if (s->n_veh < 1 || s->n_veh > RISVEC_MAX_VEH)
-        return fail(RISVEC_ERR_SHAPE, "%s: n_veh=%d outside [1,%d]", fn, s->n_veh, RISVEC_MAX_VEH);
+    if (int rc = check_envs_veh(fn, s->n_envs, s->n_veh)) return rc;
     if (s->n_ris < 1 || s->n_ris > 2048)
         return fail(RISVEC_ERR_SHAPE, "%s: n_ris=%d outside [1,2048]", fn, s->n_ris);
     if (s->control_bit < 0 || s->control_bit > 6)
@@ -529,6 +597,23 @@ static int check_sarl_ring(const char* fn, const RisVecSarlRollout* r) {
     return RISVEC_OK;
 }
 
+// the state arrays a SARL step reads or writes; `obs`: state.obs as well
+static int check_sarl_state(const char* fn, const RisVecState* s, bool obs) {
+    REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->b, "state.b"); REQ_PTR(s->pl, "state.pl");
+    REQ_PTR(s->gain, "state.gain"); REQ_PTR(s->data_buf, "state.data_buf"); REQ_PTR(s->rate, "state.rate");
+    REQ_PTR(s->data_t, "state.data_t"); REQ_PTR(s->data_p, "state.data_p"); REQ_PTR(s->reward, "state.reward");
+    REQ_PTR(s->over_power, "state.over_power"); REQ_PTR(s->over_data, "state.over_data");
+    REQ_PTR(s->metrics, "state.metrics");
+    if (obs) REQ_PTR(s->obs, "state.obs");
+    return RISVEC_OK;
+}
+
+// RISVEC_STEP_OBS is the one flag of the SARL entry points
+static int check_sarl_flags(const char* fn, uint32_t flags) {
+    if (flags & ~(uint32_t)RISVEC_STEP_OBS) return fail(RISVEC_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags);
+    return RISVEC_OK;
+}
+
 int risvec_sarl_step(const RisVecState* s, const RisVecSarlParams* p, const float* action_power,
                      const float* action_phase, const int32_t* arrivals, uint64_t seed, uint32_t counter,
                      uint32_t flags, risvec_stream_t stream) {
@@ -536,13 +621,8 @@ int risvec_sarl_step(const RisVecState* s, const RisVecSarlParams* p, const floa
     if (int rc = check_sarl_params(fn, p)) return rc;
     if (int rc = check_common(fn, s, nullptr, false)) return rc;
     REQ_PTR(action_power, "action_power"); OPT_PTR(action_phase, "action_phase"); OPT_PTR(arrivals, "arrivals");
-    REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->b, "state.b"); REQ_PTR(s->pl, "state.pl");
-    REQ_PTR(s->gain, "state.gain"); REQ_PTR(s->data_buf, "state.data_buf"); REQ_PTR(s->rate, "state.rate");
-    REQ_PTR(s->data_t, "state.data_t"); REQ_PTR(s->data_p, "state.data_p"); REQ_PTR(s->reward, "state.reward");
-    REQ_PTR(s->over_power, "state.over_power"); REQ_PTR(s->over_data, "state.over_data");
-    REQ_PTR(s->metrics, "state.metrics");
-    if (flags & RISVEC_STEP_OBS) REQ_PTR(s->obs, "state.obs");
-    if (flags & ~(uint32_t)RISVEC_STEP_OBS) return fail(RISVEC_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags);
+    if (int rc = check_sarl_state(fn, s, (flags & RISVEC_STEP_OBS) != 0)) return rc;
+    if (int rc = check_sarl_flags(fn, flags)) return rc;
     return finish(fn, risvec::launch_sarl_step(*s, *p, action_power, action_phase, arrivals, seed, counter, flags,
                                                (hipStream_t)stream));
 }
@@ -557,7 +637,7 @@ int risvec_sarl_rollout(const RisVecState* s, const RisVecSarlParams* p, const R
     if (r->struct_bytes != sizeof(RisVecSarlRollout))
         return fail(RISVEC_ERR_ARG, "%s: RisVecSarlRollout ABI mismatch (bytes %u/%zu)", fn, r->struct_bytes, sizeof(RisVecSarlRollout));
     if (int rc = check_common(fn, s, nullptr, false)) return rc;
-    if (flags & ~(uint32_t)RISVEC_STEP_OBS) return fail(RISVEC_ERR_ARG, "%s: unknown flag bits 0x%x", fn, flags);
+    if (int rc = check_sarl_flags(fn, flags)) return rc;
     if (!risvec::sarl_rollout_covers(s->n_veh, s->n_ris))
         return fail(RISVEC_ERR_UNSUPPORTED, "%s: no one-launch rollout kernel at n_veh=%d, n_ris=%d (n_veh in {4, 8, 16}, even "
                     "n_ris with n_veh <= n_ris <= 256); use the staged path: map the action on the host side, then "
@@ -572,11 +652,7 @@ int risvec_sarl_rollout(const RisVecState* s, const RisVecSarlParams* p, const R
         if (r->ou_env_offset < 0 || r->ou_env_offset + s->n_envs > 0xFFFFFFFFLL)
             return fail(RISVEC_ERR_SHAPE, "%s: ou_env_offset+n_envs must fit 32 bits", fn);
     }
-    REQ_PTR(s->h_r, "state.h_r"); REQ_PTR(s->theta, "state.theta"); REQ_PTR(s->b, "state.b"); REQ_PTR(s->pl, "state.pl");
-    REQ_PTR(s->gain, "state.gain"); REQ_PTR(s->data_buf, "state.data_buf"); REQ_PTR(s->rate, "state.rate");
-    REQ_PTR(s->data_t, "state.data_t"); REQ_PTR(s->data_p, "state.data_p"); REQ_PTR(s->reward, "state.reward");
-    REQ_PTR(s->over_power, "state.over_power"); REQ_PTR(s->over_data, "state.over_data");
-    REQ_PTR(s->metrics, "state.metrics"); REQ_PTR(s->obs, "state.obs");
+    if (int rc = check_sarl_state(fn, s, true)) return rc;
     if (r->state_memory || r->action_memory || r->reward_memory || r->new_state_memory || r->terminal_memory) {
         if (int rc = check_sarl_ring(fn, r)) return rc;
         if (r->mem_size < s->n_envs)
@@ -885,19 +961,20 @@ int risvec_replay_sample(const RisVecReplay* rb, int64_t max_mem, int32_t batch,
                                                    rewards_l, states_, dones, masks, idx_out, (hipStream_t)stream));
 }
 
+// cpu_share_floor as the marshalling kernels take it: within [0, 0.95]
+static float clamp_share_floor(float f) { return f < 0.0f ? 0.0f : (f > 0.95f ? 0.95f : f); }
+
 int risvec_marshal_actions(int32_t n_envs, int32_t n_veh, const float* power_raw, const float* probs,
                            float cpu_share_floor, float* action_env, float* p_off01, float* action_store,
                            risvec_stream_t stream) {
     const char* fn = "risvec_marshal_actions";
-    if (n_envs < 1) return fail(RISVEC_ERR_SHAPE, "%s: n_envs=%d must be >= 1", fn, n_envs);
-    if (n_veh < 1 || n_veh > RISVEC_MAX_VEH)
-        return fail(RISVEC_ERR_SHAPE, "%s: n_veh=%d outside [1,%d]", fn, n_veh, RISVEC_MAX_VEH);
+    if (int rc = check_envs_veh(fn, n_envs, n_veh)) return rc;
     REQ_PTR(power_raw, "power_raw"); OPT_PTR(probs, "probs"); OPT_PTR(action_env, "action_env");
     OPT_PTR(p_off01, "p_off01"); OPT_PTR(action_store, "action_store");
     if (action_store && !probs) return fail(RISVEC_ERR_ARG, "%s: action_store needs probs", fn);
     if ((long long)n_envs * n_veh * (n_veh + 2) >= (1LL << 31))
         return fail(RISVEC_ERR_SHAPE, "%s: n_envs*n_veh*(n_veh+2) must stay below 2^31", fn);
-    const float fl = cpu_share_floor < 0.0f ? 0.0f : (cpu_share_floor > 0.95f ? 0.95f : cpu_share_floor);
+    const float fl = clamp_share_floor(cpu_share_floor);
     return finish(fn, risvec::launch_marshal_actions(n_envs, n_veh, power_raw, probs, fl, action_env, p_off01,
                                                      action_store, (hipStream_t)stream));
 }
@@ -907,15 +984,13 @@ int risvec_policy_sample(int32_t n_envs, int32_t n_veh, int64_t env_offset, cons
                          uint32_t counter, float cpu_share_floor, float* power_raw, float* probs, float* onehot,
                          float* action_env, float* p_off01, float* action_store, risvec_stream_t stream) {
     const char* fn = "risvec_policy_sample";
-    if (n_envs < 1) return fail(RISVEC_ERR_SHAPE, "%s: n_envs=%d must be >= 1", fn, n_envs);
-    if (n_veh < 1 || n_veh > RISVEC_MAX_VEH)
-        return fail(RISVEC_ERR_SHAPE, "%s: n_veh=%d outside [1,%d]", fn, n_veh, RISVEC_MAX_VEH);
+    if (int rc = check_envs_veh(fn, n_envs, n_veh)) return rc;
     if (env_offset < 0 || env_offset + n_envs > 0xFFFFFFFFLL)
         return fail(RISVEC_ERR_SHAPE, "%s: env_offset+n_envs must fit 32 bits", fn);
     REQ_PTR(heads, "heads"); REQ_PTR(tau, "tau"); REQ_PTR(power_raw, "power_raw"); REQ_PTR(probs, "probs");
     OPT_PTR(mask, "mask"); OPT_PTR(eps, "eps"); OPT_PTR(expo, "expo"); OPT_PTR(onehot, "onehot");
     OPT_PTR(action_env, "action_env"); OPT_PTR(p_off01, "p_off01"); OPT_PTR(action_store, "action_store");
-    const float fl = cpu_share_floor < 0.0f ? 0.0f : (cpu_share_floor > 0.95f ? 0.95f : cpu_share_floor);
+    const float fl = clamp_share_floor(cpu_share_floor);
     return finish(fn, risvec::launch_policy_sample(n_envs, n_veh, env_offset, heads, mask, tau, hard, eps, expo, seed, counter,
                                                    fl, power_raw, probs, onehot, action_env, p_off01, action_store,
                                                    (hipStream_t)stream));
@@ -1006,9 +1081,7 @@ int risvec_sarl_actor(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2,
                     "and <= 1024, fc2 = 128 or 256, n_actions <= 96; use library kernels elsewhere)", fn, in_dims, fc1, fc2,
                     n_actions);
     const risvec::SarlActorGeom g = risvec::sarl_actor_geom(in_dims, fc1, fc2, n_actions);
-    if (wstream_bytes != g.stream_bytes)
-        return fail(RISVEC_ERR_ARG, "%s: wstream_bytes=%lld, this shape's weight stream has %lld", fn, (long long)wstream_bytes,
-                    g.stream_bytes);
+    if (int rc = check_wstream_bytes(fn, "", wstream_bytes, g.stream_bytes)) return rc;
     REQ_PTR(x, "x"); REQ_PTR(wstream, "wstream"); REQ_PTR(scales, "scales"); REQ_PTR(b2, "b2"); REQ_PTR(ln2_w, "ln2_w");
     REQ_PTR(ln2_b, "ln2_b"); REQ_PTR(bmu, "bmu"); OPT_PTR(logits, "logits"); REQ_PTR(mu, "mu");
     return finish(fn, risvec::launch_sarl_actor(n_rows, in_dims, fc1, fc2, n_actions, x, wstream, scales, b2, ln2_w, ln2_b, bmu,
@@ -1031,13 +1104,10 @@ int risvec_sarl_actor_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t n_
     REQ_PTR(W1, "W1"); REQ_PTR(b1, "b1"); REQ_PTR(ln1_w, "ln1_w"); REQ_PTR(ln1_b, "ln1_b"); REQ_PTR(W2, "W2");
     REQ_PTR(Wmu, "Wmu"); REQ_PTR(wstream, "wstream"); REQ_PTR(scales, "scales"); REQ_PTR(workspace, "workspace");
     const risvec::SarlActorGeom g = risvec::sarl_actor_geom(in_dims, fc1, fc2, n_actions);
-    if (wstream_bytes != (size_t)g.stream_bytes)
-        return fail(RISVEC_ERR_ARG, "%s: wstream_bytes=%zu, this shape's weight stream has %lld", fn, wstream_bytes,
-                    g.stream_bytes);
-    const size_t need = (size_t)risvec::sarl_actor_pack_workspace(in_dims, fc1, fc2, n_actions);
-    if (workspace_bytes < need)
-        return fail(RISVEC_ERR_ARG, "%s: workspace_bytes=%zu, this shape needs %zu (risvec_sarl_actor_pack_workspace)", fn,
-                    workspace_bytes, need);
+    if (int rc = check_wstream_bytes(fn, "", wstream_bytes, g.stream_bytes)) return rc;
+    if (int rc = check_workspace_bytes(fn, workspace_bytes, (size_t)risvec::sarl_actor_pack_workspace(in_dims, fc1, fc2, n_actions),
+                                       "shape", "risvec_sarl_actor_pack_workspace"))
+        return rc;
     return finish(fn, risvec::launch_sarl_actor_pack(in_dims, fc1, fc2, n_actions, W1, b1, ln1_w, ln1_b, W2, Wmu, wstream,
                                                      scales, workspace, (hipStream_t)stream));
 }
@@ -1062,9 +1132,8 @@ int risvec_sarl_critic(int32_t n_rows, int32_t in_dims, int32_t fc1, int32_t fc2
         return fail(RISVEC_ERR_SHAPE, "%s: in_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d (built for in_dims <= 128, fc1 a multiple "
                     "of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256, n_actions <= 96; use library kernels elsewhere)",
                     fn, in_dims, fc1, fc2, fc3, n_actions);
-    const long long need = risvec::sarl_critic_stream_bytes(in_dims, fc1, fc2, fc3, n_actions);
-    if (wstream_bytes != need)
-        return fail(RISVEC_ERR_ARG, "%s: wstream_bytes=%lld, this shape's weight stream has %lld", fn, (long long)wstream_bytes, need);
+    if (int rc = check_wstream_bytes(fn, "", wstream_bytes, risvec::sarl_critic_stream_bytes(in_dims, fc1, fc2, fc3, n_actions)))
+        return rc;
     if (!x || !a) return fail(RISVEC_ERR_ARG, "%s: x or a is NULL", fn);
     REQ_PTR(wstream, "wstream"); REQ_PTR(scales, "scales"); REQ_PTR(ln1_w, "ln1_w"); REQ_PTR(ln1_b, "ln1_b"); REQ_PTR(b2, "b2");
     REQ_PTR(ln2_w, "ln2_w"); REQ_PTR(ln2_b, "ln2_b"); REQ_PTR(bav, "bav"); REQ_PTR(b3, "b3"); REQ_PTR(ln3_w, "ln3_w");
@@ -1091,21 +1160,15 @@ int risvec_sarl_critic_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t f
         return fail(RISVEC_ERR_UNSUPPORTED, "%s: in_dims=%d fc1=%d fc2=%d fc3=%d n_actions=%d (risvec_sarl_critic is built for "
                     "in_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256, n_actions <= 96)",
                     fn, in_dims, fc1, fc2, fc3, n_actions);
-    // the weights are read float by float wherever they do not start on 16 bytes: float alignment is all they need
-    const struct { const float* p; const char* name; } weights[] = {{W1, "W1"}, {b1, "b1"}, {W2, "W2"}, {Wav, "Wav"}, {W3, "W3"},
-                                                                    {scales, "scales"}};
-    for (const auto& w : weights) {
-        if (!w.p) return fail(RISVEC_ERR_ARG, "%s: %s is NULL", fn, w.name);
-        if (reinterpret_cast<uintptr_t>(w.p) & 3u) return fail(RISVEC_ERR_ARG, "%s: %s is not 4-byte aligned", fn, w.name);
-    }
+    REQ_F32_IN("", W1, "W1"); REQ_F32_IN("", b1, "b1"); REQ_F32_IN("", W2, "W2"); REQ_F32_IN("", Wav, "Wav");
+    REQ_F32_IN("", W3, "W3"); REQ_F32_IN("", scales, "scales");
     REQ_PTR(wstream, "wstream"); REQ_PTR(workspace, "workspace");
-    const long long bytes = risvec::sarl_critic_stream_bytes(in_dims, fc1, fc2, fc3, n_actions);
-    if (wstream_bytes != (size_t)bytes)
-        return fail(RISVEC_ERR_ARG, "%s: wstream_bytes=%zu, this shape's weight stream has %lld", fn, wstream_bytes, bytes);
-    const size_t need = (size_t)risvec::sarl_critic_pack_workspace(in_dims, fc1, fc2, fc3, n_actions);
-    if (workspace_bytes < need)
-        return fail(RISVEC_ERR_ARG, "%s: workspace_bytes=%zu, this shape needs %zu (risvec_sarl_critic_pack_workspace)", fn,
-                    workspace_bytes, need);
+    if (int rc = check_wstream_bytes(fn, "", wstream_bytes, risvec::sarl_critic_stream_bytes(in_dims, fc1, fc2, fc3, n_actions)))
+        return rc;
+    if (int rc = check_workspace_bytes(fn, workspace_bytes,
+                                       (size_t)risvec::sarl_critic_pack_workspace(in_dims, fc1, fc2, fc3, n_actions), "shape",
+                                       "risvec_sarl_critic_pack_workspace"))
+        return rc;
     return finish(fn, risvec::launch_sarl_critic_pack(in_dims, fc1, fc2, fc3, n_actions, W1, b1, W2, Wav, W3, wstream, scales,
                                                       workspace, (hipStream_t)stream));
 }
@@ -1130,27 +1193,10 @@ int risvec_marl_critic(int32_t n_rows, int32_t state_dims, int32_t action_dims, 
                     "action_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256; use library "
                     "kernels elsewhere)", fn, state_dims, action_dims, fc1, fc2, fc3);
     if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
-    const long long need = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
-    for (int c = 0; c < n_nets; ++c) {
-        const RisVecMarlCriticNet& n = nets[c];
-        if (n.wstream_bytes != need)
-            return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream_bytes=%lld, this shape's weight stream has %lld", fn, c,
-                        (long long)n.wstream_bytes, need);
-        const struct { const void* p; const char* name; } ptrs[] = {{n.wstream, "wstream"}, {n.scales, "scales"}, {n.b1, "b1"},
-                                                                    {n.b2, "b2"}, {n.b3, "b3"}, {n.qw, "qw"}};
-        for (const auto& w : ptrs) {
-            if (!w.p) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is NULL", fn, c, w.name);
-            if (!aligned16(w.p)) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is not 16-byte aligned", fn, c, w.name);
-        }
-        if (!n.qb) return fail(RISVEC_ERR_ARG, "%s: nets[%d].qb is NULL", fn, c);
-    }
+    if (int rc = check_critic_nets(fn, nets, n_nets, risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3)))
+        return rc;
     if (!state || !action) return fail(RISVEC_ERR_ARG, "%s: state or action is NULL", fn);
-    if (!q1 && !q2 && !y) return fail(RISVEC_ERR_ARG, "%s: q1, q2 and y are all NULL", fn);
-    if (q2 && n_nets != 2) return fail(RISVEC_ERR_ARG, "%s: q2 needs n_nets == 2", fn);
-    if (y && (!reward || !done)) return fail(RISVEC_ERR_ARG, "%s: y needs reward and done", fn);
-    if ((logp_power || logp_intent) && !coef) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need coef", fn);
-    if ((logp_power || logp_intent) && !y) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need y", fn);
-    if (!std::isfinite(gamma)) return fail(RISVEC_ERR_ARG, "%s: gamma=%g must be finite", fn, (double)gamma);
+    if (int rc = check_critic_outputs(fn, n_nets, reward, done, gamma, coef, logp_power, logp_intent, q1, q2, y)) return rc;
     return finish(fn, risvec::launch_marl_critic(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, state, action,
                                                  reward, done, gamma, coef, logp_power, logp_intent, q1, q2, y,
                                                  (hipStream_t)stream));
@@ -1174,29 +1220,21 @@ int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1
     const long long bytes = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
     for (int c = 0; c < n_nets; ++c) {
         const RisVecMarlCriticPackNet& n = nets[c];
-        // the weights are read float by float wherever they do not start on 16 bytes: float alignment is all they need
-        const struct { const float* p; const char* name; } weights[] = {{n.W1, "W1"}, {n.W2, "W2"}, {n.W3, "W3"},
-                                                                        {n.scales, "scales"}};
-        for (const auto& w : weights) {
-            if (!w.p) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is NULL", fn, c, w.name);
-            if (reinterpret_cast<uintptr_t>(w.p) & 3u)
-                return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is not 4-byte aligned", fn, c, w.name);
-        }
-        if (!n.wstream) return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream is NULL", fn, c);
-        if (!aligned16(n.wstream)) return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream is not 16-byte aligned", fn, c);
-        if (n.wstream_bytes != bytes)
-            return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream_bytes=%lld, this shape's weight stream has %lld", fn, c,
-                        (long long)n.wstream_bytes, bytes);
+        const Indexed pre("nets", c);
+        REQ_F32_IN(pre.s, n.W1, "W1"); REQ_F32_IN(pre.s, n.W2, "W2"); REQ_F32_IN(pre.s, n.W3, "W3");
+        REQ_F32_IN(pre.s, n.scales, "scales");
+        REQ_PTR_IN(pre.s, n.wstream, "wstream");
+        if (int rc = check_wstream_bytes(fn, pre.s, n.wstream_bytes, bytes)) return rc;
     }
     if (n_nets == 2 && nets[0].wstream == nets[1].wstream)
         return fail(RISVEC_ERR_ARG, "%s: nets[0].wstream and nets[1].wstream are the same buffer", fn);
     if (n_nets == 2 && nets[0].scales == nets[1].scales)
         return fail(RISVEC_ERR_ARG, "%s: nets[0].scales and nets[1].scales are the same buffer", fn);
     REQ_PTR(workspace, "workspace");
-    const size_t need = (size_t)risvec::marl_critic_pack_workspace(state_dims, action_dims, fc1, fc2, fc3, n_nets);
-    if (workspace_bytes < need)
-        return fail(RISVEC_ERR_ARG, "%s: workspace_bytes=%zu, this call needs %zu (risvec_marl_critic_pack_workspace)", fn,
-                    workspace_bytes, need);
+    if (int rc = check_workspace_bytes(fn, workspace_bytes,
+                                       (size_t)risvec::marl_critic_pack_workspace(state_dims, action_dims, fc1, fc2, fc3, n_nets),
+                                       "call", "risvec_marl_critic_pack_workspace"))
+        return rc;
     return finish(fn, risvec::launch_marl_critic_pack(state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, workspace,
                                                       (hipStream_t)stream));
 }
@@ -1220,20 +1258,9 @@ int risvec_local_critics(int32_t n_rows, int32_t n_agents, int32_t state_dims, i
                     "fc3 = 128 or 256; use library kernels elsewhere)", fn, n_agents, state_dims, action_dims, fc1, fc2, fc3,
                     risvec::kLocalCriticsMaxAgents);
     if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
-    const long long need = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
-    for (int c = 0; c < n_agents * n_nets; ++c) {
-        const RisVecMarlCriticNet& n = nets[c];
-        if (n.wstream_bytes != need)
-            return fail(RISVEC_ERR_ARG, "%s: nets[%d].wstream_bytes=%lld, this shape's weight stream has %lld", fn, c,
-                        (long long)n.wstream_bytes, need);
-        const struct { const void* p; const char* name; } ptrs[] = {{n.wstream, "wstream"}, {n.scales, "scales"}, {n.b1, "b1"},
-                                                                    {n.b2, "b2"}, {n.b3, "b3"}, {n.qw, "qw"}};
-        for (const auto& w : ptrs) {
-            if (!w.p) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is NULL", fn, c, w.name);
-            if (!aligned16(w.p)) return fail(RISVEC_ERR_ARG, "%s: nets[%d].%s is not 16-byte aligned", fn, c, w.name);
-        }
-        if (!n.qb) return fail(RISVEC_ERR_ARG, "%s: nets[%d].qb is NULL", fn, c);
-    }
+    if (int rc = check_critic_nets(fn, nets, n_agents * n_nets,
+                                   risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3)))
+        return rc;
     if (!obs) return fail(RISVEC_ERR_ARG, "%s: obs is NULL", fn);
     if (action && heads) return fail(RISVEC_ERR_ARG, "%s: action and heads are both given (one of them builds the input)", fn);
     if (!action && !heads) return fail(RISVEC_ERR_ARG, "%s: action and heads are both NULL", fn);
@@ -1242,12 +1269,7 @@ int risvec_local_critics(int32_t n_rows, int32_t n_agents, int32_t state_dims, i
     if (heads && action_dims != n_agents + 2)
         return fail(RISVEC_ERR_ARG, "%s: heads needs action_dims == n_agents + 2, got action_dims=%d n_agents=%d", fn, action_dims,
                     n_agents);
-    if (!q1 && !q2 && !y) return fail(RISVEC_ERR_ARG, "%s: q1, q2 and y are all NULL", fn);
-    if (q2 && n_nets != 2) return fail(RISVEC_ERR_ARG, "%s: q2 needs n_nets == 2", fn);
-    if (y && (!reward || !done)) return fail(RISVEC_ERR_ARG, "%s: y needs reward and done", fn);
-    if ((logp_power || logp_intent) && !coef) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need coef", fn);
-    if ((logp_power || logp_intent) && !y) return fail(RISVEC_ERR_ARG, "%s: logp_power / logp_intent need y", fn);
-    if (!std::isfinite(gamma)) return fail(RISVEC_ERR_ARG, "%s: gamma=%g must be finite", fn, (double)gamma);
+    if (int rc = check_critic_outputs(fn, n_nets, reward, done, gamma, coef, logp_power, logp_intent, q1, q2, y)) return rc;
     return finish(fn, risvec::launch_local_critics(n_rows, n_agents, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, obs,
                                                    action, heads, power, reward, done, gamma, coef, logp_power, logp_intent, q1,
                                                    q2, y, (hipStream_t)stream));
@@ -1327,10 +1349,10 @@ int risvec_adam_step(int32_t n_tensors, int32_t n_groups, int32_t n_blocks, cons
                         blocks);
         const struct { const float* p; const char* name; } ptrs[] = {{d.param, "param"}, {d.grad, "grad"}, {d.exp_avg, "exp_avg"},
                                                                      {d.exp_avg_sq, "exp_avg_sq"}, {d.target, "target"}};
+        const Indexed pre("tensors", i);
         for (int k = 0; k < 5; ++k) {
-            if (!ptrs[k].p && k < 4) return fail(RISVEC_ERR_ARG, "%s: tensors[%d].%s is NULL", fn, i, ptrs[k].name);
-            if (reinterpret_cast<uintptr_t>(ptrs[k].p) & 3u)
-                return fail(RISVEC_ERR_ARG, "%s: tensors[%d].%s is not 4-byte aligned", fn, i, ptrs[k].name);
+            if (k < 4) REQ_F32_IN(pre.s, ptrs[k].p, ptrs[k].name);
+            else OPT_F32_IN(pre.s, ptrs[k].p, ptrs[k].name);      // target: NULL where the tensor has none
             for (int j = 0; j < k; ++j)
                 if (ptrs[k].p && ptrs[k].p == ptrs[j].p)
                     return fail(RISVEC_ERR_ARG, "%s: tensors[%d].%s and .%s are the same tensor", fn, i, ptrs[j].name, ptrs[k].name);
@@ -1352,8 +1374,7 @@ int risvec_adam_step(int32_t n_tensors, int32_t n_groups, int32_t n_blocks, cons
     }
     if (clip) {
         REQ_PTR(partials, "partials");
-        if (!norms) return fail(RISVEC_ERR_ARG, "%s: norms is NULL", fn);
-        if (reinterpret_cast<uintptr_t>(norms) & 3u) return fail(RISVEC_ERR_ARG, "%s: norms is not 4-byte aligned", fn);
+        REQ_F32_IN("", norms, "norms");
         if (partials_bytes < risvec_adam_workspace(n_blocks))
             return fail(RISVEC_ERR_ARG, "%s: partials_bytes=%zu, this call needs %zu (risvec_adam_workspace)", fn, partials_bytes,
                         risvec_adam_workspace(n_blocks));
@@ -1383,9 +1404,7 @@ int risvec_policy_heads(int32_t n_envs, int32_t n_veh, int32_t f2, int32_t n_hea
 }
 
 static int episode_dims(const char* fn, int32_t n_envs, int32_t n_veh) {
-    if (n_envs < 1) return fail(RISVEC_ERR_SHAPE, "%s: n_envs=%d must be >= 1", fn, n_envs);
-    if (n_veh < 1 || n_veh > RISVEC_MAX_VEH)
-        return fail(RISVEC_ERR_SHAPE, "%s: n_veh=%d outside [1,%d]", fn, n_veh, RISVEC_MAX_VEH);
+    if (int rc = check_envs_veh(fn, n_envs, n_veh)) return rc;
     if ((long long)n_envs * (RISVEC_EP_FIXED + n_veh) >= (1LL << 31))
         return fail(RISVEC_ERR_SHAPE, "%s: n_envs*(%d+n_veh) must stay below 2^31", fn, RISVEC_EP_FIXED);
     return RISVEC_OK;

@@ -25,6 +25,10 @@ struct MarlNetPtrs {
     const float* qb;               // [1]
 };
 
+inline MarlNetPtrs marl_net_ptrs(const RisVecMarlCriticNet& n) {
+    return MarlNetPtrs{static_cast<const uint4*>(n.wstream), n.scales, n.b1, n.b2, n.b3, n.qw, n.qb};
+}
+
 constexpr int kMcBlock = 256;        // 4 wavefronts = 1 per SIMD, all on the same 32 rows
 constexpr int kMcWaves = kCriticWaves;
 constexpr int kRedSlots = 2;

@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "risvec.h"
 #include "risvec_dev.hpp"
 
@@ -237,6 +239,21 @@ hipError_t launch_dynamic_lds(void (*kernel)(Args), dim3 grid, dim3 block, size_
     }
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args);
     return hipGetLastError();
+}
+
+// The <MT2, MT3> = <fc2 / 128, fc3 / 128> instantiation of a critic kernel, fc2 in {128, 256, 512}, fc3 in {128, 256}:
+// f(std::integral_constant<int, MT2>, std::integral_constant<int, MT3>) launches it.
+template <typename F>
+hipError_t dispatch_mt2_mt3(int F2, int F3, F&& f) {
+    auto f3 = [&](auto mt2) {
+        return F3 == 256 ? f(mt2, std::integral_constant<int, 2>{}) : f(mt2, std::integral_constant<int, 1>{});
+    };
+    switch (F2) {
+        case 128: return f3(std::integral_constant<int, 1>{});
+        case 256: return f3(std::integral_constant<int, 2>{});
+        case 512: return f3(std::integral_constant<int, 4>{});
+    }
+    return hipErrorInvalidValue;
 }
 
 inline Dims dims_of(const RisVecState& s) {

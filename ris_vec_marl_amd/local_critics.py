@@ -18,30 +18,21 @@ Nothing here differentiates.  No CPU compute path.
 from __future__ import annotations
 
 import ctypes as C
-import math
+from itertools import chain
 from typing import Mapping, Optional
 
 import torch
 
 from . import _native as N
-from ._weights import (PACK_RULE, choose_mode, is_f32, load_weight_sets, out_f32, polyak_pairs, polyak_tau, share_weight_sets,
-                       soft_update_tensors, stream_pair)
-from .marl_critic import _Net, marl_critic_geom, pack_marl_critic_weights, pack_marl_critic_weights_device
-
-_SOFT_UPDATE_MAX = 32                                         # tensors per `soft_update_tensors` launch (its limit)
+from ._critic_nets import CriticNets, draw_net, entropy_args, minus_entropy, net_table, q_net, q_outs
+from ._weights import (done_gamma_args, is_f32, load_weight_sets, out_f32, polyak_pairs, polyak_tau, share_weight_sets,
+                       soft_update_tensors)
 
 
-class BatchedLocalCritics:
+class BatchedLocalCritics(CriticNets):
     """`agents[j].target_q1` / `agents[j].target_q2` (`sac_agent.py:177-182`; `CriticNetwork`, networks.py:7-49) of all
     `n_agents` agents for n rows at once.  `obs_dims` is one agent's observation width, `action_dims` one agent's action
     width (default n_agents + 2: the intent one-hot and the two powers).  `nets[j][c]` is agent j's net c."""
-
-    GEMM_MODES = ("fused", "library")
-    PACK_MODES = ("host", "device")
-    #: with gemm=None, batches of fewer rows than this run the library path even where the fused kernel is built
-    #: (1 = fused at every row count; see profiles/local_critics.json and README)
-    AUTO_MIN_ROWS = 1
-    _SD = _Net._SD
 
     def __init__(self, n_agents: int, obs_dims: int = 5, action_dims: Optional[int] = None, fc1_dims: int = 1024,
                  fc2_dims: int = 512, fc3_dims: int = 256, n_nets: int = 2, device="cuda", seed: int = 0,
@@ -63,50 +54,19 @@ class BatchedLocalCritics:
             raise ValueError("BatchedLocalCritics: every dimension must be >= 1")
         if self.n_nets not in (1, 2):
             raise ValueError("BatchedLocalCritics: n_nets must be 1 or 2")
-        fused_ok = bool(lib.risvec_local_critics_supported(self.n_agents, *self._dims))
-        self.gemm = choose_mode("gemm", gemm, "fused" if fused_ok else "library", self.GEMM_MODES, fused_ok, self._shape(),
-                                "fused: n_agents <= 16, obs_dims + action_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, "
-                                "512}, fc3 in {128, 256}")
-        self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
-        self._fused_ok = fused_ok
-        self._pack = "host"                                   # see `pack`
-        self._pack_workspace = None                           # pack="device": one workspace for every agent, at first use
-        self.packs = 0                                        # how often a net's weight stream was rebuilt
-        dev = self.device
+        self._init_modes(gemm, bool(lib.risvec_local_critics_supported(self.n_agents, *self._dims)),
+                         "fused: n_agents <= 16, obs_dims + action_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, "
+                         "512}, fc3 in {128, 256}")
         g = torch.Generator(device="cpu").manual_seed(seed)
-
-        def uni(*shape, r):
-            return ((torch.rand(*shape, generator=g) * 2 - 1) * r).to(dev)
         IN = self.obs_dims + self.action_dims
-        self.nets = []
-        for _ in range(self.n_agents):
-            pair = []
-            for _ in range(self.n_nets):                      # nn.Linear's default ranges (networks.py:29-32)
-                net = _Net(dev)
-                for w, b, fan_out, fan_in in (("W1", "b1", self.fc1_dims, IN), ("W2", "b2", self.fc2_dims, self.fc1_dims),
-                                              ("W3", "b3", self.fc3_dims, self.fc2_dims), ("Wq", "bq", 1, self.fc3_dims)):
-                    r = 1.0 / math.sqrt(fan_in)
-                    setattr(net, w, uni(fan_out, fan_in, r=r))
-                    setattr(net, b, uni(fan_out, r=r))
-                pair.append(net)
-            self.nets.append(pair)
+        self.nets = [[draw_net(g, IN, *self._dims[2:], self.device) for _ in range(self.n_nets)] for _ in range(self.n_agents)]
+        self._flat = list(chain.from_iterable(self.nets))     # agent j's net c at [j n_nets + c], as the kernel's table
 
     def _shape(self) -> str:
         return "n_agents=%d obs_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d" % ((self.n_agents,) + self._dims)
 
-    @property
-    def pack(self) -> str:
-        """How the fused kernel's weight streams are rebuilt after a weight update.  "host" (the default):
-        `pack_marl_critic_weights` once per stale net.  "device": one `pack_marl_critic_weights_device` call (two
-        launches) per agent with stale nets, into buffers allocated once; only where the fused kernel covers the shape.
-        Setting it marks the streams stale; a refused value changes nothing."""
-        return self._pack
-
-    @pack.setter
-    def pack(self, mode) -> None:
-        if choose_mode("pack", mode, None, self.PACK_MODES, self._fused_ok, self._shape(), PACK_RULE) != self._pack:
-            self._pack = mode
-            self.mark_stale()
+    def _all_nets(self) -> list:
+        return self._flat
 
     # ------------------------------------------------------------------ weights
     def _agent(self, j, what: str) -> int:
@@ -159,47 +119,16 @@ class BatchedLocalCritics:
         else:
             per_agent = {js[0]: tuple(online)}
         pairs = [p for j in js for net, on, w in self._each(j, per_agent[j], what) for p in polyak_pairs(net, on, w)]
-        for k in range(0, len(pairs), _SOFT_UPDATE_MAX):
-            soft_update_tensors(pairs[k:k + _SOFT_UPDATE_MAX], tau, self.device)
+        soft_update_tensors(pairs, tau, self.device)
         for j in js:
             for net in self.nets[j]:
                 net.mark_stale()
 
-    def mark_stale(self) -> None:
-        """Have the next `forward` / `td_target` rebuild every weight stream: for writers that do not advance the
-        weights' version counters."""
-        for pair in self.nets:
-            for net in pair:
-                net.mark_stale()
-
     def _fused_weights(self) -> list:
-        """[agent][net] (wstream, scales); an agent's stale nets are rebuilt first (pack="host": net by net into new
-        tensors; pack="device": one two-launch pack per agent with stale nets, into the buffers of their first rebuild)."""
+        """[agent][net] (wstream, scales); each agent's stale nets are rebuilt first, agent by agent
+        (`CriticNets._rebuild_stale`: with pack="device" one two-launch pack per agent with stale nets)."""
         for pair in self.nets:
-            stale = []
-            for net in pair:
-                s = net._stale()
-                if s is not None:
-                    stale.append((net,) + s)
-            if not stale:
-                continue
-            if self._pack == "device":
-                dev = self.device
-                if self._pack_workspace is None:
-                    need = int(N.load().risvec_marl_critic_pack_workspace(*self._dims, self.n_nets))
-                    self._pack_workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
-                rows = marl_critic_geom(*self._dims).rows
-                for net, _, _ in stale:
-                    if net._pack_buffers is None:
-                        net._pack_buffers = stream_pair((rows, 64, 8), 3, dev, torch.zeros)
-                pack_marl_critic_weights_device([ws for _, _, ws in stale], out=[net._pack_buffers for net, _, _ in stale],
-                                                workspace=self._pack_workspace)
-                for net, key, _ in stale:
-                    net._packed = (key, net._pack_buffers)
-            else:
-                for net, key, ws in stale:
-                    net._packed = (key, pack_marl_critic_weights(*ws))
-            self.packs += len(stale)
+            self._rebuild_stale(pair)
         return [[net._packed[1] for net in pair] for pair in self.nets]
 
     # ------------------------------------------------------------------ forward
@@ -229,32 +158,10 @@ class BatchedLocalCritics:
 
     def _q_outs(self, q, n: int, what: str):
         """The caller's q buffers as a tuple of n_nets tensors [V, n, 1] (or None)."""
-        if q is None:
-            return None
-        if isinstance(q, torch.Tensor):
-            q = (q,)
-        q = tuple(q)
-        shape = (self.n_agents, n, 1)
-        if len(q) != self.n_nets or any(t is None for t in q):
-            raise ValueError("%s must hold %d tensors of shape %s" % (what, self.n_nets, shape))
-        for t in q:
-            N.in_place(t, torch.float32, shape, what, self.device)
-        if self.n_nets == 2 and q[0].data_ptr() == q[1].data_ptr():
-            raise ValueError("%s: the two tensors are the same" % what)
-        return q
-
-    def _fused(self, n: int) -> bool:
-        return self.gemm == "fused" and n >= self.fused_min_rows
+        return q_outs(q, self.n_nets, (self.n_agents, n, 1), what, self.device)
 
     def _launch(self, n, obs, action, heads, power, reward, done, gamma, coef, lp, li, qs, y) -> None:
-        nets = (N.RisVecMarlCriticNet * (self.n_agents * self.n_nets))()
-        k = 0
-        for pair, packed in zip(self.nets, self._fused_weights()):
-            for net, (ws, scales) in zip(pair, packed):
-                nets[k] = N.RisVecMarlCriticNet(ws.data_ptr(), ws.numel() * ws.element_size(), scales.data_ptr(),
-                                                net.b1.data_ptr(), net.b2.data_ptr(), net.b3.data_ptr(), net.Wq.data_ptr(),
-                                                net.bq.data_ptr())
-                k += 1
+        nets = net_table(len(self._flat), self._flat, chain.from_iterable(self._fused_weights()))
         q1 = qs[0] if qs is not None else None
         q2 = qs[1] if qs is not None and self.n_nets == 2 else None
         N.check(N.load().risvec_local_critics(
@@ -271,7 +178,6 @@ class BatchedLocalCritics:
 
     def q_torch(self, obs: torch.Tensor, action=None, heads=None, power=None) -> tuple:
         """The forward with library kernels only, agent by agent: what gemm="library" runs -> n_nets tensors [V, n, 1]."""
-        F = torch.nn.functional
         n, V = obs.shape[0], self.n_agents
         act = None if action is None else action.view(n, V, self.action_dims)
         out = [[] for _ in range(self.n_nets)]
@@ -279,10 +185,7 @@ class BatchedLocalCritics:
             a = act[:, j] if act is not None else self.next_action_torch(heads, power, j)
             x = torch.cat([obs[:, j], a], dim=1)
             for c, net in enumerate(pair):
-                h = torch.relu(F.linear(x, net.W1, net.b1))
-                h = torch.relu(F.linear(h, net.W2, net.b2))
-                h = torch.relu(F.linear(h, net.W3, net.b3))
-                out[c].append(F.linear(h, net.Wq, net.bq))
+                out[c].append(q_net(net, x))
         return tuple(torch.stack(qs, 0) for qs in out)
 
     def forward(self, obs: torch.Tensor, action: torch.Tensor, out=None):
@@ -320,21 +223,8 @@ class BatchedLocalCritics:
         n = self._rows(obs_, action_, heads, power, what)
         if not is_f32(reward_l, dev, (n, V)):
             raise ValueError("%s: reward_l must be a contiguous float32 tensor of shape (%d, %d) on %s" % (what, n, V, dev))
-        if (not isinstance(done, torch.Tensor) or done.dtype not in (torch.bool, torch.uint8) or done.device != dev
-                or not done.is_contiguous() or tuple(done.shape) != (n,)):
-            raise ValueError("%s: done must be a contiguous bool or uint8 tensor of shape (%d,) on %s" % (what, n, dev))
-        if not math.isfinite(float(gamma)):
-            raise ValueError("%s: gamma must be finite" % what)
-        for name, t in (("logp_power", logp_power), ("logp_intent", logp_intent)):
-            if t is not None and not is_f32(t, dev, (n, V)):
-                raise ValueError("%s: %s must be a contiguous float32 tensor of shape (%d, %d) on %s" % (what, name, n, V, dev))
-        if logp_power is not None or logp_intent is not None:
-            if coef is None:
-                raise ValueError("%s: logp_power / logp_intent need coef, a float32 tensor of 2 values on %s" % (what, dev))
-            if not is_f32(coef, dev) or coef.numel() != 2:
-                raise ValueError("%s: coef must be a contiguous float32 tensor of 2 values on %s" % (what, dev))
-        else:
-            coef = None
+        done_gamma_args(done, gamma, n, dev)
+        coef = entropy_args(logp_power, logp_intent, coef, ((n, V),), dev)
         out = out_f32(out, (V, n), "td_target: out", dev)
         qs = self._q_outs(q, n, "td_target: q")
         if not self._fused(n):
@@ -343,12 +233,8 @@ class BatchedLocalCritics:
                 for t, v in zip(qs, qv):
                     t.copy_(v)
             t = (torch.minimum(qv[0], qv[1]) if self.n_nets == 2 else qv[0]).view(V, n)
-            if logp_power is not None and logp_intent is not None:
-                t = t - (coef.view(2)[0] * logp_power.t() + coef.view(2)[1] * logp_intent.t())
-            elif logp_power is not None:
-                t = t - coef.view(2)[0] * logp_power.t()
-            elif logp_intent is not None:
-                t = t - coef.view(2)[1] * logp_intent.t()
+            t = minus_entropy(t, coef, None if logp_power is None else logp_power.t(),
+                              None if logp_intent is None else logp_intent.t())
             live = (1 - (done.view(torch.bool) if done.dtype == torch.uint8 else done).float()) * float(gamma)
             return out.copy_(reward_l.t() + live.view(1, n) * t)
         d8 = done.view(torch.uint8) if done.dtype == torch.bool else done

@@ -17,14 +17,14 @@ path.
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _native as N
-from ._weights import (PACK_RULE, WeightSet, choose_mode, is_f32, load_weight_sets, out_f32, pack_out, pack_workspace, polyak_pairs,
-                       polyak_tau, rows_of, share_weight_sets, soft_update_tensors, stream_pair, td_args, td_select)
+from ._critic_nets import CriticNets, _Net, draw_net, entropy_args, minus_entropy, net_table, q_net, q_outs  # noqa: F401 (_Net)
+from ._weights import (is_f32, load_weight_sets, out_f32, pack_out, pack_workspace, polyak_pairs, polyak_tau, rows_of,
+                       share_weight_sets, soft_update_tensors, td_args, td_select)
 from ._wstream import _WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags
 
 
@@ -153,35 +153,12 @@ def _unpack(stream: torch.Tensor, scales: torch.Tensor, state_dims: int, action_
             "fc3": _unfrags(_from_wave(s[g.fc3:g.rows], g.mt3, 8 * g.mt2), "cd") * sc[2]}
 
 
-class _Net(WeightSet):
-    """One `CriticNetwork`'s weights (NET:29-32) and weight stream; `BatchedTwinCritic` rebuilds the stale streams of its
-    nets together."""
-    _WEIGHTS = ("W1", "b1", "W2", "b2", "W3", "b3", "Wq", "bq")
-    _SD = {"fc1.weight": "W1", "fc1.bias": "b1", "fc2.weight": "W2", "fc2.bias": "b2", "fc3.weight": "W3", "fc3.bias": "b3",
-           "q.weight": "Wq", "q.bias": "bq"}
-    _PACKED = ("W1", "W2", "W3")                              # what the weight stream is built from
-    _NOUN = "critic"
-
-    def __init__(self, device):
-        self.device = device
-        self._packed = (None, None)                           # (key, (wstream, scales))
-        self._pack_buffers = None                             # pack="device": (wstream, scales), at first use
-
-    packed = property(lambda self: self._packed)              # the cache slot under the name it had before `WeightSet`
-
-
-class BatchedTwinCritic:
+class BatchedTwinCritic(CriticNets):
     """`global_target_critic1` / `global_target_critic2` (`global_sac_critic.py:55-62`; `CriticNetwork`, NET:7-49) for n
     rows at once.  `state_dims` is the flattened state width (n_agents x per-agent width), `action_dims` the flattened
     action width (n_agents x per-agent action); the outputs are q [n, 1] per net.  n_nets=1 is one `CriticNetwork`: the
-    local critics of `sac_agent.py:276-284` have the same class and the same target form, one call per agent."""
-
-    GEMM_MODES = ("fused", "library")
-    PACK_MODES = ("host", "device")
-    #: with gemm=None, batches of fewer rows than this run the library path even where the fused kernel is built
-    #: (the measured crossover, profiles/marl_critic.json; 1 = fused at every row count)
-    AUTO_MIN_ROWS = 1
-    _SD = _Net._SD
+    local critics of `sac_agent.py:276-284` have the same class and the same target form, one call per agent.  With
+    pack="device" both nets' stale weight streams are rebuilt together, in two launches (see `CriticNets.pack`)."""
 
     def __init__(self, state_dims: int, action_dims: int, fc1_dims: int = 1024, fc2_dims: int = 512, fc3_dims: int = 256,
                  n_nets: int = 2, device="cuda", seed: int = 0, gemm: Optional[str] = None):
@@ -197,54 +174,21 @@ class BatchedTwinCritic:
         self.state_dims, self.action_dims = int(state_dims), int(action_dims)
         self.fc1_dims, self.fc2_dims, self.fc3_dims = int(fc1_dims), int(fc2_dims), int(fc3_dims)
         self.n_nets = int(n_nets)
-        dims = (self.state_dims, self.action_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims)
-        if min(dims) < 1:
+        self._dims = (self.state_dims, self.action_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims)
+        if min(self._dims) < 1:
             raise ValueError("BatchedTwinCritic: every dimension must be >= 1")
         if self.n_nets not in (1, 2):
             raise ValueError("BatchedTwinCritic: n_nets must be 1 or 2")
-        fused_ok = bool(lib.risvec_marl_critic_supported(*dims))
-        self.gemm = choose_mode("gemm", gemm, "fused" if fused_ok else "library", self.GEMM_MODES, fused_ok, self._shape(),
-                                "fused: state_dims + action_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in "
-                                "{128, 256}")
-        self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
-        self._fused_ok = fused_ok
-        self._pack = "host"                                   # see `pack`
-        self._pack_workspace = None                           # pack="device": one workspace for both nets, at first use
-        self.packs = 0                                        # how often a net's weight stream was rebuilt
-        dev = self.device
+        self._init_modes(gemm, bool(lib.risvec_marl_critic_supported(*self._dims)),
+                         "fused: state_dims + action_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}")
         g = torch.Generator(device="cpu").manual_seed(seed)
-
-        def uni(*shape, r):
-            return ((torch.rand(*shape, generator=g) * 2 - 1) * r).to(dev)
-        IN = self.state_dims + self.action_dims
-        self.nets = []
-        for _ in range(self.n_nets):                          # nn.Linear's default ranges (NET:29-32): 1 / sqrt(fan_in)
-            net = _Net(dev)
-            for w, b, fan_out, fan_in in (("W1", "b1", self.fc1_dims, IN), ("W2", "b2", self.fc2_dims, self.fc1_dims),
-                                          ("W3", "b3", self.fc3_dims, self.fc2_dims), ("Wq", "bq", 1, self.fc3_dims)):
-                r = 1.0 / math.sqrt(fan_in)
-                setattr(net, w, uni(fan_out, fan_in, r=r))
-                setattr(net, b, uni(fan_out, r=r))
-            self.nets.append(net)
+        self.nets = [draw_net(g, self.state_dims + self.action_dims, *self._dims[2:], self.device) for _ in range(self.n_nets)]
 
     def _shape(self) -> str:
-        return "state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d" % (self.state_dims, self.action_dims, self.fc1_dims,
-                                                                      self.fc2_dims, self.fc3_dims)
+        return "state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d" % self._dims
 
-    @property
-    def pack(self) -> str:
-        """How the fused kernel's weight streams are rebuilt after a weight update.  "host" (the default):
-        `pack_marl_critic_weights` once per stale net, library kernels into new tensors.  "device":
-        `pack_marl_critic_weights_device`, two launches for all stale nets together into buffers allocated once -- for
-        target critics that are blended every learning step (see `soft_update_from`); only where the fused kernel covers
-        the shape.  Setting it marks the streams stale; a refused value changes nothing."""
-        return self._pack
-
-    @pack.setter
-    def pack(self, mode) -> None:
-        if choose_mode("pack", mode, None, self.PACK_MODES, self._fused_ok, self._shape(), PACK_RULE) != self._pack:
-            self._pack = mode
-            self.mark_stale()
+    def _all_nets(self) -> list:
+        return self.nets
 
     # ------------------------------------------------------------------ weights
     def state_dict(self) -> list:
@@ -283,39 +227,9 @@ class BatchedTwinCritic:
         soft_update_tensors(pairs, tau, self.device)
         self.mark_stale()
 
-    def mark_stale(self) -> None:
-        """Have the next `forward` / `td_target` rebuild the weight streams: for writers that do not advance the weights'
-        version counters."""
-        for net in self.nets:
-            net.mark_stale()
-
     def _fused_weights(self) -> list:
-        """(wstream, scales) of every net; a net's are rebuilt when one of its packed weight tensors is replaced or updated
-        in place, or after `mark_stale` (pack="host": library kernels into new tensors, net by net; pack="device": the
-        stale nets together in two launches, into the buffers of their first rebuild)."""
-        stale = []
-        for net in self.nets:
-            s = net._stale()
-            if s is not None:
-                stale.append((net,) + s)
-        if stale and self._pack == "device":
-            dev = self.device
-            if self._pack_workspace is None:
-                need = int(N.load().risvec_marl_critic_pack_workspace(self.state_dims, self.action_dims, self.fc1_dims,
-                                                                      self.fc2_dims, self.fc3_dims, self.n_nets))
-                self._pack_workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
-            rows = marl_critic_geom(self.state_dims, self.action_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims).rows
-            for net, _, _ in stale:
-                if net._pack_buffers is None:
-                    net._pack_buffers = stream_pair((rows, 64, 8), 3, dev, torch.zeros)
-            pack_marl_critic_weights_device([ws for _, _, ws in stale], out=[net._pack_buffers for net, _, _ in stale],
-                                            workspace=self._pack_workspace)
-            for net, key, _ in stale:
-                net._packed = (key, net._pack_buffers)
-        else:
-            for net, key, ws in stale:
-                net._packed = (key, pack_marl_critic_weights(*ws))
-        self.packs += len(stale)
+        """(wstream, scales) of every net, the stale ones rebuilt first (`CriticNets._rebuild_stale`)."""
+        self._rebuild_stale(self.nets)
         return [net._packed[1] for net in self.nets]
 
     # ------------------------------------------------------------------ forward
@@ -325,34 +239,14 @@ class BatchedTwinCritic:
 
     def _q_outs(self, q, n: int, what: str):
         """The caller's q buffers as a tuple of n_nets tensors [n, 1] (or None)."""
-        if q is None:
-            return None
-        if isinstance(q, torch.Tensor):
-            q = (q,)
-        q = tuple(q)
-        if len(q) != self.n_nets:
-            raise ValueError("%s must hold %d tensors of shape (%d, 1)" % (what, self.n_nets, n))
-        for t in q:
-            if t is None:
-                raise ValueError("%s must hold %d tensors of shape (%d, 1)" % (what, self.n_nets, n))
-            N.in_place(t, torch.float32, (n, 1), what, self.device)
-        if self.n_nets == 2 and q[0].data_ptr() == q[1].data_ptr():
-            raise ValueError("%s: the two tensors are the same" % what)
-        return q
-
-    def _fused(self, n: int) -> bool:
-        return self.gemm == "fused" and n >= self.fused_min_rows
+        return q_outs(q, self.n_nets, (n, 1), what, self.device)
 
     def _launch(self, n, state, action, reward, done, gamma, coef, lp, li, qs, y) -> None:
-        nets = (N.RisVecMarlCriticNet * self.n_nets)()
-        for c, (net, (ws, scales)) in enumerate(zip(self.nets, self._fused_weights())):
-            nets[c] = N.RisVecMarlCriticNet(ws.data_ptr(), ws.numel() * ws.element_size(), scales.data_ptr(), net.b1.data_ptr(),
-                                            net.b2.data_ptr(), net.b3.data_ptr(), net.Wq.data_ptr(), net.bq.data_ptr())
+        nets = net_table(self.n_nets, self.nets, self._fused_weights())
         q1 = qs[0] if qs is not None else None
         q2 = qs[1] if qs is not None and self.n_nets == 2 else None
         N.check(N.load().risvec_marl_critic(
-            n, self.state_dims, self.action_dims, self.fc1_dims, self.fc2_dims, self.fc3_dims, self.n_nets,
-            C.cast(nets, C.c_void_p), state.data_ptr(), action.data_ptr(), N.ptr(reward), N.ptr(done), float(gamma),
+            n, *self._dims, self.n_nets, C.cast(nets, C.c_void_p), state.data_ptr(), action.data_ptr(), N.ptr(reward), N.ptr(done), float(gamma),
             N.ptr(coef), N.ptr(lp), N.ptr(li), N.ptr(q1), N.ptr(q2), N.ptr(y), N.stream(self.device)))
 
     def forward(self, state: torch.Tensor, action: torch.Tensor, out=None):
@@ -385,17 +279,7 @@ class BatchedTwinCritic:
         tensors (a pair; one when n_nets == 1) that receive Q_c(state_, action_)."""
         n, dev = self._rows(state_, action_), self.device
         td_args(reward, done, gamma, n, dev)
-        for name, t in (("logp_power", logp_power), ("logp_intent", logp_intent)):
-            if t is not None and not (is_f32(t, dev, (n,)) or is_f32(t, dev, (n, 1))):
-                raise ValueError("td_target: %s must be a contiguous float32 tensor of shape (%d,) or (%d, 1) on %s"
-                                 % (name, n, n, dev))
-        if logp_power is not None or logp_intent is not None:
-            if coef is None:
-                raise ValueError("td_target: logp_power / logp_intent need coef, a float32 tensor of 2 values on %s" % dev)
-            if not is_f32(coef, dev) or coef.numel() != 2:
-                raise ValueError("td_target: coef must be a contiguous float32 tensor of 2 values on %s" % dev)
-        else:
-            coef = None
+        coef = entropy_args(logp_power, logp_intent, coef, ((n,), (n, 1)), dev)
         out = out_f32(out, (n,), "td_target: out", dev)
         qs = self._q_outs(q, n, "td_target: q")
         if not self._fused(n):
@@ -404,27 +288,16 @@ class BatchedTwinCritic:
                 for t, v in zip(qs, qv):
                     t.copy_(v)
             m = (torch.minimum(qv[0], qv[1]) if self.n_nets == 2 else qv[0]).view(n)
-            if logp_power is not None and logp_intent is not None:
-                m = m - (coef.view(2)[0] * logp_power.view(n) + coef.view(2)[1] * logp_intent.view(n))
-            elif logp_power is not None:
-                m = m - coef.view(2)[0] * logp_power.view(n)
-            elif logp_intent is not None:
-                m = m - coef.view(2)[1] * logp_intent.view(n)
+            m = minus_entropy(m, coef, None if logp_power is None else logp_power.view(n),
+                              None if logp_intent is None else logp_intent.view(n))
             return td_select(out, reward, done, gamma, m)
         d8 = done.view(torch.uint8) if done.dtype == torch.bool else done
         self._launch(n, state_, action_, reward, d8, gamma, coef, logp_power, logp_intent, qs, out)
         return out
 
     def q_torch(self, state: torch.Tensor, action: torch.Tensor) -> tuple:
-        F = torch.nn.functional
         x = torch.cat([state, action], dim=1)
-        out = []
-        for net in self.nets:
-            h = torch.relu(F.linear(x, net.W1, net.b1))
-            h = torch.relu(F.linear(h, net.W2, net.b2))
-            h = torch.relu(F.linear(h, net.W3, net.b3))
-            out.append(F.linear(h, net.Wq, net.bq))
-        return tuple(out)
+        return tuple(q_net(net, x) for net in self.nets)
 
     def forward_torch(self, state: torch.Tensor, action: torch.Tensor):
         """The same forward with library kernels only (torch.cat, torch.nn.functional.linear, relu): what gemm="library"

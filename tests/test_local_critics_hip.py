@@ -436,3 +436,33 @@ def test_class_refuses_what_it_would_have_to_copy_or_convert():
                  lambda: critic.soft_update_from(0, [{}], 0.5), lambda: critic.soft_update_from(None, [], 0.5)):
         with pytest.raises((ValueError, KeyError)):
             call()
+
+
+def test_seeded_constructor_draws_the_same_weights_as_before():
+    """`BatchedLocalCritics(seed=7)`: the draw loop as it stood in the constructor, restated literally on a CPU generator
+    -- agent 0 net 1, agent 0 net 2, agent 1 net 1, ...; W1 b1 W2 b2 W3 b3 Wq bq inside a net -- bit for bit."""
+    import math
+    from ris_vec_marl_amd import BatchedLocalCritics
+    V, S, A, F1, F2, F3 = 2, 3, 2, 32, 128, 128
+    g = torch.Generator(device="cpu").manual_seed(7)
+
+    def uni(*shape, r):
+        return (torch.rand(*shape, generator=g) * 2 - 1) * r
+    want = []
+    for _ in range(V):
+        pair = []
+        for _ in range(2):
+            sd = {}
+            for name, fan_out, fan_in in (("fc1", F1, S + A), ("fc2", F2, F1), ("fc3", F3, F2), ("q", 1, F3)):
+                r = 1.0 / math.sqrt(fan_in)
+                sd[name + ".weight"] = uni(fan_out, fan_in, r=r)
+                sd[name + ".bias"] = uni(fan_out, r=r)
+            pair.append(sd)
+        want.append(pair)
+    got = BatchedLocalCritics(V, S, A, F1, F2, F3, seed=7).state_dict()
+    assert [len(pair) for pair in got] == [2, 2]
+    for pair, refs in zip(got, want):
+        for sd, ref in zip(pair, refs):
+            assert list(sd) == list(ref)
+            for k in ref:
+                assert sd[k].dtype == torch.float32 and torch.equal(sd[k], ref[k]), k

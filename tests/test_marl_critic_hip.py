@@ -387,3 +387,29 @@ def test_example_runs():
     print(out.stdout[-1500:], out.stderr[-1500:])
     assert out.returncode == 0
     assert "mean target" in out.stdout
+
+
+def test_seeded_constructor_draws_the_same_weights_as_before():
+    """`BatchedTwinCritic(seed=7)`: the draw loop as it stood in the constructor, restated literally on a CPU generator --
+    net 1 then net 2, W1 b1 W2 b2 W3 b3 Wq bq inside a net -- bit for bit."""
+    import math
+    from ris_vec_marl_amd import BatchedTwinCritic
+    S, A, F1, F2, F3 = 3, 2, 32, 128, 128
+    g = torch.Generator(device="cpu").manual_seed(7)
+
+    def uni(*shape, r):
+        return (torch.rand(*shape, generator=g) * 2 - 1) * r
+    want = []
+    for _ in range(2):
+        sd = {}
+        for name, fan_out, fan_in in (("fc1", F1, S + A), ("fc2", F2, F1), ("fc3", F3, F2), ("q", 1, F3)):
+            r = 1.0 / math.sqrt(fan_in)
+            sd[name + ".weight"] = uni(fan_out, fan_in, r=r)
+            sd[name + ".bias"] = uni(fan_out, r=r)
+        want.append(sd)
+    got = BatchedTwinCritic(S, A, F1, F2, F3, seed=7).state_dict()
+    assert len(got) == 2
+    for sd, ref in zip(got, want):
+        assert list(sd) == list(ref)
+        for k in ref:
+            assert sd[k].dtype == torch.float32 and torch.equal(sd[k], ref[k]), k

@@ -92,9 +92,14 @@ def test_32_tensors_at_once_and_the_contracted_form_would_fail():
     from ris_vec_marl_amd import _native as N
     blend_and_check([(1 + 37 * i, i % 4, i % 4 if i % 3 else (i + 1) % 4) for i in range(32)], 0.005)
     assert N.last_kernel() == "k_soft_update"
-    from ris_vec_marl_amd.actor import soft_update_tensors
+    # 33 are more than a launch takes: the entry point refuses them, and `soft_update_tensors` blends them in runs of 32 and 1
+    import ctypes as C
+    ts = [torch.zeros(4, device=DEV) for _ in range(66)]
+    on, tg = (C.c_void_p * 33)(*(t.data_ptr() for t in ts[:33])), (C.c_void_p * 33)(*(t.data_ptr() for t in ts[33:]))
+    assert N.load().risvec_soft_update(33, on, tg, (C.c_int64 * 33)(*([4] * 33)), 0.5, 0.5, N.stream(torch.device(DEV))) == N.ERR_SHAPE
     with pytest.raises(ValueError):
-        soft_update_tensors([(torch.zeros(4, device=DEV), torch.zeros(4, device=DEV)) for _ in range(33)], 0.5, torch.device(DEV))
+        N.check(N.ERR_SHAPE)
+    blend_and_check([(1 + 37 * i, i % 4, i % 4 if i % 3 else (i + 1) % 4) for i in range(33)], 0.005)
     # the oracle tells the two forms apart: a fused multiply-add (computed in float64, rounded once) gives other bits
     g = torch.Generator().manual_seed(9)
     a, b = torch.randn(1 << 16, generator=g), torch.randn(1 << 16, generator=g)
