@@ -84,7 +84,7 @@ enum {
                                        latency-shaped kernels' NT and ALT members.  Every other kernel -- the latency-shaped
                                        members with the default cache policy among them -- ignores the bit.  Unlike
                                        RISVEC_STEP_THETA_BY_INDEX the tensor is not stale. */
-    RISVEC_STEP_H_R_STEER_CURRENT = 2048 /* risvec_step_fused and the fused form of risvec_step_ring: state.h_r is exactly
+    RISVEC_STEP_H_R_STEER_CURRENT = 2048, /* risvec_step_fused and the fused form of risvec_step_ring: state.h_r is exactly
                                        what risvec_geometry wrote from the state.steer_ang / state.z_r now in the state, so
                                        a kernel may rebuild rows instead of reading them.  Like
                                        RISVEC_STEP_THETA_IDX_CURRENT it never changes the plan or the kernel name; where
@@ -95,6 +95,14 @@ enum {
                                        (risvec_last_h_r_rebuilt() tells; the walk stays the pipeline's).  Ignored everywhere else: the latency family,
                                        the generic kernels, n_ris % 16 != 0, steer_ang or z_r NULL.  Not accepted
                                        together with RISVEC_STEP_STEER. */
+    RISVEC_STEP_STEER_HEADS_CURRENT = 8192 /* only together with RISVEC_STEP_H_R_STEER_CURRENT (alone: RISVEC_ERR_ARG): the
+                                       allocation state.steer_ang points to holds the n_envs * n_veh angles followed AT ONCE
+                                       by [n_envs, n_veh, n_ris / 16] complex128 chunk heads, as risvec_steer_heads wrote
+                                       them from those angles.  The GEN member then reads the head of each 16-element chunk
+                                       (16 bytes) instead of evaluating it with sincospi on every launch and does not read
+                                       the angles; the rotations start from the same float64 pair, so every output stays
+                                       bit for bit (risvec_last_h_r_heads() tells).  Never changes the plan, the kernel
+                                       name or the walk; dropped silently wherever RISVEC_STEP_H_R_STEER_CURRENT is. */
 };
 
 /* risvec_bcd flags */
@@ -265,6 +273,9 @@ int risvec_last_h_r_rebuilt(void);
  * (risvec_last_h_r_rebuilt() == 1), else 0.  1 = the member without a group loop ran: the launcher picks it exactly when
  * every wavefront owns one group.  Results and kernel name do not depend on it. */
 int risvec_last_gen_groups_per_wave(void);
+/* 1 when the calling thread's last step launch was a GEN member that read the chunk heads behind state.steer_ang
+ * (RISVEC_STEP_STEER_HEADS_CURRENT) instead of evaluating them, else 0. */
+int risvec_last_h_r_heads(void);
 const char *risvec_last_error(void);
 
 /* Forms of a step call, for risvec_step_kernel(): risvec_step, risvec_step_fused, risvec_step_ring (cached / fused),
@@ -329,6 +340,12 @@ int risvec_geometry(const RisVecState *s, const RisVecParams *p, risvec_stream_t
  * state.steer_ang / state.z_r, by the routine risvec_geometry itself runs.  n_ris must be a multiple of 16.  After
  * risvec_geometry, `out` equals state.h_r bit for bit; tests compare the two. */
 int risvec_h_r_from_steer(const RisVecState *s, float *out, risvec_stream_t stream);
+
+/* The head of every 16-element chunk of every h_r row in float64: heads[e,v,c] = exp(-j pi steer_ang[e,v] 16 c) as
+ * (re, im), [E,V,M/16] complex128 (16-byte aligned), by the routine risvec_geometry starts each chunk with.  n_ris must
+ * be a multiple of 16.  The heads are a function of state.steer_ang alone: write them after risvec_geometry, directly
+ * behind the angles, and the fused step may be sent RISVEC_STEP_STEER_HEADS_CURRENT until the angles change. */
+int risvec_steer_heads(const RisVecState *s, double *heads, risvec_stream_t stream);
 
 /* update_channel_gains, "free" model (ENV:263-273): theta, h_r, b, pl -> gain. */
 int risvec_gain(const RisVecState *s, const RisVecParams *p, risvec_stream_t stream);

@@ -30,7 +30,8 @@ STEP_REUSE_IDX = 128
 STEP_THETA_BY_INDEX = 256
 STEP_THETA_IDX_CURRENT = 1024     # state.theta_idx matches state.theta: a kernel may read either (fused forms)
 STEP_H_R_STEER_CURRENT = 2048     # state.h_r is what risvec_geometry wrote from steer_ang / z_r: a kernel may rebuild rows
-STEP_3GPP = 512          # risvec_step_kernel(): the 3GPP member of the form (the 3GPP entry points set it themselves)
+STEP_STEER_HEADS_CURRENT = 8192   # with the bit above: the chunk heads stand behind the angles at state.steer_ang
+STEP_3GPP = 512         # risvec_step_kernel(): the 3GPP member of the form (the 3GPP entry points set it themselves)
 BCD_REUSE_COLSUM, BCD_REUSE_SSUM, BCD_REUSE_IDX, BCD_NO_THETA = 1, 2, 4, 8
 FORM_CACHED, FORM_FUSED, FORM_CACHED_RING, FORM_FUSED_RING, FORM_FUSED_MULTI = range(5)
 BY_RULE, FORCE_OFF, FORCE_ON = range(3)
@@ -192,7 +193,9 @@ _PROTOS = {
     "risvec_last_pipe_walk": (C.c_int, []),
     "risvec_last_h_r_rebuilt": (C.c_int, []),
     "risvec_last_gen_groups_per_wave": (C.c_int, []),
+    "risvec_last_h_r_heads": (C.c_int, []),
     "risvec_h_r_from_steer": (C.c_int, [C.POINTER(RisVecState), _FP, _FP]),
+    "risvec_steer_heads": (C.c_int, [C.POINTER(RisVecState), _FP, _FP]),
     "risvec_step_kernel": (C.c_char_p, [C.POINTER(RisVecState), C.c_uint32, C.c_int32]),
     "risvec_force_forms": (C.c_int, [C.POINTER(RisVecForce)]),
     "risvec_default_params": (None, [C.POINTER(RisVecParams)]),
@@ -400,6 +403,12 @@ def last_h_r_rebuilt() -> int:
     """1 if the calling thread's last step launch rebuilt the h_r rows from steer_ang / z_r instead of reading them
     (risvec_last_h_r_rebuilt)."""
     return int(load().risvec_last_h_r_rebuilt())
+
+
+def last_h_r_heads() -> int:
+    """1 if the calling thread's last step launch was a GEN member that read the chunk heads instead of evaluating them
+    (risvec_last_h_r_heads)."""
+    return int(load().risvec_last_h_r_heads())
 
 
 def last_gen_groups_per_wave() -> int:

@@ -326,6 +326,8 @@ static hipError_t launch_step_vp(const RisVecState& s, const RisVecParams& p, co
 //   cache policy), M % 16 == 0 and the state carries steer_ang and z_r, launch_step runs the pipeline's GEN member
 //   k_step_fused_gen<V,M,Core,TK?> (k_step_gen.hip): the rows are rebuilt by steer_chunk(), not read; the walk is the
 //   pipeline's (the order of a wavefront's groups).  Everywhere else the bit is ignored.
+//   RISVEC_STEP_STEER_HEADS_CURRENT rides on that bit: where the GEN member runs, its HD form reads the chunk heads
+//   kept behind state.steer_ang (risvec_steer_heads) instead of evaluating them; where it does not, the bit is dropped.
 //
 // Why (us per step; profiles/):
 //   * beyond 1.29 IC many short wavefronts with every request up front are what the best pure reader looks like: 1-4 %
@@ -526,7 +528,7 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
     if (pl.family == StepPlan::NONE) return hipErrorNotSupported;
     StepArgs a = make_step_args(s, action, partner, n_groups, arrivals, seed, counter,
                                 flags & ~(uint32_t)(RISVEC_STEP_STEER | RISVEC_STEP_THETA_BY_INDEX | RISVEC_STEP_THETA_IDX_CURRENT |
-                                                    RISVEC_STEP_H_R_STEER_CURRENT));
+                                                    RISVEC_STEP_H_R_STEER_CURRENT | RISVEC_STEP_STEER_HEADS_CURRENT));
     if (ring) a.ring = *ring;                                  // the transition store rides in the step kernel
     // theta is kept by index (the API checked the shape), or the indices are known to match the tensor and the plan is one
     // of the byte-bound kernels with a by-index instantiation: the software pipeline (either cache policy, the ring form
@@ -543,6 +545,10 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
     // whose rows are whole 16-element chunks: its GEN member rebuilds the rows instead of reading them (same bits).
     const bool gen = (flags & RISVEC_STEP_H_R_STEER_CURRENT) && pl.family == StepPlan::PIPE && pl.M % 16 == 0 &&
                      s.steer_ang != nullptr && s.z_r != nullptr;
+    // ... and the chunk heads stand behind the angles: the member that reads them instead of evaluating sincospi (the
+    // same float64 pair either way).  No plan and no name changes; dropped wherever the GEN member is.  (A GEN shape has
+    // V in {4, 8, 16}, so the heads, n_envs * n_veh doubles behind a 16-byte aligned pointer, are 16-byte aligned.)
+    const bool heads = gen && (flags & RISVEC_STEP_STEER_HEADS_CURRENT);
     hipError_t err;
     if (pl.family == StepPlan::LAT) err = launch_step_fused_lat(s, p, a, pl, 1, RisVecTraj{}, st);
     else if (pl.family == StepPlan::PIPE) {
@@ -551,12 +557,13 @@ hipError_t launch_step(const RisVecState& s, const RisVecParams& p, const float*
         // name, same results; RisVecForce::pipe_rev pins the direction.  The GEN member keeps the walk (the order of a
         // wavefront's groups) for what it still reads.
         const bool rev = pl.pol == 0 && forced_or(forced_forms().pipe_rev, (a.counter & 1u) != 0);
-        err = gen ? launch_step_fused_gen(s, p, a, pl, rev, st) : launch_step_fused_pipe(s, p, a, pl, rev, st);
+        err = gen ? launch_step_fused_gen(s, p, a, pl, rev, heads, st) : launch_step_fused_pipe(s, p, a, pl, rev, st);
     }
     else err = with_vp(s.n_veh, [&](auto vp) { return launch_step_vp<vp>(s, p, a, pl, st); });
     note_kernel("%s", pl.name);
     note_theta_by_index(a.theta_k != nullptr);
     note_h_r_rebuilt(gen);
+    note_h_r_heads(heads);
     return err;
 }
 

@@ -27,6 +27,9 @@
 //     that a field's place in the segment is its offsetof.
 //   * ONE: the member for launches in which every wavefront owns one group (the headline: 4 096 groups on 4 096
 //     wavefronts).  No group loop, no second set of step() inputs, no request for "the next group".
+//   * HD (RISVEC_STEP_STEER_HEADS_CURRENT): the sincospi at the head of a chunk is a function of the angle alone, so
+//     risvec_steer_heads() evaluates it once per geometry and the feed reads the float64 pair (steer_head() /
+//     steer_chunk_from_head(), risvec_dev.hpp): 48 vector instructions per pass less, 16 bytes per lane and pass more.
 #include <cstddef>
 
 #include "risvec_pipe.hpp"
@@ -52,17 +55,24 @@ struct GenShape : PipeShape<V, M> {
     static constexpr int STAGE = kWave * (kGeoChunk / 2 + 1);  // float4 per wavefront: 64 chunks of 8 (+1 pad)
 };
 
-// what one outer iteration reads from memory
-template <int SP, int EPO, int NIT, bool TK>
-struct GenFeed {
+// what one outer iteration reads from memory: per pass the lane's chunk -- its row's angle, or (HD) the chunk's head as
+// risvec_steer_heads stored it -- and the row's w; per env theta or its indices
+template <int SP, bool HD>
+struct GenRows {
     double ang[SP];
     double2 w[SP];
+};
+template <int SP>
+struct GenRows<SP, true> {
+    double2 head[SP];
+    double2 w[SP];
+};
+template <int SP, int EPO, int NIT, bool TK, bool HD>
+struct GenFeed : GenRows<SP, HD> {
     float4 t[EPO][NIT];
 };
-template <int SP, int EPO, int NIT>
-struct GenFeed<SP, EPO, NIT, true> {
-    double ang[SP];
-    double2 w[SP];
+template <int SP, int EPO, int NIT, bool HD>
+struct GenFeed<SP, EPO, NIT, true, HD> : GenRows<SP, HD> {
     unsigned k[EPO][NIT];
 };
 
@@ -78,7 +88,7 @@ struct GenArgs {
     Dims d;
     typename Core::Params P;
     typename Core::Args A;
-    const double* steer_ang;
+    const double* steer;            // HD: the chunk heads [E,V,M/16] complex128, else state.steer_ang [E,V]
     const double* z_r;
     int n_groups_total, per_wave, rev;
 };
@@ -97,8 +107,11 @@ __device__ __forceinline__ const GenArgs<Core>& late_args() {
 }
 
 // TK: theta by index, as in k_step_fused_pipe.  ONE: every wavefront owns one group (group `wid`; per_wave and rev are
-// not read).
-template <int V, int M, class Core, bool TK, bool ONE>
+// not read).  HD (RISVEC_STEP_STEER_HEADS_CURRENT): the head of a chunk, exp(-j pi ang m0) in float64, is a function of
+// the angle alone and changes only when the geometry does, so it is read (16 B per lane and pass, the heads of a pass
+// contiguous) instead of evaluated by sincospi 64 lanes x NCH passes x every launch; the rotations start from the same
+// float64 pair either way.  steer_ang is not read then.
+template <int V, int M, class Core, bool TK, bool ONE, bool HD>
 __global__ void __launch_bounds__(kBlock)
 k_step_fused_gen(GenArgs<Core> KA) {
     using In = typename Core::In;
@@ -107,7 +120,7 @@ k_step_fused_gen(GenArgs<Core> KA) {
     constexpr int PC = S::PC, CHUNKS = S::CHUNKS, K = S::K;
     constexpr int NCH = S::NCH, RPP = S::RPP, RPU = S::RPU, UPP = S::UPP, SP = S::SP, EPO = S::EPO, NO = S::NO;
     static_assert(std::is_same<typename Core::Args, StepArgs>::value, "the GEN members step on StepArgs");
-    using Feed = GenFeed<SP, EPO, NIT, TK>;
+    using Feed = GenFeed<SP, EPO, NIT, TK, HD>;
     __shared__ float s_img[kBlock / kWave][kWave * 2];
     __shared__ float2 s_ph[TK ? kBlock / kWave : 1][16];
     __shared__ float4 s_stage[kBlock / kWave][S::STAGE];
@@ -115,7 +128,7 @@ k_step_fused_gen(GenArgs<Core> KA) {
     // the prologue's view of the arguments: what is named here is loaded at entry.  step() goes through late_args().
     const Dims& d = KA.d;
     const typename Core::Args& A = KA.A;
-    const double* __restrict__ steer_ang = KA.steer_ang;
+    const double* __restrict__ steer = KA.steer;
     const int n_groups_total = KA.n_groups_total;
 
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
@@ -138,7 +151,7 @@ k_step_fused_gen(GenArgs<Core> KA) {
         pcl[it] = (NP % G == 0 || p < NP) ? p : NP - 1;
     }
     // producer: this lane's chunk of a pass -- row lane / NCH of the pass, elements m0 ...
-    const int p_row = lane / NCH, p_m0 = (lane % NCH) * kGeoChunk;
+    const int p_row = lane / NCH, p_ch = lane % NCH, p_m0 = p_ch * kGeoChunk;
     float4* __restrict__ stage = s_stage[wave];
     float4* __restrict__ p_dst = stage + lane * (kGeoChunk / 2 + 1);
     // consumer: float4 `pcl[it]` of row gv of a unit's lane-group pass, as an index into the stage (8 float4 per chunk,
@@ -156,7 +169,8 @@ k_step_fused_gen(GenArgs<Core> KA) {
         for (int sp = 0; sp < SP; ++sp) {
             int row = grp * kWave + (o * SP + sp) * RPP + p_row;
             row = row < row_last ? row : row_last;
-            f.ang[sp] = steer_ang[row];
+            if constexpr (HD) f.head[sp] = reinterpret_cast<const double2*>(steer)[(long long)row * NCH + p_ch];
+            else f.ang[sp] = steer[row];
             f.w[sp] = z2[row];
         }
 #pragma unroll
@@ -181,7 +195,8 @@ k_step_fused_gen(GenArgs<Core> KA) {
 #pragma unroll
         for (int sp = 0; sp < SP; ++sp) {
             float4 q[kGeoChunk / 2];
-            steer_chunk(cur.ang[sp], cur.w[sp].x, cur.w[sp].y, p_m0, q);
+            if constexpr (HD) steer_chunk_from_head(cur.head[sp].x, cur.head[sp].y, cur.w[sp].x, cur.w[sp].y, q);
+            else steer_chunk(cur.ang[sp], cur.w[sp].x, cur.w[sp].y, p_m0, q);
 #pragma unroll
             for (int k = 0; k < kGeoChunk / 2; ++k) p_dst[k] = q[k];
             __builtin_amdgcn_wave_barrier();           // the stage's writes -> its reads (same wave: in order)
@@ -233,10 +248,10 @@ k_step_fused_gen(GenArgs<Core> KA) {
 
     if constexpr (ONE) {
         if constexpr (TK) {
-            RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
+            RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
                                     "s"(n_groups_total), "s"(d.E));
         } else {
-            RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E));
+            RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E));
         }
         const int grp = wid;
         if (grp >= n_groups_total) return;                     // whole wave: no cross-lane op is skipped
@@ -272,10 +287,10 @@ k_step_fused_gen(GenArgs<Core> KA) {
         int grp_end = per_wave > 0 ? grp + per_wave : n_groups_total;
         grp_end = grp_end < n_groups_total ? grp_end : n_groups_total;
         if constexpr (TK) {
-            RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
+            RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
                                     "s"(n_groups_total), "s"(per_wave), "s"(d.E));
         } else {
-            RISVEC_ARGS_IN_ONE_TRIP("s"(steer_ang), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave),
+            RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave),
                                     "s"(d.E));
         }
         if (grp >= grp_end) return;                            // whole wave: no cross-lane op is skipped
@@ -338,7 +353,7 @@ static thread_local int g_gen_per_wave = 0;
 
 template <int V, int M, class Core>
 static hipError_t launch_gen(const RisVecState& s, const typename Core::Params& p, const typename Core::Args& a, bool rev,
-                             hipStream_t st) {
+                             bool heads, hipStream_t st) {
     using S = GenShape<V, M>;
     const int n_groups = (s.n_envs + S::EPW - 1) / S::EPW;
     const int wpb = kBlock / kWave;
@@ -349,17 +364,23 @@ static hipError_t launch_gen(const RisVecState& s, const typename Core::Params& 
     want_waves = (n_groups + per_wave - 1) / per_wave;
     const unsigned grid = (unsigned)((want_waves + wpb - 1) / wpb);
     const int contiguous = forced_waves > 0 ? (int)per_wave : 0;
-    const GenArgs<Core> ka{dims_of(s), p, a, s.steer_ang, s.z_r, n_groups, contiguous, rev ? 1 : 0};
+    // the heads stand behind the angles in the allocation state.steer_ang points to (RISVEC_STEP_STEER_HEADS_CURRENT)
+    const double* steer = heads ? s.steer_ang + (long long)s.n_envs * s.n_veh : s.steer_ang;
+    const GenArgs<Core> ka{dims_of(s), p, a, steer, s.z_r, n_groups, contiguous, rev ? 1 : 0};
     auto go = [&](auto knl) { hipLaunchKernelGGL(knl, dim3(grid), dim3(kBlock), 0, st, ka); };
     // one group per wavefront (then the grid covers the groups, whichever way they are dealt): the member without a
     // group loop
     const bool one = per_wave == 1;
+    auto pick = [&](auto tk, auto hd) {
+        if (one) go(k_step_fused_gen<V, M, Core, decltype(tk)::value, true, decltype(hd)::value>);
+        else go(k_step_fused_gen<V, M, Core, decltype(tk)::value, false, decltype(hd)::value>);
+    };
     if (a.theta_k != nullptr) {
-        if (one) go(k_step_fused_gen<V, M, Core, true, true>);
-        else go(k_step_fused_gen<V, M, Core, true, false>);
+        if (heads) pick(std::true_type{}, std::true_type{});
+        else pick(std::true_type{}, std::false_type{});
     } else {
-        if (one) go(k_step_fused_gen<V, M, Core, false, true>);
-        else go(k_step_fused_gen<V, M, Core, false, false>);
+        if (heads) pick(std::false_type{}, std::true_type{});
+        else pick(std::false_type{}, std::false_type{});
     }
     g_gen_per_wave = (int)per_wave;
     return hipGetLastError();
@@ -370,22 +391,24 @@ int last_gen_launch_groups_per_wave() { return g_gen_per_wave; }
 // the shapes whose rows are whole chunks have GEN members; the others keep reading
 template <int V, int M, bool WHOLE = (M % kGeoChunk == 0)>
 struct GenMember {
-    static hipError_t launch(const RisVecState&, const RisVecParams&, const StepArgs&, bool, bool, hipStream_t) {
+    static hipError_t launch(const RisVecState&, const RisVecParams&, const StepArgs&, bool, bool, bool, hipStream_t) {
         return hipErrorNotSupported;
     }
 };
 template <int V, int M>
 struct GenMember<V, M, true> {
-    static hipError_t launch(const RisVecState& s, const RisVecParams& p, const StepArgs& a, bool ring, bool rev, hipStream_t st) {
-        return ring ? launch_gen<V, M, MarlRingCore<V>>(s, p, a, rev, st) : launch_gen<V, M, MarlCore>(s, p, a, rev, st);
+    static hipError_t launch(const RisVecState& s, const RisVecParams& p, const StepArgs& a, bool ring, bool rev, bool heads,
+                             hipStream_t st) {
+        return ring ? launch_gen<V, M, MarlRingCore<V>>(s, p, a, rev, heads, st)
+                    : launch_gen<V, M, MarlCore>(s, p, a, rev, heads, st);
     }
 };
 
 hipError_t launch_step_fused_gen(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
-                                 bool rev, hipStream_t st) {
+                                 bool rev, bool heads, hipStream_t st) {
     note_pipe_walk(rev ? 1 : 0);
 #define RISVEC_X(VV, MM, DD, EMIN, EMAX, T) \
-    if (pl.V == VV && pl.M == MM) return GenMember<VV, MM>::launch(s, p, a, pl.ring, rev, st);
+    if (pl.V == VV && pl.M == MM) return GenMember<VV, MM>::launch(s, p, a, pl.ring, rev, heads, st);
     RISVEC_FIXED_SHAPES(RISVEC_X)
 #undef RISVEC_X
     return hipErrorNotSupported;
@@ -405,6 +428,22 @@ k_h_r_from_steer(Dims d, const double* __restrict__ steer_ang, const double* __r
     float4* dst = reinterpret_cast<float4*>(out + (ev * d.M + m0) * 2);
 #pragma unroll
     for (int k = 0; k < kGeoChunk / 2; ++k) dst[k] = q[k];
+}
+
+// risvec_steer_heads: one thread per chunk, the head as steer_chunk() would start from it
+__global__ void __launch_bounds__(kBlock)
+k_steer_heads(Dims d, const double* __restrict__ steer_ang, double2* __restrict__ heads) {
+    const int nchunk = d.M / kGeoChunk;
+    const long long idx = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= (long long)d.E * d.V * nchunk) return;
+    heads[idx] = steer_head(steer_ang[idx / nchunk], (int)(idx % nchunk) * kGeoChunk);
+}
+
+hipError_t launch_steer_heads(const RisVecState& s, double* heads, hipStream_t st) {
+    const long long n = (long long)s.n_envs * s.n_veh * (s.n_ris / kGeoChunk);
+    hipLaunchKernelGGL(k_steer_heads, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, dims_of(s), s.steer_ang,
+                       reinterpret_cast<double2*>(heads));
+    return hipGetLastError();
 }
 
 hipError_t launch_h_r_from_steer(const RisVecState& s, float* out, hipStream_t st) {

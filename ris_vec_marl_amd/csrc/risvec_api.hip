@@ -17,6 +17,7 @@ thread_local char g_err[512] = "";
 thread_local char g_kernel[160] = "";
 thread_local int g_theta_by_index = 0;
 thread_local int g_h_r_rebuilt = 0;
+thread_local int g_h_r_heads = 0;
 RisVecForce g_force{};                  // risvec_force_forms(): all RISVEC_BY_RULE
 
 int fail(int code, const char* fmt, ...) {
@@ -177,10 +178,17 @@ int check_step(const char* fn, const RisVecState* s, const float* action, const 
     return RISVEC_OK;
 }
 
-// RISVEC_STEP_THETA_IDX_CURRENT and RISVEC_STEP_H_R_STEER_CURRENT, accepted by risvec_step_fused and the fused form of
-// risvec_step_ring only (check_step refuses them as unknown bits everywhere else): checks what they need and returns the
-// flags check_step sees
+// RISVEC_STEP_THETA_IDX_CURRENT, RISVEC_STEP_H_R_STEER_CURRENT and RISVEC_STEP_STEER_HEADS_CURRENT, accepted by
+// risvec_step_fused and the fused form of risvec_step_ring only (check_step refuses them as unknown bits everywhere else):
+// checks what they need and returns the flags check_step sees
 int check_idx_current(const char* fn, const RisVecState* s, bool fused, uint32_t* flags) {
+    if (*flags & RISVEC_STEP_STEER_HEADS_CURRENT) {
+        if (!fused) return fail(RISVEC_ERR_ARG, "%s: RISVEC_STEP_STEER_HEADS_CURRENT is a hint to the fused forms (this one rebuilds no h_r)", fn);
+        if (!(*flags & RISVEC_STEP_H_R_STEER_CURRENT))
+            return fail(RISVEC_ERR_ARG, "%s: RISVEC_STEP_STEER_HEADS_CURRENT needs RISVEC_STEP_H_R_STEER_CURRENT (the heads serve the "
+                        "rebuilt rows only)", fn);
+        *flags &= ~(uint32_t)RISVEC_STEP_STEER_HEADS_CURRENT;
+    }
     if (*flags & RISVEC_STEP_H_R_STEER_CURRENT) {
         if (!fused) return fail(RISVEC_ERR_ARG, "%s: RISVEC_STEP_H_R_STEER_CURRENT is a hint to the fused forms (this one reads no h_r)", fn);
         if (*flags & RISVEC_STEP_STEER)
@@ -274,11 +282,14 @@ void note_kernel(const char* fmt, ...) {
     va_end(ap);
     g_theta_by_index = 0;
     g_h_r_rebuilt = 0;
+    g_h_r_heads = 0;
 }
 
 void note_theta_by_index(bool by_index) { g_theta_by_index = by_index ? 1 : 0; }
 
 void note_h_r_rebuilt(bool rebuilt) { g_h_r_rebuilt = rebuilt ? 1 : 0; }
+
+void note_h_r_heads(bool heads) { g_h_r_heads = heads ? 1 : 0; }
 
 const RisVecForce& forced_forms() { return g_force; }
 }  // namespace risvec
@@ -294,6 +305,8 @@ int risvec_last_theta_by_index(void) { return g_theta_by_index; }
 int risvec_last_pipe_walk(void) { return risvec::last_pipe_walk(); }
 
 int risvec_last_h_r_rebuilt(void) { return g_h_r_rebuilt; }
+
+int risvec_last_h_r_heads(void) { return g_h_r_heads; }
 
 int risvec_last_gen_groups_per_wave(void) { return g_h_r_rebuilt ? risvec::last_gen_launch_groups_per_wave() : 0; }
 
@@ -419,6 +432,16 @@ int risvec_h_r_from_steer(const RisVecState* s, float* out, risvec_stream_t stre
     if (s->n_ris % 16 != 0)
         return fail(RISVEC_ERR_UNSUPPORTED, "%s: n_ris=%d is not a multiple of 16 (rows are rebuilt in 16-element chunks)", fn, s->n_ris);
     return finish(fn, risvec::launch_h_r_from_steer(*s, out, (hipStream_t)stream));
+}
+
+int risvec_steer_heads(const RisVecState* s, double* heads, risvec_stream_t stream) {
+    const char* fn = "risvec_steer_heads";
+    if (int rc = check_common(fn, s, nullptr, false)) return rc;
+    REQ_PTR(s->steer_ang, "state.steer_ang"); REQ_PTR(heads, "heads");
+    if (s->n_ris % 16 != 0)
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: n_ris=%d is not a multiple of 16 (a head stands in front of a 16-element chunk)", fn,
+                    s->n_ris);
+    return finish(fn, risvec::launch_steer_heads(*s, heads, (hipStream_t)stream));
 }
 
 int risvec_gain(const RisVecState* s, const RisVecParams* p, risvec_stream_t stream) {

@@ -186,13 +186,22 @@ __device__ __forceinline__ float2 phasor_of_angle(float angle) {
 // association below is the one the compiler had chosen for k_geometry (read off its gfx950 code): the w-real product is
 // fused and the w-imaginary product rounded first, except in the first rotation of every pair after the chunk's first,
 // where it is the other way round.
+//
+// The routine is two: steer_head() gives the chunk's first element in float64, steer_chunk_from_head() rotates on from
+// it.  The head depends on the angle alone, so it may be kept in memory (risvec_steer_heads) and the chain started from
+// the stored value (the GEN members under RISVEC_STEP_STEER_HEADS_CURRENT): a float64 store and load change no bit.
 constexpr int kGeoChunk = 16;
 
-__device__ __forceinline__ void steer_chunk(double ang, double wr, double wi, int m0, float4 (&out)[kGeoChunk / 2]) {
+// z = exp(-j pi ang m0) = (zc, -zs)
+__device__ __forceinline__ double2 steer_head(double ang, int m0) {
 #pragma clang fp contract(off)
     double zs, zc;
-    sincospi(__dmul_rn(ang, (double)m0), &zs, &zc);          // z = exp(-j pi ang m0) = (zc, -zs)
-    double ar = zc, ai = -zs;
+    sincospi(__dmul_rn(ang, (double)m0), &zs, &zc);
+    return make_double2(zc, -zs);
+}
+
+__device__ __forceinline__ void steer_chunk_from_head(double ar, double ai, double wr, double wi, float4 (&out)[kGeoChunk / 2]) {
+#pragma clang fp contract(off)
 #pragma unroll
     for (int k = 0; k < kGeoChunk; k += 2) {
         const double br = k == 0 ? fma(ar, wr, -__dmul_rn(ai, wi)) : fma(-ai, wi, __dmul_rn(ar, wr));   // next element
@@ -201,6 +210,11 @@ __device__ __forceinline__ void steer_chunk(double ang, double wr, double wi, in
         ar = fma(br, wr, -__dmul_rn(bi, wi));                                                           // the one after
         ai = fma(bi, wr, __dmul_rn(br, wi));
     }
+}
+
+__device__ __forceinline__ void steer_chunk(double ang, double wr, double wi, int m0, float4 (&out)[kGeoChunk / 2]) {
+    const double2 z = steer_head(ang, m0);
+    steer_chunk_from_head(z.x, z.y, wr, wi, out);
 }
 
 }  // namespace risvec

@@ -220,6 +220,10 @@ void note_kernel(const char* fmt, ...);
 void note_theta_by_index(bool by_index);
 // risvec_last_h_r_rebuilt(): likewise
 void note_h_r_rebuilt(bool rebuilt);
+// risvec_last_h_r_heads(): likewise
+void note_h_r_heads(bool heads);
+// state.steer_ang -> heads [E,V,M/16] c128 by steer_head(), M % 16 == 0 (k_step_gen.hip)
+hipError_t launch_steer_heads(const RisVecState& s, double* heads, hipStream_t st);
 // state.steer_ang / state.z_r -> out [E,V,M] c64 by steer_chunk(), M % 16 == 0 (k_step_gen.hip)
 hipError_t launch_h_r_from_steer(const RisVecState& s, float* out, hipStream_t st);
 

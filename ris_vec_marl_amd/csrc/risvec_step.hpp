@@ -133,12 +133,65 @@ __device__ __forceinline__ float gsum(float x) {
     return x;
 }
 
+// v_permlane16_swap_b32 / v_permlane32_swap_b32 (O = 16 / 32) on one, two or four register pairs (a, b): rows of O lanes,
+// the odd rows of a change places with the even rows of b.  `s_nop 1` = the two wait states the instruction needs behind a
+// VALU write of an operand.
+#define RISVEC_SWAP16 "v_permlane16_swap_b32"
+#define RISVEC_SWAP32 "v_permlane32_swap_b32"
+template <int O>
+__device__ __forceinline__ void swap_rows(float& a0, float& b0) {
+    static_assert(O == 16 || O == 32, "rows of 16 or 32 lanes");
+    if constexpr (O == 16) asm("s_nop 1\n\t" RISVEC_SWAP16 " %0, %1" : "+v"(a0), "+v"(b0));
+    else asm("s_nop 1\n\t" RISVEC_SWAP32 " %0, %1" : "+v"(a0), "+v"(b0));
+}
+template <int O>
+__device__ __forceinline__ void swap_rows(float& a0, float& b0, float& a1, float& b1) {
+    static_assert(O == 16 || O == 32, "rows of 16 or 32 lanes");
+    if constexpr (O == 16)
+        asm("s_nop 1\n\t" RISVEC_SWAP16 " %0, %1\n\t" RISVEC_SWAP16 " %2, %3" : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1));
+    else
+        asm("s_nop 1\n\t" RISVEC_SWAP32 " %0, %1\n\t" RISVEC_SWAP32 " %2, %3" : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1));
+}
+template <int O>
+__device__ __forceinline__ void swap_rows(float& a0, float& b0, float& a1, float& b1, float& a2, float& b2, float& a3, float& b3) {
+    static_assert(O == 16 || O == 32, "rows of 16 or 32 lanes");
+    if constexpr (O == 16)
+        asm("s_nop 1\n\t" RISVEC_SWAP16 " %0, %1\n\t" RISVEC_SWAP16 " %2, %3\n\t" RISVEC_SWAP16 " %4, %5\n\t" RISVEC_SWAP16 " %6, %7"
+            : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2), "+v"(a3), "+v"(b3));
+    else
+        asm("s_nop 1\n\t" RISVEC_SWAP32 " %0, %1\n\t" RISVEC_SWAP32 " %2, %3\n\t" RISVEC_SWAP32 " %4, %5\n\t" RISVEC_SWAP32 " %6, %7"
+            : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2), "+v"(a3), "+v"(b3));
+}
+#undef RISVEC_SWAP16
+#undef RISVEC_SWAP32
+
 // transposing butterfly over a G-lane group: K values in, after log2(K) halving steps one
 // value per lane, then plain all-reduce steps down to distance 1.
 template <int K, int O, int N>
 __device__ __forceinline__ void treduce(float (&val)[N], int gl) {
     if constexpr (O >= 1) {
-        if constexpr (K > 1) {
+        if constexpr (K > 1 && (O == 16 || O == 32)) {
+            // gfx950's v_permlane16_swap / v_permlane32_swap exchange the odd rows (of 16 / 32 lanes) of the first operand
+            // with the even rows of the second: on (val[j], val[j + K/2]) the even rows end up with their own val[j] and
+            // the partner's val[j], the odd rows with the partner's val[j + K/2] and their own -- the two operands of the
+            // sum below, which the odd rows add the other way round (a float add commutes: the same bits).  One VALU
+            // instruction per pair where the select form takes two v_cndmask and an LDS-crossbar exchange.
+            //
+            // Inline assembly, not __builtin_amdgcn_permlane16_swap: the compiler this is built with returns the FIRST
+            // result for both elements of the builtin's pair (`r[0] + r[1]` came out as `v_add_f32 v, vdst, vdst`).  The
+            // instruction must not read a register a VALU instruction wrote less than two wait states before, and the
+            // compiler does not look into the string: the pad (s_nop 1) stands inside it, once in front of a stage's swaps
+            // (they touch distinct registers).
+            if constexpr (K == 8) swap_rows<O>(val[0], val[4], val[1], val[5], val[2], val[6], val[3], val[7]);
+            else if constexpr (K == 4) swap_rows<O>(val[0], val[2], val[1], val[3]);
+            else {
+#pragma unroll
+                for (int j = 0; j < K / 2; ++j) swap_rows<O>(val[j], val[j + K / 2]);
+            }
+#pragma unroll
+            for (int j = 0; j < K / 2; ++j) val[j] = val[j] + val[j + K / 2];
+            treduce<K / 2, O / 2, N>(val, gl);
+        } else if constexpr (K > 1) {
             const bool hi = (gl & O) != 0;
 #pragma unroll
             for (int j = 0; j < K / 2; ++j) {
@@ -784,9 +837,10 @@ bool theta_by_index_supported(int V, int M);
 hipError_t launch_step_fused_pipe(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
                                   bool rev, hipStream_t st);
 // the pipeline's GEN member (k_step_gen.hip): h_r rebuilt from s.steer_ang / s.z_r; the plan's shape has M % 16 == 0.
-// rev: serve each wavefront's groups last first (the pipeline's walk)
+// rev: serve each wavefront's groups last first (the pipeline's walk); heads: the chunk heads stand behind the angles at
+// s.steer_ang and are read instead of evaluated (RISVEC_STEP_STEER_HEADS_CURRENT)
 hipError_t launch_step_fused_gen(const RisVecState& s, const RisVecParams& p, const StepArgs& a, const StepPlan& pl,
-                                 bool rev, hipStream_t st);
+                                 bool rev, bool heads, hipStream_t st);
 // 0 / 1: the walk the calling thread's last software-pipeline launch took (risvec_last_pipe_walk)
 int last_pipe_walk();
 void note_pipe_walk(int walk);

@@ -94,7 +94,9 @@ class VecEnviron(ParamAttrs):
         # without steer_ang was loaded): while it has not moved, h_r is exactly what the kernel wrote from steer_ang / z_r
         # and the fused step is told so (RISVEC_STEP_H_R_STEER_CURRENT)
         self._h_r_steer_version = -1
-        self._ssum_sweeps = 0          # >0: s_sum = sum theta.c of the CURRENT theta, left by that many
+        # tensors["steer_ang"]._version when the chunk heads behind the angles were last written from them (-1: never)
+        self._steer_head_version = -1
+        self._ssum_sweeps = 0       # >0: s_sum = sum theta.c of the CURRENT theta, left by that many
                                        # consecutive sweeps (0 = unknown; refreshed every 64 sweeps)
         self._idx_valid = False        # theta_idx = candidate index of every CURRENT theta element (left by a sweep)
         # lazy_theta: between BCD sweeps keep theta BY INDEX (one byte per element, theta_idx): `step(bcd=True)` then
@@ -158,7 +160,16 @@ class VecEnviron(ParamAttrs):
         t["z_r"] = z(E, V, 2, dt=torch.float64)        # steering base exp(-j pi angle) per vehicle: h_r[e,v,m] = z^m
         # candidate index of every theta element as the last BCD sweep left it: [E, 32 ceil(M/32)] bytes
         t["theta_idx"] = z(E, (M + 31) // 32 * 32, dt=torch.uint8)
-        t["steer_ang"] = z(E, V, dt=torch.float64)     # the float64 angle every h_r row is a function of (ang_r: its float32)
+        # the float64 angle every h_r row is a function of (ang_r: its float32) and, where the rows are whole 16-element
+        # chunks, directly behind it the float64 head exp(-j pi ang 16 c) of every chunk (risvec_steer_heads): one
+        # allocation, because that is how RISVEC_STEP_STEER_HEADS_CURRENT finds the heads
+        if M % 16 == 0:
+            steer = z(E * V * (1 + 2 * (M // 16)), dt=torch.float64)
+            t["steer_ang"] = steer[:E * V].view(E, V)
+            t["steer_head"] = steer[E * V:].view(E, V, M // 16, 2)
+            assert t["steer_head"].data_ptr() % 16 == 0 or V not in (4, 8, 16)
+        else:
+            t["steer_ang"] = z(E, V, dt=torch.float64)
         s = N.RisVecState()
         s.abi_version = N.ABI_VERSION
         s.struct_bytes = C.sizeof(N.RisVecState)
@@ -174,6 +185,10 @@ class VecEnviron(ParamAttrs):
 
     # how the h_r allocation was chosen (None: not needed / switched off); bench.py reports it
     placement: Optional[dict] = None
+
+    # send RISVEC_STEP_STEER_HEADS_CURRENT with RISVEC_STEP_H_R_STEER_CURRENT while the heads are current (same outputs
+    # either way; False keeps the GEN members on sincospi: tests and A/Bs)
+    steer_heads: bool = True
 
     def _place_stream(self) -> None:
         """h_r is THE stream of the fused step.  Once it no longer fits the Infinity Cache, the rate at which the kernels
@@ -321,7 +336,16 @@ class VecEnviron(ParamAttrs):
         self._colsum_valid = True
         self._steer_valid = True       # h_r[e,v,m] = z_r[e,v]^m from here on
         self._h_r_steer_version = self._t["h_r"]._version   # kernels write through raw pointers: no bump
+        self._write_steer_heads()
         self._ssum_sweeps = 0          # c changed: the cached sum is stale (the candidate indices are not)
+
+    def _write_steer_heads(self) -> None:
+        """The chunk heads of the steer_ang now in the state (risvec_steer_heads), where the shape keeps them."""
+        head = self._t.get("steer_head")
+        if head is None or head.data_ptr() % 16:
+            return
+        N.check(N.load().risvec_steer_heads(C.byref(self._cstate), head.data_ptr(), N.stream(self.device)))
+        self._steer_head_version = self._t["steer_ang"]._version    # kernels write through raw pointers: no bump
 
     def rebuild_colsum(self) -> None:
         """Recompute the BCD cache c_col[e,m] = (sum_v h_r[e,v,m]) b[m] (float64).  compute_parms()
@@ -398,6 +422,10 @@ class VecEnviron(ParamAttrs):
         and only at shapes whose rows are whole 16-element chunks (the others have no rebuilding kernel, and a launch that
         is a few microseconds long should not pay for the question)."""
         if self._steer_valid and self._t["h_r"]._version == self._h_r_steer_version:
+            # ... and RISVEC_STEP_STEER_HEADS_CURRENT with it while the heads behind the angles are the angles' own:
+            # written since (compute_parms / load_state_dict), and no torch write has moved the angles' version since
+            if self.steer_heads and self._t["steer_ang"]._version == self._steer_head_version:
+                return N.STEP_H_R_STEER_CURRENT | N.STEP_STEER_HEADS_CURRENT
             return N.STEP_H_R_STEER_CURRENT
         return 0
 
@@ -994,6 +1022,10 @@ class VecEnviron(ParamAttrs):
         # compute_parms() (the copy above moved h_r's version either way)
         rebuildable = self._steer_valid and bool(c.get("h_r_steer", False)) and "steer_ang" in sd
         self._h_r_steer_version = t["h_r"]._version if rebuildable else -1
+        # the heads are no part of a checkpoint: a function of the angles, recomputed from the ones just loaded
+        self._steer_head_version = -1
+        if "steer_ang" in sd:
+            self._write_steer_heads()
         self._obs_stale = bool(c.get("obs_stale", self._steps == 0))
         self._sarl_obs_mark = None
 
