@@ -6,6 +6,11 @@
 // operation: lane gl accumulates its NIT pairs with cfma from zero in `it` order, treduce<K, G/2>, the same s_img slot,
 // the same core.  Only where the float4 comes from changes, so every output is the reading form's bit for bit.
 //
+// Two layouts share the file.  Where every wavefront owns ONE group and the shape keeps four wavefronts per SIMD
+// (GenRowLane: 8 x 64 -- the headline --, 4 x 16, 16 x 64) a lane owns a whole ROW: gen_row_lane_form() below, whose
+// comment has the layout and the order of its sums.  Everywhere else (more groups than wavefronts, 16 x 256) lanes own
+// chunks and hand them over through LDS: gen_stage_form(), described here.
+//
 // The rotation chain inside a chunk is sequential (each step rounds), so a lane cannot start in the middle of one:
 // lanes own WHOLE chunks.  One pass of the wavefront makes 64 chunks = 1024 consecutive elements of the group's rows
 // (kWave / NCH rows, NCH = M / 16 chunks per row), parks each chunk's eight float4 in a per-wavefront LDS stage (chunk
@@ -26,7 +31,9 @@
 //     the kernel-argument segment AFTER the last pass (late_args below): the kernel takes its arguments as one struct so
 //     that a field's place in the segment is its offsetof.
 //   * ONE: the member for launches in which every wavefront owns one group (the headline: 4 096 groups on 4 096
-//     wavefronts).  No group loop, no second set of step() inputs, no request for "the next group".
+//     wavefronts).  No group loop, no second set of step() inputs, no request for "the next group" -- and, in the
+//     row-per-lane form, no stage, no s_img, no cross-lane reduce: what the stage layout costs beside the arithmetic
+//     (16 + 16 ds_*_b128, the swaps, selects, DPP adds and their wait states per group) is not issued at all.
 //   * HD (RISVEC_STEP_STEER_HEADS_CURRENT): the sincospi at the head of a chunk is a function of the angle alone, so
 //     risvec_steer_heads() evaluates it once per geometry and the feed reads the float64 pair (steer_head() /
 //     steer_chunk_from_head(), risvec_dev.hpp): 48 vector instructions per pass less, 16 bytes per lane and pass more.
@@ -112,8 +119,7 @@ __device__ __forceinline__ const GenArgs<Core>& late_args() {
 // contiguous) instead of evaluated by sincospi 64 lanes x NCH passes x every launch; the rotations start from the same
 // float64 pair either way.  steer_ang is not read then.
 template <int V, int M, class Core, bool TK, bool ONE, bool HD>
-__global__ void __launch_bounds__(kBlock)
-k_step_fused_gen(GenArgs<Core> KA) {
+__device__ __forceinline__ void gen_stage_form(const GenArgs<Core>& KA) {
     using In = typename Core::In;
     using S = GenShape<V, M>;
     constexpr int VP = S::VP, EPW = S::EPW, NP = S::NP, G = S::G, NIT = S::NIT, VPP = S::VPP;
@@ -341,6 +347,194 @@ k_step_fused_gen(GenArgs<Core> KA) {
             if (grp < grp_first || grp >= grp_end) break;
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// The row-per-lane form of the one-group member.  A group is 64 rows and step() runs with lane = (env lane / V, vehicle
+// lane % V), which IS the row index: the lane that rebuilds a row also consumes it.  It runs the row's NCH chunk chains
+// (the same float64 work per wavefront as a pass per chunk), multiplies each float4 by the env's w = theta * b as it
+// leaves the chain, and adds the partials in registers in the order the reading form's treduce<K, G/2> adds them across
+// lanes -- so the reduced img is already in the lane that runs step(), with no stage, no s_img, no cross-lane exchange.
+//
+// The tree.  In the reading form lane gl of a row chains its NIT float4 from zero (cfma, `it` order) into the partial
+// p[gl]; treduce then adds pairwise at distance O = G/2, ..., 1 with xchg<O>'s partners: gl ^ O, except the DPP mirrors at
+// O = 8 (g <-> 15 - g within 16) and O = 4 (g <-> 7 - g within 8).  Which lane keeps and which sends does not matter (a
+// float add commutes), so with s_G = p the sums are
+//     s_O[g] = s_2O[g] + s_2O[O == 8 || O == 4 ? 2 O - 1 - g : g + O],   g < O,
+// and s_1[0] is what the writer lane held.  row_tree_block() evaluates s_O in blocks of 8 consecutive g -- a leaf block is
+// one chunk (and the chunk G/8 behind it where NIT = 2) -- depth first, so that partners at the largest distance fold
+// first and few blocks are live.  Ragged rows (NP < G): the reading form's lanes past the end of a row form their
+// partial against b = 0, an exact +0 (fma(h, +-0, +0) is +0 for every finite h); those blocks are +0 here too and are
+// added, not skipped.
+// ---------------------------------------------------------------------------
+template <int G, int O, int J, class Leaf>
+__device__ __forceinline__ void row_tree_block(float2 (&out)[8], Leaf&& leaf) {
+    if constexpr (O == G) {
+        leaf(std::integral_constant<int, J>{}, out);
+    } else if constexpr (O >= 16) {
+        float2 far[8];
+        row_tree_block<G, 2 * O, J>(out, leaf);
+        row_tree_block<G, 2 * O, J + O / 8>(far, leaf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) out[k] = make_float2(out[k].x + far[k].x, out[k].y + far[k].y);
+    } else {
+        static_assert(O == 8 && J == 0, "below 16 the values of a row sit in one block");
+        float2 far[8];
+        row_tree_block<G, 16, 0>(out, leaf);
+        row_tree_block<G, 16, 1>(far, leaf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) out[k] = make_float2(out[k].x + far[7 - k].x, out[k].y + far[7 - k].y);
+    }
+}
+
+template <int G, class Leaf>
+__device__ __forceinline__ float2 row_tree(Leaf&& leaf) {
+    static_assert(G == 16 || G == 32 || G == 64, "treduce<K, G/2> starts at distance 8, 16 or 32");
+    float2 s[8];
+    row_tree_block<G, 8, 0>(s, leaf);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) s[g] = make_float2(s[g].x + s[7 - g].x, s[g].y + s[7 - g].y);       // O = 4: the half mirror
+#pragma unroll
+    for (int g = 0; g < 2; ++g) s[g] = make_float2(s[g].x + s[g + 2].x, s[g].y + s[g + 2].y);       // O = 2
+    return make_float2(s[0].x + s[1].x, s[0].y + s[1].y);                                           // O = 1
+}
+
+// the theta indices of Q float4 (2 Q bytes, Q even), as one aligned load: theta_idx_stride() is a multiple of 32
+template <int Q>
+struct alignas(2 * Q) GenIdx {
+    unsigned w[Q / 2];
+};
+
+template <int V, int M, class Core, bool TK, bool HD>
+__device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
+    using In = typename Core::In;
+    using S = GenShape<V, M>;
+    constexpr int VP = S::VP, EPW = S::EPW, NP = S::NP, G = S::G, NIT = S::NIT, NCH = S::NCH;
+    static_assert(std::is_same<typename Core::Args, StepArgs>::value, "the GEN members step on StepArgs");
+    static_assert(VP == V && EPW * V == kWave, "lane = row of the group");
+    static_assert(NP % V == 0 && (NP / V) % 2 == 0, "an env's w is made by its V lanes, an even share each");
+    static_assert(NP % G == 0 || NIT == 1, "ragged rows: whole blocks past the end of the row");
+    constexpr int Q = NP / V;                                  // float4 of w per lane
+    constexpr int WS = NP + 1;                                 // env stride of s_w: the EPW addresses of a read on their own banks
+    __shared__ float4 s_w[kBlock / kWave][EPW * WS];
+    __shared__ float2 s_ph[TK ? kBlock / kWave : 1][16];
+
+    const Dims& d = KA.d;
+    const typename Core::Args& A = KA.A;
+    const double* __restrict__ steer = KA.steer;
+    const int n_groups_total = KA.n_groups_total;
+
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / kWave) + wave);
+    if constexpr (TK) {
+        RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
+                                "s"(n_groups_total), "s"(d.E));
+    } else {
+        RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E));
+    }
+    const int grp = wid;
+    if (grp >= n_groups_total) return;                         // whole wave
+
+    // everything the lane reads, in one batch (tail: the last row / env again, masked by `active`)
+    const int v_mine = lane % VP, i_env = lane / VP;
+    const int e_mine = grp * EPW + i_env;
+    const bool active = e_mine < d.E;
+    const int e_ld = active ? e_mine : d.E - 1;
+    const int row = e_ld * V + v_mine;
+    double2 head[HD ? NCH : 1];
+    if constexpr (HD) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) head[c] = reinterpret_cast<const double2*>(steer)[(long long)row * NCH + c];
+    } else {
+        head[0].x = steer[row];
+    }
+    const double2 z = reinterpret_cast<const double2*>(KA.z_r)[row];
+    GenIdx<Q> kq;
+    float4 tq[TK ? 1 : Q], bq[Q];
+    if constexpr (TK) {
+        kq = *reinterpret_cast<const GenIdx<Q>*>(A.theta_k + (long long)e_ld * A.theta_k_stride + 2 * Q * v_mine);
+    } else {
+        const float4* __restrict__ tb = reinterpret_cast<const float4*>(A.theta) + (long long)e_ld * NP + Q * v_mine;
+#pragma unroll
+        for (int i = 0; i < Q; ++i) tq[i] = tb[i];
+    }
+#pragma unroll
+    for (int i = 0; i < Q; ++i) bq[i] = reinterpret_cast<const float4*>(A.b)[Q * v_mine + i];
+    if constexpr (TK) {
+        theta_table_fill(s_ph[wave], lane);
+        __builtin_amdgcn_wave_barrier();
+    }
+    const In in = Core::load(d, A, e_mine, v_mine, active);
+    Core::hold(in);
+
+    // the env's w0 / w1 of float4 p, cmul(theta, b) as the reading lane p forms them: Q per lane, shared through s_w
+    float4* __restrict__ wrow = s_w[wave] + i_env * WS;
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+        float2 t0, t1;
+        if constexpr (TK) {
+            const unsigned k2 = kq.w[i / 2] >> (16 * (i & 1));
+            t0 = s_ph[wave][k2 & 15u];
+            t1 = s_ph[wave][(k2 >> 8) & 15u];
+        } else {
+            t0 = make_float2(tq[i].x, tq[i].y);
+            t1 = make_float2(tq[i].z, tq[i].w);
+        }
+        const float2 w0 = cmul(t0, make_float2(bq[i].x, bq[i].y));
+        const float2 w1 = cmul(t1, make_float2(bq[i].z, bq[i].w));
+        wrow[Q * v_mine + i] = make_float4(w0.x, w0.y, w1.x, w1.y);
+    }
+    __builtin_amdgcn_wave_barrier();                           // s_w's writes -> its reads (same wave: in order)
+
+    // block J of the partials: float4 gl = 8 J + k of the row, i.e. chunk J (then chunk J + G/8), against w of the same index
+    auto leaf = [&](auto jc, float2 (&acc)[8]) {
+        constexpr int J = decltype(jc)::value;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = make_float2(0.f, 0.f);
+        if constexpr (8 * J < NP) {
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                constexpr int GC = G / 8;
+                const int c = J + it * GC;
+                float4 q[kGeoChunk / 2];
+                if constexpr (HD) steer_chunk_from_head(head[c].x, head[c].y, z.x, z.y, q);
+                else steer_chunk(head[0].x, z.x, z.y, c * kGeoChunk, q);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float4 w = wrow[8 * c + k];
+                    acc[k] = cfma(make_float2(q[k].x, q[k].y), make_float2(w.x, w.y), acc[k]);
+                    acc[k] = cfma(make_float2(q[k].z, q[k].w), make_float2(w.z, w.w), acc[k]);
+                }
+                // One chain and its 8 float4 of w at a time: left to itself the compiler asks for all of the row's w first
+                // (32 float4 in registers at M = 64) and the fourth wavefront per SIMD is lost.  The partials pass through
+                // an empty asm that clobbers memory: the next chunk's LDS reads cannot rise above it, nor this chunk's
+                // arithmetic sink below it.
+                asm volatile("" : "+v"(acc[0].x), "+v"(acc[0].y), "+v"(acc[1].x), "+v"(acc[1].y), "+v"(acc[2].x), "+v"(acc[2].y),
+                                  "+v"(acc[3].x), "+v"(acc[3].y), "+v"(acc[4].x), "+v"(acc[4].y), "+v"(acc[5].x), "+v"(acc[5].y),
+                                  "+v"(acc[6].x), "+v"(acc[6].y), "+v"(acc[7].x), "+v"(acc[7].y)
+                             :
+                             : "memory");
+            }
+        }
+    };
+    const float2 img = row_tree<G>(leaf);
+
+    const GenArgs<Core>& L = late_args<Core>();
+    Core::template run<VP>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
+}
+
+// The shapes whose one-group member is the row-per-lane form: those that keep four wavefronts per SIMD (128 VGPRs) with it.
+// 16 x 256 does not -- a lane would run 16 chains against 128 float4 of w, 171 ... 204 VGPRs -- and keeps the stage form.
+template <int V, int M>
+struct GenRowLane {
+    static constexpr bool value = M <= 64;
+};
+
+template <int V, int M, class Core, bool TK, bool ONE, bool HD>
+__global__ void __launch_bounds__(kBlock)
+k_step_fused_gen(GenArgs<Core> KA) {
+    if constexpr (ONE && GenRowLane<V, M>::value) gen_row_lane_form<V, M, Core, TK, HD>(KA);
+    else gen_stage_form<V, M, Core, TK, ONE, HD>(KA);
 }
 
 // Wavefronts per CU: no register ring, and 38.5 KiB of LDS per workgroup (the stage), so four workgroups fit a CU.  The
