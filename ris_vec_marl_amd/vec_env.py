@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._currency import Currency
 from .params import CHANNEL_MODELS, EnvParams
 
 # module constants of the reference (Environment.py:29-42)
@@ -48,7 +49,7 @@ class ParamAttrs:
             object.__setattr__(self, name, value)
 
 
-class VecEnviron(ParamAttrs):
+class VecEnviron(ParamAttrs, Currency):
     """Batched environment.  Constructor mirrors Environment.py:57 plus batching args."""
 
     def __init__(self, down_lane, up_lane, left_lane, right_lane, width, height, n_veh, M, control_bit,
@@ -88,29 +89,13 @@ class VecEnviron(ParamAttrs):
         self._obs_stale = True   # obs[E,V,5] does not reflect the state tensors (no step since the last reset)
         self._sarl_obs_mark = None   # (_epoch, _steps) at which the SARL observation tensor was current (bind_sarl_rollout)
         self._t: Dict[str, torch.Tensor] = {}
-        self._colsum_valid = False     # c_col matches h_r (set by compute_parms / rebuild_colsum)
-        self._steer_valid = False      # h_r is the steering vector compute_parms wrote, z_r its base
-        # tensors["h_r"]._version when compute_parms() last wrote it together with steer_ang (-1: never, or a checkpoint
-        # without steer_ang was loaded): while it has not moved, h_r is exactly what the kernel wrote from steer_ang / z_r
-        # and the fused step is told so (RISVEC_STEP_H_R_STEER_CURRENT)
-        self._h_r_steer_version = -1
-        # tensors["steer_ang"]._version when the chunk heads behind the angles were last written from them (-1: never)
-        self._steer_head_version = -1
-        self._ssum_sweeps = 0       # >0: s_sum = sum theta.c of the CURRENT theta, left by that many
-                                       # consecutive sweeps (0 = unknown; refreshed every 64 sweeps)
-        self._idx_valid = False        # theta_idx = candidate index of every CURRENT theta element (left by a sweep)
         # lazy_theta: between BCD sweeps keep theta BY INDEX (one byte per element, theta_idx): `step(bcd=True)` then
         # neither writes nor reads the complex64 tensor (67 MB out + 67 MB in per step at BASELINE configs[4]); it is
         # materialised when somebody asks for it (`tensors`, any other consumer).  Same step outputs bit for bit.
         self.lazy_theta = bool(lazy_theta)
-        self._theta_stale = False      # tensors["theta"] lags behind theta_idx (only ever True with lazy_theta)
-        self._stale_version = -1       # tensors["theta"]._version when it went stale: a later write through torch moves it
-        self._tk_ok = None             # does the fused step have a theta-by-index form at this shape? (asked lazily)
-        # theta_idx holds the candidate index of every element of tensors["theta"] AS IT IS NOW (Random_phase with
-        # control_bit = 3, or a sweep that wrote both): the fused step may then read either, and is told so
-        # (RISVEC_STEP_THETA_IDX_CURRENT).  Its own field, not `_idx_valid`: that one steers which BCD sweep runs.
-        self._idx_current = False
-        self._idx_current_version = -1  # tensors["theta"]._version when it was set: a write through torch moves it
+        # what theta, its indices, h_r and the caches derived from them are known to hold: every "this is current" bit a
+        # launch carries is decided by the Currency base (_currency.py), which owns the fields behind them
+        self._init_currency()
         self._cstate: Optional[N.RisVecState] = None
         self._cparams: Optional[N.RisVecParams] = None
         self._cparams_version = -1
@@ -235,8 +220,6 @@ class VecEnviron(ParamAttrs):
             if min(x[0] for x in cands) < 0.96 * max(x[0] for x in cands):
                 break                                  # both levels seen: the faster one is known
         us, keep = min(cands, key=lambda x: x[0])
-        if self._h_r_steer_version == t["h_r"]._version:
-            self._h_r_steer_version = keep._version    # the record follows the allocation
         t["h_r"] = keep
         self._cstate.h_r = keep.data_ptr()
         self.placement = dict(candidates=len(cands), step_kernel_us=[round(x[0], 1) for x in cands], kept_us=round(us, 1))
@@ -275,19 +258,11 @@ class VecEnviron(ParamAttrs):
         self._sync_theta()
         return self._t
 
-    def _sync_theta(self) -> None:
-        """Materialise tensors["theta"] from the candidate indices if the last sweeps kept theta by index."""
-        if self._theta_stale:
-            N.check(N.load().risvec_theta_from_index(C.byref(self._cstate), N.stream(self.device)))
-            self._theta_stale = False
+    def _theta_from_index(self) -> None:
+        N.check(N.load().risvec_theta_from_index(C.byref(self._cstate), N.stream(self.device)))
 
-    def _by_index(self, fused: bool, steer: bool) -> bool:
-        """Can this fused step read theta as candidate indices?  (lazy_theta, indices current, a shape with that form)"""
-        if not (self.lazy_theta and fused and not steer and self._idx_valid and self.control_bit == 3):
-            return False
-        if self._tk_ok is None:                  # asked once: the answer depends on the shape only
-            self._tk_ok = bool(N.load().risvec_theta_by_index_supported(self.n_veh, self.M))
-        return self._tk_ok
+    def _theta_by_index_supported(self) -> bool:
+        return bool(N.load().risvec_theta_by_index_supported(self.n_veh, self.M))
 
     def __getattr__(self, name):
         t = self.__dict__.get("_t")
@@ -333,11 +308,8 @@ class VecEnviron(ParamAttrs):
         """Environment.py:241-253: pos -> distances_R_i, angles_R_i, phases_R_i (+ path-loss factor)."""
         self._ensure_device()
         N.check(N.load().risvec_geometry(C.byref(self._cstate), C.byref(self._p()), N.stream(self.device)))
-        self._colsum_valid = True
-        self._steer_valid = True       # h_r[e,v,m] = z_r[e,v]^m from here on
-        self._h_r_steer_version = self._t["h_r"]._version   # kernels write through raw pointers: no bump
+        self._geometry_written()
         self._write_steer_heads()
-        self._ssum_sweeps = 0          # c changed: the cached sum is stale (the candidate indices are not)
 
     def _write_steer_heads(self) -> None:
         """The chunk heads of the steer_ang now in the state (risvec_steer_heads), where the shape keeps them."""
@@ -345,7 +317,7 @@ class VecEnviron(ParamAttrs):
         if head is None or head.data_ptr() % 16:
             return
         N.check(N.load().risvec_steer_heads(C.byref(self._cstate), head.data_ptr(), N.stream(self.device)))
-        self._steer_head_version = self._t["steer_ang"]._version    # kernels write through raw pointers: no bump
+        self._heads_written()
 
     def rebuild_colsum(self) -> None:
         """Recompute the BCD cache c_col[e,m] = (sum_v h_r[e,v,m]) b[m] (float64).  compute_parms()
@@ -354,9 +326,7 @@ class VecEnviron(ParamAttrs):
         left as it is: candidate indices the last sweep kept stay valid (the next sweep re-sums theta.c)."""
         self._ensure_device()
         N.check(N.load().risvec_colsum(C.byref(self._cstate), N.stream(self.device)))
-        self._colsum_valid = True
-        self._steer_valid = False
-        self._ssum_sweeps = 0
+        self._colsum_rebuilt()
 
     def colsum_rows(self) -> torch.Tensor:
         """The BCD cache as [E, M] complex128 (a copy; the device layout is lane-major slabs)."""
@@ -368,9 +338,7 @@ class VecEnviron(ParamAttrs):
         re-sums theta.c and re-derives the candidate indices, and the steering form of the fused step
         (`steer=True`) is refused until compute_parms() writes steering vectors again.  theta is handled as by
         invalidate_theta(): if it was not written, what the sweeps left in it is kept."""
-        self._colsum_valid = False
-        self._steer_valid = False      # h_r is no longer known to be the steering vectors z_r^m
-        self._theta_written()
+        self._h_r_write_announced()
 
     def invalidate_theta(self) -> None:
         """Announce a direct write to `tensors["theta"]`: the written tensor becomes theta, and the next BCD sweep
@@ -378,75 +346,7 @@ class VecEnviron(ParamAttrs):
         track on their own).  With lazy_theta, where the last sweeps may have kept theta by index only, a theta
         tensor that torch has not written since (its `_version` has not moved) is first materialised from those
         indices, so an announcement without a theta write loses no sweep."""
-        self._theta_written()
-
-    def _theta_written(self) -> None:
-        """An announced direct write (invalidate_colsum / invalidate_theta) that may or may not have touched theta."""
-        # (read through `_t`: `tensors` would materialise theta before the check)
-        if self._theta_stale and self._t["theta"]._version == self._stale_version:
-            self._sync_theta()         # theta not written: the indices hold the swept theta, keep it
-        self._theta_changed()
-
-    def _mark_theta_stale(self, stale: bool) -> None:
-        """The last sweep kept theta by index (stale) or wrote the complex64 tensor."""
-        self._theta_stale = stale
-        if stale:
-            self._stale_version = self._t["theta"]._version     # kernels write through raw pointers: no bump
-        self._set_idx_current(not stale and self.control_bit == 3)  # a 2^b = 8 sweep that wrote the tensor wrote both
-
-    def _theta_changed(self) -> None:
-        """theta was written by something other than a BCD sweep: its cached sum and candidate indices are stale."""
-        self._ssum_sweeps = 0
-        self._idx_valid = False
-        self._theta_stale = False      # whoever wrote theta made the tensor the truth again
-        self._idx_current = False
-
-    def _set_idx_current(self, current: bool) -> None:
-        """A kernel just wrote theta; `current`: it wrote the matching candidate indices too."""
-        self._idx_current = current
-        if current:
-            self._idx_current_version = self._t["theta"]._version   # kernels write through raw pointers: no bump
-
-    def _idx_current_flag(self) -> int:
-        """RISVEC_STEP_THETA_IDX_CURRENT while the indices are known to match the tensor: set by a kernel that wrote both,
-        and nothing has written the tensor through torch since (an unannounced write moves its `_version`)."""
-        if self._idx_current and self._t["theta"]._version == self._idx_current_version:
-            return N.STEP_THETA_IDX_CURRENT
-        return 0
-
-    def _h_r_steer_flag(self) -> int:
-        """RISVEC_STEP_H_R_STEER_CURRENT while h_r is known to be what compute_parms() wrote from the steer_ang / z_r now
-        in the state: nothing announced a write (rebuild_colsum / invalidate_colsum clear `_steer_valid`) and nothing
-        wrote the tensor or its complex view through torch (that moves `_version`).  Asked on the launch path of the RIS
-        cascade only -- channel_model "free": under a 3GPP model the launchers have already taken the other branch --
-        and only at shapes whose rows are whole 16-element chunks (the others have no rebuilding kernel, and a launch that
-        is a few microseconds long should not pay for the question)."""
-        if self._steer_valid and self._t["h_r"]._version == self._h_r_steer_version:
-            # ... and RISVEC_STEP_STEER_HEADS_CURRENT with it while the heads behind the angles are the angles' own:
-            # written since (compute_parms / load_state_dict), and no torch write has moved the angles' version since
-            if self.steer_heads and self._t["steer_ang"]._version == self._steer_head_version:
-                return N.STEP_H_R_STEER_CURRENT | N.STEP_STEER_HEADS_CURRENT
-            return N.STEP_H_R_STEER_CURRENT
-        return 0
-
-    def _h_r_is_steer(self) -> bool:
-        return self._h_r_steer_flag() != 0
-
-    def _bcd_flags(self, reuse_colsum: Optional[bool], step: bool) -> int:
-        reuse_c = self._colsum_valid if reuse_colsum is None else bool(reuse_colsum)
-        reuse_s = reuse_c and 0 < self._ssum_sweeps < 64
-        reuse_i = self._idx_valid and self.control_bit == 3
-        if step:
-            return ((N.STEP_REUSE_COLSUM if reuse_c else 0) | (N.STEP_REUSE_SSUM if reuse_s else 0)
-                    | (N.STEP_REUSE_IDX if reuse_i else 0))
-        return ((N.BCD_REUSE_COLSUM if reuse_c else 0) | (N.BCD_REUSE_SSUM if reuse_s else 0)
-                | (N.BCD_REUSE_IDX if reuse_i else 0))
-
-    def _bcd_done(self, flags: int, step: bool) -> None:
-        reused_s = bool(flags & (N.STEP_REUSE_SSUM if step else N.BCD_REUSE_SSUM))
-        self._colsum_valid = True
-        self._ssum_sweeps = self._ssum_sweeps + 1 if reused_s else 1
-        self._idx_valid = self.control_bit == 3        # every 2^b = 8 sweep leaves the indices of what it stored
+        self._theta_write_announced()
 
     def optimize_phase_shift(self, return_idx: bool = False, reuse_colsum: Optional[bool] = None):
         """Environment.py:208-220 (one BCD sweep, objective of :222-231).  The column sums the
@@ -454,13 +354,9 @@ class VecEnviron(ParamAttrs):
         compute_parms()/rebuild_colsum()), otherwise rebuilt first.  reuse_colsum overrides."""
         self._ensure_device()
         idx = torch.zeros(self.n_envs, self.M, dtype=torch.int32, device=self.device) if return_idx else None
-        flags = self._bcd_flags(reuse_colsum, step=False)
-        lazy = self.lazy_theta and bool(flags & N.BCD_REUSE_IDX)
-        if lazy:
-            flags |= N.BCD_NO_THETA        # the indices are the state; theta follows on demand
+        flags = self._sweep_flags(reuse_colsum, False)
         N.check(N.load().risvec_bcd(C.byref(self._cstate), C.byref(self._p()), N.ptr(idx), flags, N.stream(self.device)))
-        self._bcd_done(flags, step=False)
-        self._mark_theta_stale(lazy)
+        self._sweep_ran(flags, False)
         return idx
 
     def update_channel_gains(self, u_los=None, z_shadow=None, small=None) -> None:
@@ -490,7 +386,7 @@ class VecEnviron(ParamAttrs):
         self._ensure_device()
         a = self._arg(action_phase, torch.float32, (self.n_envs, self.M), "action_phase")
         N.check(N.load().risvec_set_phase(C.byref(self._cstate), N.ptr(a), N.stream(self.device)))
-        self._theta_changed()
+        self._theta_set(False)
 
     def Random_phase(self, idx=None) -> None:
         """Environment.py:203-206; idx [E,M] int32 indices into possible_angles (optional)."""
@@ -499,8 +395,7 @@ class VecEnviron(ParamAttrs):
         self._chan += 1
         N.check(N.load().risvec_random_phase(C.byref(self._cstate), N.ptr(i), self.seed, self._chan,
                                              N.stream(self.device)))
-        self._theta_changed()
-        self._set_idx_current(self.control_bit == 3)   # with 2^b = 8 the kernel writes each element's index as well
+        self._theta_set(True)      # with 2^b = 8 the kernel writes each element's index as well
 
     def data_rate(self, p_off, partner, n_groups) -> torch.Tensor:
         """Environment.py:331-372 on the cached gains: p_off [E,V] offload power in W -> rate [E,V]."""
@@ -553,15 +448,6 @@ class VecEnviron(ParamAttrs):
             raise ValueError("fading must be (u_los, z_shadow, small), all three given")
         ts = tuple(conv(x, torch.float32, shape, n) for x, n in zip(fading, ("u_los", "z_shadow", "small")))
         return ts, N.RisVecFading(*(N.ptr(x) for x in ts))
-
-    def _theta_mode(self, flags: int, fused: bool, bcd: bool, steer: bool) -> int:
-        """Decide how a step gets at theta: by index (flag added) where lazy_theta allows, else make sure the complex64
-        tensor is current for the kernels that read it."""
-        if self._by_index(fused, steer) and (not bcd or bool(flags & N.STEP_REUSE_IDX)):
-            return flags | N.STEP_THETA_BY_INDEX
-        if fused:
-            self._sync_theta()
-        return flags
 
     # Every step call has ONE implementation, `_bind_*(conv, ...)`: validate, marshal once, return the launcher.  `conv`
     # is the whole difference between the public twins: `bind_*` passes `_bound` (inputs used in place or refused), the
@@ -623,8 +509,9 @@ class VecEnviron(ParamAttrs):
         cs, seed, stream = C.byref(self._cstate), C.c_uint64(self.seed), N.stream(self.device)
         pa, pp, pn, par = N.ptr(a), N.ptr(pt), N.ptr(ng), N.ptr(ar)
         pfd = C.byref(fd) if fd is not None else None
-        either = fused and not bcd and not steer       # a launch that may be told "theta_idx matches theta"
-        rows = either and self.M % 16 == 0             # ... and "h_r is what compute_parms() wrote"
+        by_index = not steer                           # a launch that may read theta as candidate indices
+        current = not bcd and not steer                # ... that may be told "theta_idx matches theta", "h_r is what
+                                                       # compute_parms() wrote"
 
         def launch() -> None:
             model = self._model(fused, steer, fd) if fused else None
@@ -637,19 +524,14 @@ class VecEnviron(ParamAttrs):
                 if rc:
                     N.check(rc)
             else:
-                flags = base_flags | (self._bcd_flags(None, step=True) if bcd else 0)
-                if self.lazy_theta or self._theta_stale:       # otherwise theta is the tensor, and current
-                    flags = self._theta_mode(flags, fused, bcd, steer)
-                elif either:
-                    flags |= self._idx_current_flag()
-                    if rows:
-                        flags |= self._h_r_steer_flag()
+                flags = base_flags | self._sweep_flags(None, True) if bcd else base_flags
+                if fused:
+                    flags |= self._fused_launch(by_index, current)
                 rc = fn(cs, C.byref(self._p()), pa, pp, pn, par, seed, self._steps, flags, stream)
                 if rc:
                     N.check(rc)
                 if bcd:
-                    self._bcd_done(flags, step=True)
-                    self._mark_theta_stale(bool(flags & N.STEP_THETA_BY_INDEX))
+                    self._sweep_ran(flags, True)
             self._steps += 1
             self._obs_stale = not obs
 
@@ -738,7 +620,7 @@ class VecEnviron(ParamAttrs):
                 self._chan += T
             else:
                 if fused:
-                    self._sync_theta()
+                    self._fused_launch(False, False)     # reads the complex64 theta, takes no bits
                 rc = fn(cs, C.byref(self._p()), T, pa, pp, pn, par, seed, self._steps, flags, ptj, stream)
                 if rc:
                     N.check(rc)
@@ -783,7 +665,7 @@ class VecEnviron(ParamAttrs):
             if rc:
                 N.check(rc)
             if ph is not None:
-                self._theta_changed()
+                self._theta_set(False)
             self._steps += 1
             self._obs_stale = False        # sarl_observe assembles its own observation from the state tensors
 
@@ -859,7 +741,7 @@ class VecEnviron(ParamAttrs):
             if replay is not None:
                 replay.mem_cntr += E
             self._steps += 1
-            self._theta_changed()
+            self._theta_set(False)
             self._obs_stale = False
             self._sarl_obs_mark = (self._epoch, self._steps)
 
@@ -902,7 +784,6 @@ class VecEnviron(ParamAttrs):
         fn3 = N.load().risvec_step_fused_3gpp
         pa, pp, pn, par, pmask = N.ptr(a), N.ptr(pt), N.ptr(ng), N.ptr(ar), N.ptr(mk)
         fz = 1 if fused else 0
-        rows = fused and self.M % 16 == 0
         pfd = C.byref(fd) if fd is not None else None
 
         def launch(done: bool = False, use_mask: bool = True) -> None:
@@ -916,13 +797,7 @@ class VecEnviron(ParamAttrs):
                 rc = fn3(cs, C.byref(self._p()), model, pa, pp, pn, par, pfd, seed, self._steps, self._chan, flags,
                          C.byref(ring), stream)
             else:
-                fl = flags
-                if fused:
-                    self._sync_theta()
-                    if not self.lazy_theta:
-                        fl |= self._idx_current_flag()
-                        if rows:
-                            fl |= self._h_r_steer_flag()
+                fl = flags | self._fused_launch(False, True) if fused else flags
                 rc = fn(cs, C.byref(self._p()), C.byref(ring), pa, pp, pn, par, seed, self._steps, fl, fz, stream)
             if rc:
                 N.check(rc)
@@ -996,8 +871,8 @@ class VecEnviron(ParamAttrs):
         t = self.tensors
         sd: Dict[str, object] = {k: t[k].detach().cpu().clone() for k in self._STATE_KEYS}
         sd["counters"] = dict(epoch=self._epoch, moves=self._moves, steps=self._steps, chan=self._chan,
-                              seed=self.seed, env_offset=self.env_offset, steer_valid=self._steer_valid,
-                              h_r_steer=self._h_r_is_steer(), obs_stale=self._obs_stale)
+                              seed=self.seed, env_offset=self.env_offset, obs_stale=self._obs_stale,
+                              **self._checkpoint_record())
         return sd
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
@@ -1014,16 +889,8 @@ class VecEnviron(ParamAttrs):
         for k in self._STATE_KEYS:
             if k in sd:                # power_w joined the checkpoint in round 2, steer_ang with the rebuilt rows
                 t[k].copy_(sd[k])
-        self._colsum_valid = False
-        self._theta_changed()
         self._epoch, self._moves, self._steps, self._chan = c["epoch"], c["moves"], c["steps"], c["chan"]
-        self._steer_valid = bool(c.get("steer_valid", False))      # z_r travels with h_r
-        # ... and so does steer_ang, from the checkpoints that have it: without it the rows cannot be rebuilt until the next
-        # compute_parms() (the copy above moved h_r's version either way)
-        rebuildable = self._steer_valid and bool(c.get("h_r_steer", False)) and "steer_ang" in sd
-        self._h_r_steer_version = t["h_r"]._version if rebuildable else -1
-        # the heads are no part of a checkpoint: a function of the angles, recomputed from the ones just loaded
-        self._steer_head_version = -1
+        self._checkpoint_loaded(bool(c.get("steer_valid", False)), bool(c.get("h_r_steer", False)), "steer_ang" in sd)
         if "steer_ang" in sd:
             self._write_steer_heads()
         self._obs_stale = bool(c.get("obs_stale", self._steps == 0))
