@@ -977,6 +977,27 @@ size_t risvec_marl_critic_pack_workspace(int32_t state_dims, int32_t action_dims
 int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
                             const RisVecMarlCriticPackNet *nets, void *workspace, size_t workspace_bytes,
                             risvec_stream_t stream);
+/* risvec_marl_critic for inputs that do not fit in LDS beside the activations: the same computation, arguments, weight
+ * stream (the layout above at this shape's KS), outputs, checks and error codes, in ONE launch, with fc1 walking the input
+ * in chunks of 8 k-steps (128 inputs) while a wavefront keeps the accumulators of all its fc1 groups in registers; every
+ * net stages the input again, chunk by chunk.  Built for state_dims + action_dims <= 512 (each >= 1) and the fc rule of
+ * risvec_marl_critic (risvec_marl_critic_wide_supported, host only) -- 16 vehicles are (80, 288) -- which deliberately
+ * overlaps risvec_marl_critic_supported: within a group the k-steps are added in the same order into one accumulator, so
+ * on a shape both cover the two entries give the same bits.  risvec_marl_critic_wide_stream_bytes is ONE net's stream
+ * size under this rule (0: not built); risvec_marl_critic_wide_pack_workspace / risvec_marl_critic_wide_pack are
+ * risvec_marl_critic_pack_workspace / risvec_marl_critic_pack -- the same two kernels, the same bits -- behind this
+ * rule.  Nothing about risvec_marl_critic or its rule changes. */
+int risvec_marl_critic_wide_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3);
+int64_t risvec_marl_critic_wide_stream_bytes(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3);
+int risvec_marl_critic_wide(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                            int32_t n_nets, const RisVecMarlCriticNet *nets, const float *state, const float *action,
+                            const float *reward, const uint8_t *done, float gamma, const float *coef, const float *logp_power,
+                            const float *logp_intent, float *q1, float *q2, float *y, risvec_stream_t stream);
+size_t risvec_marl_critic_wide_pack_workspace(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                                              int32_t n_nets);
+int risvec_marl_critic_wide_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
+                                 const RisVecMarlCriticPackNet *nets, void *workspace, size_t workspace_bytes,
+                                 risvec_stream_t stream);
 /* Every agent's local twin target critics and local TD target of the multi-agent (SAC) learner (Agent.local_learn,
  * Simulation-MARL-BCD/sac_agent.py:263-284, called once per agent by global_sac_critic.py:373-392) in ONE launch for n_rows
  * rows and n_agents agents; grid (ceil(n_rows / 32), n_agents).  Agent j has n_nets in {1, 2} CriticNetworks of one shape

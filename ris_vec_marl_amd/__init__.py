@@ -16,7 +16,8 @@ from .policy import BatchedPolicy
 from .actor import BatchedActor, pack_actor_weights_device
 from .critic import (BatchedCritic, ddpg_soft_update, ddpg_td_target, pack_critic_weights, pack_critic_weights_device,
                      unpack_critic_weights)
-from .marl_critic import BatchedTwinCritic, pack_marl_critic_weights, pack_marl_critic_weights_device
+from .marl_critic import (BatchedTwinCritic, pack_marl_critic_weights, pack_marl_critic_weights_device,
+                          pack_marl_critic_weights_wide_device)
 from .local_critics import BatchedLocalCritics
 from .optim import BatchedAdam
 from .metrics import EpisodeMeter, ScalarSink
@@ -27,4 +28,5 @@ __all__ = ["EnvParams", "apply_yaml_config", "load_yaml", "reference_lanes", "po
            "sarl_observe", "OUNoise", "SarlReplayBuffer", "NomaConfig", "NomaGrouper", "anneal_topk", "VecReplayBuffer",
            "marshal_actions", "BatchedPolicy", "BatchedActor", "pack_actor_weights_device", "BatchedCritic",
            "ddpg_td_target", "ddpg_soft_update", "pack_critic_weights", "pack_critic_weights_device", "unpack_critic_weights", "BatchedTwinCritic",
-           "pack_marl_critic_weights", "pack_marl_critic_weights_device", "BatchedLocalCritics", "BatchedAdam", "EpisodeMeter", "ScalarSink", "dist"]
+           "pack_marl_critic_weights", "pack_marl_critic_weights_device", "pack_marl_critic_weights_wide_device",
+           "BatchedLocalCritics", "BatchedAdam", "EpisodeMeter", "ScalarSink", "dist"]

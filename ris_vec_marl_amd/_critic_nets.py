@@ -117,10 +117,14 @@ class CriticNets:
     AUTO_MIN_ROWS = 1
     _SD = _Net._SD
 
-    def _init_modes(self, gemm, fused_ok: bool, rule: str) -> None:
-        self.gemm = choose_mode("gemm", gemm, "fused" if fused_ok else "library", self.GEMM_MODES, fused_ok, self._shape(), rule)
+    def _init_modes(self, gemm, fused_ok: bool, rule: str, wide_ok: bool = False) -> None:
+        """wide_ok: the chunked kernel (`BatchedTwinCritic`'s gemm="wide") is built for the shape.  It is opt-in: gemm=None
+        chooses between "fused" and "library" as before."""
+        self.gemm = choose_mode("gemm", gemm, "fused" if fused_ok else "library", self.GEMM_MODES, fused_ok, self._shape(), rule,
+                                wide_ok)
         self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
         self._fused_ok = fused_ok
+        self._wide = self.gemm == "wide"                      # built as gemm="wide": the streams are packed under the wide rule
         self._pack = "host"                                   # see `pack`
         self._pack_workspace = None                           # pack="device": one workspace for every group, at first use
         self.packs = 0                                        # how often a net's weight stream was rebuilt
@@ -131,13 +135,13 @@ class CriticNets:
         `pack_marl_critic_weights` once per stale net, library kernels into new tensors.  "device":
         `pack_marl_critic_weights_device`, two launches for the stale nets of a group together (the twin critic's nets;
         one agent's local nets) into buffers allocated once -- for target critics that are blended every learning step
-        (see `soft_update_from`); only where the fused kernel covers the shape.  Setting it marks the streams stale; a
+        (see `soft_update_from`); only where the fused kernel covers the shape, or on a gemm="wide" object.  Setting it marks the streams stale; a
         refused value changes nothing."""
         return self._pack
 
     @pack.setter
     def pack(self, mode) -> None:
-        if choose_mode("pack", mode, None, self.PACK_MODES, self._fused_ok, self._shape(), PACK_RULE) != self._pack:
+        if choose_mode("pack", mode, None, self.PACK_MODES, self._fused_ok or self._wide, self._shape(), PACK_RULE) != self._pack:
             self._pack = mode
             self.mark_stale()
 
@@ -148,7 +152,7 @@ class CriticNets:
             net.mark_stale()
 
     def _fused(self, n: int) -> bool:
-        return self.gemm == "fused" and n >= self.fused_min_rows
+        return self.gemm in ("fused", "wide") and n >= self.fused_min_rows
 
     def _rebuild_stale(self, nets) -> None:
         """Rebuild the stale weight streams among `nets`, one group: a net's is stale when one of its packed weight tensors
@@ -165,17 +169,19 @@ class CriticNets:
         if self._pack == "device":
             dev = self.device
             if self._pack_workspace is None:
-                need = int(N.load().risvec_marl_critic_pack_workspace(*self._dims, self.n_nets))
+                lib = N.load()
+                workspace = lib.risvec_marl_critic_wide_pack_workspace if self._wide else lib.risvec_marl_critic_pack_workspace
+                need = int(workspace(*self._dims, self.n_nets))
                 self._pack_workspace = torch.zeros(need, dtype=torch.uint8, device=dev)
             rows = MC.marl_critic_geom(*self._dims).rows
             for net, _, _ in stale:
                 if net._pack_buffers is None:
                     net._pack_buffers = stream_pair((rows, 64, 8), 3, dev, torch.zeros)
-            MC.pack_marl_critic_weights_device([ws for _, _, ws in stale], out=[net._pack_buffers for net, _, _ in stale],
-                                               workspace=self._pack_workspace)
+            pack = MC.pack_marl_critic_weights_wide_device if self._wide else MC.pack_marl_critic_weights_device
+            pack([ws for _, _, ws in stale], out=[net._pack_buffers for net, _, _ in stale], workspace=self._pack_workspace)
             for net, key, _ in stale:
                 net._packed = (key, net._pack_buffers)
         else:
             for net, key, ws in stale:
-                net._packed = (key, MC.pack_marl_critic_weights(*ws))
+                net._packed = (key, MC.pack_marl_critic_weights(*ws, wide=self._wide))
         self.packs += len(stale)

@@ -275,6 +275,11 @@ _PROTOS = {
     "risvec_marl_critic": (C.c_int, [C.c_int32] * 7 + [_FP] * 5 + [C.c_float] + [_FP] * 7),
     "risvec_marl_critic_pack_workspace": (C.c_size_t, [C.c_int32] * 6),
     "risvec_marl_critic_pack": (C.c_int, [C.c_int32] * 6 + [_FP, _FP, C.c_size_t, _FP]),
+    "risvec_marl_critic_wide_supported": (C.c_int, [C.c_int32] * 5),
+    "risvec_marl_critic_wide_stream_bytes": (C.c_int64, [C.c_int32] * 5),
+    "risvec_marl_critic_wide": (C.c_int, [C.c_int32] * 7 + [_FP] * 5 + [C.c_float] + [_FP] * 7),
+    "risvec_marl_critic_wide_pack_workspace": (C.c_size_t, [C.c_int32] * 6),
+    "risvec_marl_critic_wide_pack": (C.c_int, [C.c_int32] * 6 + [_FP, _FP, C.c_size_t, _FP]),
     "risvec_local_critics_supported": (C.c_int, [C.c_int32] * 6),
     "risvec_local_critics": (C.c_int, [C.c_int32] * 8 + [_FP] * 7 + [C.c_float] + [_FP] * 7),
     "risvec_soft_update": (C.c_int, [C.c_int32, _FP, _FP, _FP, C.c_float, C.c_float, _FP]),

@@ -24,11 +24,11 @@ def is_f32(t, device, shape=None) -> bool:
 _NOT_F32 = "%s: %s must be a contiguous float32 tensor of shape %s on %s (%s)"
 
 
-def choose_mode(name: str, mode, default, modes, fused_ok: bool, shape: str, rule: str):
+def choose_mode(name: str, mode, default, modes, fused_ok: bool, shape: str, rule: str, wide_ok: bool = False):
     """The value of a `gemm=` / `pack=` argument (None: `default`), refused unless it is one of `modes` and, for the modes
-    that need the fused kernel, the kernel is built for the shape."""
+    that need the fused kernel ("wide": the chunked one, `wide_ok`), the kernel is built for the shape."""
     chosen = mode if mode is not None else default
-    if chosen not in modes or (chosen in ("fused", "device") and not fused_ok):
+    if chosen not in modes or (chosen in ("fused", "device") and not fused_ok) or (chosen == "wide" and not wide_ok):
         raise ValueError("%s=%r is not available for %s (modes: %s; %s)" % (name, mode, shape, ", ".join(modes), rule))
     return chosen
 

@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(kPackBlock)
 k_marl_critic_pack(PackArgs P) {
     // pr, the pair of fragment rows, is the same for the 64 lanes of a wavefront: every branch below is wave-uniform
     // but the column guard of fc1
-    const int idx = blockIdx.x * kPackBlock + threadIdx.x;       // < 2^31: at most 2560 pairs of rows per net
+    const int idx = blockIdx.x * kPackBlock + threadIdx.x;       // < 2^31: at most 2560 pairs of rows per net (2304 at 512 inputs)
     const int lane = idx & (kWave - 1), r = lane & 31, h = lane >> 5;
     const int c = blockIdx.y;
     int q = idx >> 6;
@@ -140,25 +140,22 @@ k_marl_critic_pack(PackArgs P) {
     store_pair(N.ws, pr, lane, w);
 }
 
-}  // namespace
-
-long long marl_critic_pack_workspace(int S, int A, int F1, int F2, int F3, int n_nets) {
-    if (!marl_critic_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return 0;
+long long workspace_bytes(int n_nets) {
     const long long bytes = (long long)n_nets * 3 * kMaxBlocks * (long long)sizeof(float);
     return (bytes + 15) / 16 * 16;
 }
 
-hipError_t launch_marl_critic_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
-                                   void* workspace, hipStream_t st) {
-    if (!marl_critic_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return hipErrorInvalidValue;
+// The two launches for a shape one of the two rules covers; stream_bytes: what that rule's *_stream_bytes() states
+hipError_t launch_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets, void* workspace,
+                       long long stream_bytes, hipStream_t st) {
     const int IN = S + A, KS = ks_of(IN), NG = F1 / 32, MT2 = F2 / 128, MT3 = F3 / 128;
     const MarlLayout L = marl_layout(KS, NG, MT2, MT3);              // a block's pairs: half its rows
     PackArgs a{};
     a.IN = IN; a.F1 = F1; a.F2 = F2; a.F3 = F3; a.KS = KS; a.NG = NG; a.MT2 = MT2; a.MT3 = MT3;
     a.n_fc1 = (int)((L.fc2 - L.fc1) / 2); a.n_fc2 = (int)((L.fc3 - L.fc2) / 2); a.n_fc3 = (int)((L.rows - L.fc3) / 2);
-    // the pairs of rows in all: half the rows of marl_critic_stream_bytes()
+    // the pairs of rows in all: half the rows of the stream
     const long long pairs = (long long)a.n_fc1 + a.n_fc2 + a.n_fc3;
-    if (pairs * 2048 != marl_critic_stream_bytes(S, A, F1, F2, F3)) return hipErrorInvalidValue;
+    if (pairs * 2048 != stream_bytes) return hipErrorInvalidValue;
     uintptr_t align = 0;
     for (int i = 0; i < kMaxNets; ++i) {
         const RisVecMarlCriticPackNet& n = nets[i < n_nets ? i : 0];  // the unused slot of a single net repeats net 1
@@ -174,6 +171,30 @@ hipError_t launch_marl_critic_pack(int S, int A, int F1, int F2, int F3, int n_n
     hipLaunchKernelGGL(k_marl_critic_pack, dim3((unsigned)((pairs * kWave + kPackBlock - 1) / kPackBlock), n_nets),
                        dim3(kPackBlock), 0, st, a);
     return hipGetLastError();
+}
+
+}  // namespace
+
+long long marl_critic_pack_workspace(int S, int A, int F1, int F2, int F3, int n_nets) {
+    if (!marl_critic_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return 0;
+    return workspace_bytes(n_nets);
+}
+
+long long marl_critic_wide_pack_workspace(int S, int A, int F1, int F2, int F3, int n_nets) {
+    if (!marl_critic_wide_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return 0;
+    return workspace_bytes(n_nets);
+}
+
+hipError_t launch_marl_critic_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
+                                   void* workspace, hipStream_t st) {
+    if (!marl_critic_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return hipErrorInvalidValue;
+    return launch_pack(S, A, F1, F2, F3, n_nets, nets, workspace, marl_critic_stream_bytes(S, A, F1, F2, F3), st);
+}
+
+hipError_t launch_marl_critic_wide_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
+                                        void* workspace, hipStream_t st) {
+    if (!marl_critic_wide_supported(S, A, F1, F2, F3) || n_nets < 1 || n_nets > kMaxNets) return hipErrorInvalidValue;
+    return launch_pack(S, A, F1, F2, F3, n_nets, nets, workspace, marl_critic_wide_stream_bytes(S, A, F1, F2, F3), st);
 }
 
 }  // namespace risvec

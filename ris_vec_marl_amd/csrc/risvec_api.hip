@@ -1196,51 +1196,43 @@ int risvec_sarl_critic_pack(int32_t in_dims, int32_t fc1, int32_t fc2, int32_t f
                                                       workspace, (hipStream_t)stream));
 }
 
-int risvec_marl_critic_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
-    return risvec::marl_critic_supported(state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;
-}
+namespace {
 
-int64_t risvec_marl_critic_stream_bytes(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
-    return risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
-}
-
-int risvec_marl_critic(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
-                       int32_t n_nets, const RisVecMarlCriticNet* nets, const float* state, const float* action,
-                       const float* reward, const uint8_t* done, float gamma, const float* coef, const float* logp_power,
-                       const float* logp_intent, float* q1, float* q2, float* y, risvec_stream_t stream) {
-    const char* fn = "risvec_marl_critic";
+// risvec_marl_critic and risvec_marl_critic_wide: one argument list, one set of checks, two rules and two kernels
+int marl_critic_entry(const char* fn, bool wide, int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                      int32_t fc3, int32_t n_nets, const RisVecMarlCriticNet* nets, const float* state, const float* action,
+                      const float* reward, const uint8_t* done, float gamma, const float* coef, const float* logp_power,
+                      const float* logp_intent, float* q1, float* q2, float* y, risvec_stream_t stream) {
     if (n_rows < 1) return fail(RISVEC_ERR_ARG, "%s: n_rows=%d must be >= 1", fn, n_rows);
     if (n_nets < 1 || n_nets > 2) return fail(RISVEC_ERR_ARG, "%s: n_nets=%d must be 1 or 2", fn, n_nets);
-    if (!risvec::marl_critic_supported(state_dims, action_dims, fc1, fc2, fc3))
+    if (!(wide ? risvec::marl_critic_wide_supported : risvec::marl_critic_supported)(state_dims, action_dims, fc1, fc2, fc3))
         return fail(RISVEC_ERR_UNSUPPORTED, "%s: state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (built for state_dims + "
-                    "action_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256; use library "
-                    "kernels elsewhere)", fn, state_dims, action_dims, fc1, fc2, fc3);
+                    "action_dims <= %d, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256; use library "
+                    "kernels elsewhere)", fn, state_dims, action_dims, fc1, fc2, fc3, wide ? 512 : 128);
     if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
-    if (int rc = check_critic_nets(fn, nets, n_nets, risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3)))
-        return rc;
+    const long long bytes = (wide ? risvec::marl_critic_wide_stream_bytes : risvec::marl_critic_stream_bytes)(state_dims, action_dims,
+                                                                                                              fc1, fc2, fc3);
+    if (int rc = check_critic_nets(fn, nets, n_nets, bytes)) return rc;
     if (!state || !action) return fail(RISVEC_ERR_ARG, "%s: state or action is NULL", fn);
     if (int rc = check_critic_outputs(fn, n_nets, reward, done, gamma, coef, logp_power, logp_intent, q1, q2, y)) return rc;
-    return finish(fn, risvec::launch_marl_critic(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, state, action,
-                                                 reward, done, gamma, coef, logp_power, logp_intent, q1, q2, y,
-                                                 (hipStream_t)stream));
+    return finish(fn, (wide ? risvec::launch_marl_critic_wide : risvec::launch_marl_critic)(
+                          n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, state, action, reward, done, gamma, coef,
+                          logp_power, logp_intent, q1, q2, y, (hipStream_t)stream));
 }
 
-size_t risvec_marl_critic_pack_workspace(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
-                                         int32_t n_nets) {
-    return (size_t)risvec::marl_critic_pack_workspace(state_dims, action_dims, fc1, fc2, fc3, n_nets);
-}
-
-int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
-                            const RisVecMarlCriticPackNet* nets, void* workspace, size_t workspace_bytes,
-                            risvec_stream_t stream) {
-    const char* fn = "risvec_marl_critic_pack";
+// risvec_marl_critic_pack and risvec_marl_critic_wide_pack, likewise; ws_fn: the entry that states the workspace
+int marl_critic_pack_entry(const char* fn, const char* ws_fn, bool wide, int32_t state_dims, int32_t action_dims, int32_t fc1,
+                           int32_t fc2, int32_t fc3, int32_t n_nets, const RisVecMarlCriticPackNet* nets, void* workspace,
+                           size_t workspace_bytes, risvec_stream_t stream) {
     if (n_nets < 1 || n_nets > 2) return fail(RISVEC_ERR_ARG, "%s: n_nets=%d must be 1 or 2", fn, n_nets);
-    if (!risvec::marl_critic_supported(state_dims, action_dims, fc1, fc2, fc3))
-        return fail(RISVEC_ERR_UNSUPPORTED, "%s: state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (risvec_marl_critic is built "
-                    "for state_dims + action_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or "
-                    "256)", fn, state_dims, action_dims, fc1, fc2, fc3);
+    if (!(wide ? risvec::marl_critic_wide_supported : risvec::marl_critic_supported)(state_dims, action_dims, fc1, fc2, fc3))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (%s is built "
+                    "for state_dims + action_dims <= %d, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or "
+                    "256)", fn, state_dims, action_dims, fc1, fc2, fc3, wide ? "risvec_marl_critic_wide" : "risvec_marl_critic",
+                    wide ? 512 : 128);
     if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
-    const long long bytes = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+    const long long bytes = (wide ? risvec::marl_critic_wide_stream_bytes : risvec::marl_critic_stream_bytes)(state_dims, action_dims,
+                                                                                                              fc1, fc2, fc3);
     for (int c = 0; c < n_nets; ++c) {
         const RisVecMarlCriticPackNet& n = nets[c];
         const Indexed pre("nets", c);
@@ -1254,12 +1246,69 @@ int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1
     if (n_nets == 2 && nets[0].scales == nets[1].scales)
         return fail(RISVEC_ERR_ARG, "%s: nets[0].scales and nets[1].scales are the same buffer", fn);
     REQ_PTR(workspace, "workspace");
-    if (int rc = check_workspace_bytes(fn, workspace_bytes,
-                                       (size_t)risvec::marl_critic_pack_workspace(state_dims, action_dims, fc1, fc2, fc3, n_nets),
-                                       "call", "risvec_marl_critic_pack_workspace"))
-        return rc;
-    return finish(fn, risvec::launch_marl_critic_pack(state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, workspace,
-                                                      (hipStream_t)stream));
+    const long long need = (wide ? risvec::marl_critic_wide_pack_workspace : risvec::marl_critic_pack_workspace)(
+        state_dims, action_dims, fc1, fc2, fc3, n_nets);
+    if (int rc = check_workspace_bytes(fn, workspace_bytes, (size_t)need, "call", ws_fn)) return rc;
+    return finish(fn, (wide ? risvec::launch_marl_critic_wide_pack : risvec::launch_marl_critic_pack)(
+                          state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, workspace, (hipStream_t)stream));
+}
+
+}  // namespace
+
+int risvec_marl_critic_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
+    return risvec::marl_critic_supported(state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;
+}
+
+int64_t risvec_marl_critic_stream_bytes(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
+    return risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+}
+
+int risvec_marl_critic(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                       int32_t n_nets, const RisVecMarlCriticNet* nets, const float* state, const float* action,
+                       const float* reward, const uint8_t* done, float gamma, const float* coef, const float* logp_power,
+                       const float* logp_intent, float* q1, float* q2, float* y, risvec_stream_t stream) {
+    return marl_critic_entry("risvec_marl_critic", false, n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, state, action,
+                             reward, done, gamma, coef, logp_power, logp_intent, q1, q2, y, stream);
+}
+
+size_t risvec_marl_critic_pack_workspace(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                                         int32_t n_nets) {
+    return (size_t)risvec::marl_critic_pack_workspace(state_dims, action_dims, fc1, fc2, fc3, n_nets);
+}
+
+int risvec_marl_critic_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
+                            const RisVecMarlCriticPackNet* nets, void* workspace, size_t workspace_bytes,
+                            risvec_stream_t stream) {
+    return marl_critic_pack_entry("risvec_marl_critic_pack", "risvec_marl_critic_pack_workspace", false, state_dims, action_dims, fc1,
+                                  fc2, fc3, n_nets, nets, workspace, workspace_bytes, stream);
+}
+
+int risvec_marl_critic_wide_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
+    return risvec::marl_critic_wide_supported(state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;
+}
+
+int64_t risvec_marl_critic_wide_stream_bytes(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
+    return risvec::marl_critic_wide_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+}
+
+int risvec_marl_critic_wide(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                            int32_t n_nets, const RisVecMarlCriticNet* nets, const float* state, const float* action,
+                            const float* reward, const uint8_t* done, float gamma, const float* coef, const float* logp_power,
+                            const float* logp_intent, float* q1, float* q2, float* y, risvec_stream_t stream) {
+    return marl_critic_entry("risvec_marl_critic_wide", true, n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, state,
+                             action, reward, done, gamma, coef, logp_power, logp_intent, q1, q2, y, stream);
+}
+
+size_t risvec_marl_critic_wide_pack_workspace(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                                              int32_t n_nets) {
+    return (size_t)risvec::marl_critic_wide_pack_workspace(state_dims, action_dims, fc1, fc2, fc3, n_nets);
+}
+
+int risvec_marl_critic_wide_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
+                                 const RisVecMarlCriticPackNet* nets, void* workspace, size_t workspace_bytes,
+                                 risvec_stream_t stream) {
+    return marl_critic_pack_entry("risvec_marl_critic_wide_pack", "risvec_marl_critic_wide_pack_workspace", true, state_dims,
+                                  action_dims, fc1, fc2, fc3, n_nets, nets, workspace, workspace_bytes, stream);
 }
 
 int risvec_local_critics_supported(int32_t n_agents, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,

@@ -8,6 +8,8 @@
 //   s_in  the split B fragments of the input x, staged ONCE for all nets     [KS k-steps][hi | lo][64 lanes] x 16 bytes
 //   s_h   the fc1 activations, then the fc2 activations (each dead before the next)  [max(2 NG, fc2 / 16)][hi | lo][64]
 //   s_red the per-row partial sums of the q dot product, one slot per net: [kRedSlots][4 waves][32]
+// k_marl_critic_wide carves the same three with an s_in of 8 k-steps that it restages chunk by chunk; it runs fc1 itself
+// and takes the rest of the walk from marl_run_tail.
 #pragma once
 
 #include "risvec_launch.hpp"
@@ -95,6 +97,51 @@ __device__ __forceinline__ void marl_run_net(const MarlNetPtrs& P, int slot, con
     }
     __syncthreads();
 
+    // ---- fc2: output tiles [wave MT2, (wave + 1) MT2) over all 2 NG k-steps
+    f32x16_t acc[MT2];
+#pragma unroll
+    for (int m = 0; m < MT2; ++m)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[m][q] = 0.0f;
+    gemm_tiles<MT2>(acc, P.ws + (L.fc2 + (long long)wave * (2 * NG) * MT2 * 2) * kWave, s_h, 2 * NG, lane);
+    __syncthreads();                                          // every wavefront is past its fc2 MFMAs: s_h is free
+#pragma unroll
+    for (int m = 0; m < MT2; ++m) {
+        const int t = wave * MT2 + m;
+        put_tile(s_h, t, bias_relu(acc[m], u2, tile_of(P.b2, 32 * t, h)), lane);
+    }
+    __syncthreads();
+
+    // ---- fc3 + ReLU, then the 1-wide q layer as a dot product in registers
+    f32x16_t a3[MT3];
+#pragma unroll
+    for (int m = 0; m < MT3; ++m)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) a3[m][q] = 0.0f;
+    gemm_tiles<MT3>(a3, P.ws + (L.fc3 + (long long)wave * K3 * MT3 * 2) * kWave, s_h, K3, lane);
+    f32x16_t qs;
+#pragma unroll
+    for (int m = 0; m < MT3; ++m) {
+        const int f0 = 32 * (wave * MT3 + m);
+        const f32x16_t p = bias_relu(a3[m], u3, tile_of(P.b3, f0, h)) * tile_of(P.qw, f0, h);
+        qs = m == 0 ? p : qs + p;
+    }
+    float qp = sum16(qs);
+    qp += __shfl_xor(qp, 32, kWave);
+    if (h == 0) s_red[(slot * kMcWaves + wave) * 32 + r] = qp;
+    __syncthreads();                                          // every wavefront is past its fc3 MFMAs: s_h is free
+}
+
+// marl_run_net from its second barrier on, for a kernel that runs fc1 its own way (k_marl_critic_wide): the fc1
+// activations in s_h -> fc2 -> s_h, fc3 and the q dot product -> s_red[slot]; u2, u3 undo the fc2 and fc3 weight scalings.
+// Called under wave-uniform control flow after the barrier that completes s_h; ends on a barrier, after which s_h is free
+// again and s_red[slot] is complete.  A RESTATEMENT of marl_run_net's second half, statement for statement: having
+// marl_run_net call it changes k_marl_critic<4, *>'s registers (160 -> 162 VGPRs).  Keep the two in step.
+template <int MT2, int MT3>
+__device__ __forceinline__ void marl_run_tail(const MarlNetPtrs& P, int slot, uint4* s_h, float* s_red, const MarlLayout& L, int NG,
+                                              int wave, int lane, float u2, float u3) {
+    constexpr int K3 = 8 * MT2;                               // fc3 k-steps = fc2 / 16
+    const int r = lane & 31, h = lane >> 5;
     // ---- fc2: output tiles [wave MT2, (wave + 1) MT2) over all 2 NG k-steps
     f32x16_t acc[MT2];
 #pragma unroll

@@ -163,12 +163,23 @@ hipError_t launch_marl_critic(long long n_rows, int S, int A, int F1, int F2, in
                               const float* state, const float* action, const float* reward, const uint8_t* done, float gamma,
                               const float* coef, const float* logp_power, const float* logp_intent, float* q1, float* q2,
                               float* y, hipStream_t st);
+// The same launch with fc1 walking the input in chunks (k_marl_critic_wide in k_marl_critic.hip), for S + A <= 512: the
+// same arguments, the same weight stream (marl_layout at this shape's KS), a rule of its own that overlaps the one above.
+bool marl_critic_wide_supported(int S, int A, int F1, int F2, int F3);
+long long marl_critic_wide_stream_bytes(int S, int A, int F1, int F2, int F3);
+hipError_t launch_marl_critic_wide(long long n_rows, int S, int A, int F1, int F2, int F3, int n_nets,
+                                   const RisVecMarlCriticNet* nets, const float* state, const float* action, const float* reward,
+                                   const uint8_t* done, float gamma, const float* coef, const float* logp_power,
+                                   const float* logp_intent, float* q1, float* q2, float* y, hipStream_t st);
 // The weight streams and scales of n_nets in {1, 2} such nets from their float32 weights, in two launches in all
 // (k_marl_critic_pack.hip); the workspace holds marl_critic_pack_workspace() bytes (0: no such shape or net count) and
-// needs no initialisation.
+// needs no initialisation.  The _wide pair is the same two kernels behind marl_critic_wide_supported.
 long long marl_critic_pack_workspace(int S, int A, int F1, int F2, int F3, int n_nets);
 hipError_t launch_marl_critic_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
                                    void* workspace, hipStream_t st);
+long long marl_critic_wide_pack_workspace(int S, int A, int F1, int F2, int F3, int n_nets);
+hipError_t launch_marl_critic_wide_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
+                                        void* workspace, hipStream_t st);
 
 // Every agent's local twin critics and local TD target in one launch (k_local_critics.hip): n_agents x n_nets nets of the
 // shape of k_marl_critic at (S, A), nets[j n_nets + c] = agent j's net c, on agent j's columns of the batch.  Exactly one of

@@ -8,7 +8,8 @@ ReLU MLP on `cat([state, action])` -- the minimum, the entropy term and the TD t
     ent = coef[0] logp_power + coef[1] logp_intent           an absent logp is an absent term
     y   = done ? reward : reward + gamma (m - ent)
 
-`BatchedTwinCritic.forward` / `td_target` are one launch (`risvec_marl_critic`); the log-probability sums arrive as
+`BatchedTwinCritic.forward` / `td_target` are one launch (`risvec_marl_critic`; gemm="wide": `risvec_marl_critic_wide`,
+which covers 16 vehicles); the log-probability sums arrive as
 tensors the learner already has.  `soft_update_from` is `update_global_network_parameters` (:394-400) for both nets in
 one launch; with pack="device" the next `td_target` rebuilds both weight streams in two launches in all
 (`risvec_marl_critic_pack`).  Nothing here differentiates: the gradient half of `global_learn` stays with the learner.  No CPU compute
@@ -58,16 +59,26 @@ def _supported(state_dims: int, action_dims: int, fc1_dims: int, fc2_dims: int, 
             and fc1_dims % 32 == 0 and fc1_dims <= 1024 and fc2_dims in (128, 256, 512) and fc3_dims in (128, 256))
 
 
-def pack_marl_critic_weights(W1, W2, W3) -> Tuple[torch.Tensor, torch.Tensor]:
+def _supported_wide(state_dims: int, action_dims: int, fc1_dims: int, fc2_dims: int, fc3_dims: int) -> bool:
+    """The rule of `risvec_marl_critic_wide_supported`, restated likewise: up to 512 inputs, the same fc sizes.  It
+    overlaps `_supported` on purpose."""
+    return (state_dims >= 1 and action_dims >= 1 and state_dims + action_dims <= 512 and fc1_dims >= 32
+            and fc1_dims % 32 == 0 and fc1_dims <= 1024 and fc2_dims in (128, 256, 512) and fc3_dims in (128, 256))
+
+
+def pack_marl_critic_weights(W1, W2, W3, wide: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(wstream [rows, 64, 8] float16, scales [3] float32) of one net of `risvec_marl_critic` from its float32 Linear
     weights ([out, in]: fc1 over [state | action], fc2, fc3).  A pure function of its arguments; runs on any device, CPU
-    included.  The biases and the q layer are read by the kernel as float32, as they are."""
+    included.  The biases and the q layer are read by the kernel as float32, as they are.  wide=True: the shapes of
+    `risvec_marl_critic_wide` (up to 512 inputs) -- the same layout at that shape's number of k-steps, and the same
+    bits where both rules hold."""
     if W1.dim() != 2 or W2.dim() != 2 or W3.dim() != 2:
         raise ValueError("pack_marl_critic_weights: W1, W2 and W3 are Linear weights [out, in]")
     (F1, IN), F2, F3 = W1.shape, W2.shape[0], W3.shape[0]
     # the rule depends on the two widths through their sum only
-    if IN < 2 or not _supported(IN - 1, 1, F1, F2, F3):
-        raise ValueError("no fused twin-critic kernel for state_dims + action_dims=%d fc1=%d fc2=%d fc3=%d" % (IN, F1, F2, F3))
+    if IN < 2 or not (_supported_wide if wide else _supported)(IN - 1, 1, F1, F2, F3):
+        raise ValueError("no %s twin-critic kernel for state_dims + action_dims=%d fc1=%d fc2=%d fc3=%d"
+                         % ("wide" if wide else "fused", IN, F1, F2, F3))
     if tuple(W2.shape) != (F2, F1) or tuple(W3.shape) != (F3, F2):
         raise ValueError("pack_marl_critic_weights: the weights' shapes do not chain")
     g = marl_critic_geom(IN - 1, 1, F1, F2, F3)
@@ -92,8 +103,21 @@ def pack_marl_critic_weights_device(weights: Sequence, out: Optional[Sequence] =
     them (default: new tensors); workspace: a uint8 tensor of at least `risvec_marl_critic_pack_workspace` bytes (default:
     a new one).  -> the list of (wstream, scales) pairs, bit for bit what the host function gives net by net.  What would
     have to be copied or converted is refused with ValueError."""
-    what = "pack_marl_critic_weights_device"
+    return _pack_device(weights, out, workspace, False, "pack_marl_critic_weights_device")
+
+
+def pack_marl_critic_weights_wide_device(weights: Sequence, out: Optional[Sequence] = None,
+                                         workspace: Optional[torch.Tensor] = None) -> list:
+    """`pack_marl_critic_weights_device` for the shapes of `risvec_marl_critic_wide` (up to 512 inputs), through
+    `risvec_marl_critic_wide_pack`: the same two kernels, the workspace of `risvec_marl_critic_wide_pack_workspace`, bit
+    for bit what `pack_marl_critic_weights(..., wide=True)` gives net by net."""
+    return _pack_device(weights, out, workspace, True, "pack_marl_critic_weights_wide_device")
+
+
+def _pack_device(weights, out, workspace, wide: bool, what: str) -> list:
     lib = N.load()
+    pack_workspace_fn = lib.risvec_marl_critic_wide_pack_workspace if wide else lib.risvec_marl_critic_pack_workspace
+    pack_fn = lib.risvec_marl_critic_wide_pack if wide else lib.risvec_marl_critic_pack
     try:
         weights = [tuple(ws) for ws in weights]
     except TypeError:
@@ -120,9 +144,10 @@ def pack_marl_critic_weights_device(weights: Sequence, out: Optional[Sequence] =
                                  % (what, name, c + 1, tuple(t.shape), shape))
     # the rule depends on the two widths through their sum only
     dims = (IN - 1, 1, F1, F2, F3)
-    need = int(lib.risvec_marl_critic_pack_workspace(*dims, n_nets)) if IN >= 2 else 0
+    need = int(pack_workspace_fn(*dims, n_nets)) if IN >= 2 else 0
     if need == 0:
-        raise ValueError("no fused twin-critic kernel for state_dims + action_dims=%d fc1=%d fc2=%d fc3=%d" % (IN, F1, F2, F3))
+        raise ValueError("no %s twin-critic kernel for state_dims + action_dims=%d fc1=%d fc2=%d fc3=%d"
+                         % ("wide" if wide else "fused", IN, F1, F2, F3))
     g = marl_critic_geom(*dims)
     try:
         out = [None] * n_nets if out is None else [tuple(o) for o in out]
@@ -136,8 +161,7 @@ def pack_marl_critic_weights_device(weights: Sequence, out: Optional[Sequence] =
     for c, (ws, (stream, scales)) in enumerate(zip(weights, out)):
         nets[c] = N.RisVecMarlCriticPackNet(ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), stream.data_ptr(),
                                             stream.numel() * stream.element_size(), scales.data_ptr())
-    N.check(lib.risvec_marl_critic_pack(*dims, n_nets, C.cast(nets, C.c_void_p), workspace.data_ptr(), workspace.numel(),
-                                        N.stream(dev)))
+    N.check(pack_fn(*dims, n_nets, C.cast(nets, C.c_void_p), workspace.data_ptr(), workspace.numel(), N.stream(dev)))
     return out
 
 
@@ -160,14 +184,18 @@ class BatchedTwinCritic(CriticNets):
     local critics of `sac_agent.py:276-284` have the same class and the same target form, one call per agent.  With
     pack="device" both nets' stale weight streams are rebuilt together, in two launches (see `CriticNets.pack`)."""
 
+    GEMM_MODES = ("fused", "library", "wide")
+
     def __init__(self, state_dims: int, action_dims: int, fc1_dims: int = 1024, fc2_dims: int = 512, fc3_dims: int = 256,
                  n_nets: int = 2, device="cuda", seed: int = 0, gemm: Optional[str] = None):
         """gemm: how `forward` / `td_target` run.  "fused": one hand-written MFMA launch (`risvec_marl_critic`: float16
         hi + lo split products at float32 accuracy, neither the hidden layers nor the concatenated input ever in memory);
         built for state_dims + action_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}.
         "library": `forward_torch` and the same epilogue with torch.nn.functional only -- the fallback for every other
-        shape (16 vehicles: 80 + 288 inputs) and the comparator.  Default (None): fused where built, for batches of at
-        least `AUTO_MIN_ROWS` rows; library otherwise."""
+        shape (16 vehicles: 80 + 288 inputs) and the comparator.  "wide": one launch of `risvec_marl_critic_wide`, the
+        fused kernel with fc1 walking the input in chunks of 128; built for state_dims + action_dims <= 512 and the same
+        fc sizes, so for 16 vehicles too; opt-in, and `pack = "device"` is available with it.  Default (None): fused
+        where built, for batches of at least `AUTO_MIN_ROWS` rows; library otherwise -- never wide."""
         lib = N.load()
         self.device = N.resolve_device(device)
         N.require_hip(self.device)
@@ -180,7 +208,8 @@ class BatchedTwinCritic(CriticNets):
         if self.n_nets not in (1, 2):
             raise ValueError("BatchedTwinCritic: n_nets must be 1 or 2")
         self._init_modes(gemm, bool(lib.risvec_marl_critic_supported(*self._dims)),
-                         "fused: state_dims + action_dims <= 128, fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, fc3 in {128, 256}")
+                         "fused: state_dims + action_dims <= 128 (wide: <= 512), fc1 % 32 == 0 <= 1024, fc2 in {128, 256, 512}, "
+                         "fc3 in {128, 256}", bool(lib.risvec_marl_critic_wide_supported(*self._dims)))
         g = torch.Generator(device="cpu").manual_seed(seed)
         self.nets = [draw_net(g, self.state_dims + self.action_dims, *self._dims[2:], self.device) for _ in range(self.n_nets)]
 
@@ -245,7 +274,8 @@ class BatchedTwinCritic(CriticNets):
         nets = net_table(self.n_nets, self.nets, self._fused_weights())
         q1 = qs[0] if qs is not None else None
         q2 = qs[1] if qs is not None and self.n_nets == 2 else None
-        N.check(N.load().risvec_marl_critic(
+        lib = N.load()
+        N.check((lib.risvec_marl_critic_wide if self.gemm == "wide" else lib.risvec_marl_critic)(
             n, *self._dims, self.n_nets, C.cast(nets, C.c_void_p), state.data_ptr(), action.data_ptr(), N.ptr(reward), N.ptr(done), float(gamma),
             N.ptr(coef), N.ptr(lp), N.ptr(li), N.ptr(q1), N.ptr(q2), N.ptr(y), N.stream(self.device)))
 
