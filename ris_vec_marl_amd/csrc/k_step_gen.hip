@@ -41,7 +41,18 @@
 
 #include "risvec_pipe.hpp"
 
+// How the GEN members write step()'s outputs (StorePolicy, risvec_step.hpp): every output with the non-temporal hint,
+// row-lane and stage form, both cores.  A launch leaves 48 V + 68 bytes per env behind (14.8 MB at 32 768 x 8) and
+// nothing on the device reads them before the launch ends; plain stores left them all dirty in L2 for the end of the
+// launch to write back.  Measured against plain, write-through and write-through with the re-read tensors or obs left
+// plain (EXPERIMENTS.md 2026-10-20 (d)); RISVEC_GEN_STORES builds the others (Makefile: gen_ab).
+#ifndef RISVEC_GEN_STORES
+#define RISVEC_GEN_STORES kStNonTemporal
+#endif
+
 namespace risvec {
+
+using GenStores = StorePolicy<RISVEC_GEN_STORES>;
 
 template <int V, int M>
 struct GenShape : PipeShape<V, M> {
@@ -284,7 +295,7 @@ __device__ __forceinline__ void gen_stage_form(const GenArgs<Core>& KA) {
         const GenArgs<Core>& L = late_args<Core>();
         __builtin_amdgcn_wave_barrier();
         const float2 img = *reinterpret_cast<const float2*>(&s_img[wave][lane * 2]);
-        Core::template run<VP>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
+        Core::template run<VP, GenStores>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
     } else {
         const int per_wave = KA.per_wave;
         const int nw = gridDim.x * (kBlock / kWave);
@@ -333,7 +344,7 @@ __device__ __forceinline__ void gen_stage_form(const GenArgs<Core>& KA) {
 
             __builtin_amdgcn_wave_barrier();
             const float2 img = *reinterpret_cast<const float2*>(&s_img[wave][lane * 2]);
-            Core::template run<VP>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
+            Core::template run<VP, GenStores>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
             __builtin_amdgcn_wave_barrier();
         };
 
@@ -520,7 +531,7 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
     const float2 img = row_tree<G>(leaf);
 
     const GenArgs<Core>& L = late_args<Core>();
-    Core::template run<VP>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
+    Core::template run<VP, GenStores>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
 }
 
 // The shapes whose one-group member is the row-per-lane form: those that keep four wavefronts per SIMD (128 VGPRs) with it.

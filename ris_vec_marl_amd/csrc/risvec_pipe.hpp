@@ -86,16 +86,16 @@ struct MarlCore {
     static __device__ __forceinline__ void hold(const In& in) {
         asm volatile("" ::"v"(in.a0), "v"(in.a1), "v"(in.B), "v"(in.Q0), "v"(in.pl), "v"(in.part), "v"(in.G), "v"(in.arr_in));
     }
-    template <int VP>
+    template <int VP, class ST = StepStores>
     static __device__ __forceinline__ void run(const Dims& d, const Params& P, const Args& A, int e, int v,
                                                bool active, float2 img, const In& in) {
         float g = 0.f;
         if (active) {
             const long long idx = (long long)e * d.V + v;
             g = gain_from_img(img, in.pl, A.h_d, idx);
-            A.gain[idx] = g;
+            st_to<ST::reread>(A.gain[idx]) = g;
         }
-        step_core<VP>(d, P, A, e, v, active, g, in);
+        step_core<VP, false, false, NoRing, ST>(d, P, A, e, v, active, g, in);
     }
 };
 
@@ -161,7 +161,7 @@ struct MarlRingCore {
 #pragma unroll
         for (int k = 0; k < VPC / 4; ++k) asm volatile("" ::"v"(in.r.mk[k]));
     }
-    template <int VP>
+    template <int VP, class ST = StepStores>
     static __device__ __forceinline__ void run(const Dims& d, const Params& P, const Args& A, int e, int v,
                                                bool active, float2 img, const In& in) {
         static_assert(VP == VPC, "ring core instantiated for another V");
@@ -169,9 +169,9 @@ struct MarlRingCore {
         if (active) {
             const long long idx = (long long)e * d.V + v;
             g = gain_from_img(img, in.s.pl, A.h_d, idx);
-            A.gain[idx] = g;
+            st_to<ST::reread>(A.gain[idx]) = g;
         }
-        step_core<VP, false, false, RingIn<VPC>>(d, P, A, e, v, active, g, in.s, nullptr, &in.r);
+        step_core<VP, false, false, RingIn<VPC>, ST>(d, P, A, e, v, active, g, in.s, nullptr, &in.r);
     }
 };
 

@@ -351,15 +351,66 @@ inline int pick_group(int M, int vec, int VP) {
     return g;
 }
 
-// store of an output nobody reads again before the next kernel (experiment switch: non-temporal hint)
-template <class T>
-__device__ __forceinline__ void st_out(T* p, T v) {
-#ifdef RISVEC_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
+// How step() writes its outputs: a compile-time policy of the kernel that calls it (step_core / step_tail / Core::run).
+//   kStPlain        `*p = v`: the line stays dirty in the XCD's L2 until the end of the launch writes it back
+//   kStThrough      write-through (sc1): the bytes leave L2 as they are stored, the line is dropped
+//   kStNonTemporal  the nt hint: the line stays in L2, first in line to go
+// Three classes of output take a kind each: `out` (rate, data_t, data_p, reward, over_power, power_w, metrics: nobody on
+// the device reads them before the next kernel), `reread` (data_buf, mec_q, gain: the next launch or the cached step
+// reads them back) and `obs` (five 4-byte stores 20 bytes apart per lane).  StepStores is what a kernel gets when it
+// names no policy: plain everywhere -- with it a kernel compiles to what it was before the policy existed -- unless the
+// whole library is built with another kind (RISVEC_STEP_STORES: the A/B library of the Makefile's `stores_ab`).  The GEN
+// members name their own (GenStores, k_step_gen.hip).  The replay ring's stores are not the policy's: they are
+// non-temporal always (ring_st*).
+enum : int { kStPlain = 0, kStThrough = 1, kStNonTemporal = 2 };
+template <int OUT, int REREAD = OUT, int OBS = OUT>
+struct StorePolicy {
+    static constexpr int out = OUT, reread = REREAD, obs = OBS;
+};
+#ifndef RISVEC_STEP_STORES
+#define RISVEC_STEP_STORES kStPlain
 #endif
+using StepStores = StorePolicy<RISVEC_STEP_STORES>;
+
+template <int KIND, class T>
+__device__ __forceinline__ void st_out(T* p, T v) {
+    static_assert(sizeof(T) <= 8, "16-byte outputs go through st_out4");
+    if constexpr (KIND == kStThrough) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (KIND == kStNonTemporal) __builtin_nontemporal_store(v, p);
+    else *p = v;
 }
+// The same store written as an assignment, `st_to<KIND>(x) = v`: for the outputs step() used to assign directly.  (An
+// assignment evaluates its right side first, a call its arguments left to right; keeping each site's order keeps the
+// plain policy's code what it was.)
+template <int KIND, class T>
+struct StoreTo {
+    T* p;
+    __device__ __forceinline__ void operator=(T v) const { st_out<KIND>(p, v); }
+};
+template <int KIND, class T>
+__device__ __forceinline__ StoreTo<KIND, T> st_to(T& x) { return StoreTo<KIND, T>{&x}; }
+// 16 bytes: no atomic store is that wide, so the write-through form is the instruction itself.  The `s_nop 1` keeps the
+// compiler's next instruction off the data registers until the store has read them.
+template <int KIND>
+__device__ __forceinline__ void st_out4(float4* p, float4 v) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    if constexpr (KIND == kStThrough) {
+        v4f t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(t) : "memory");
+    } else if constexpr (KIND == kStNonTemporal) {
+        v4f t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+        __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
+    } else {
+        *p = v;
+    }
+}
+template <int KIND>
+struct StoreTo4 {
+    float4* p;
+    __device__ __forceinline__ void operator=(const float4& v) const { st_out4<KIND>(p, v); }
+};
+template <int KIND>
+__device__ __forceinline__ StoreTo4<KIND> st_to4(float4& x) { return StoreTo4<KIND>{&x}; }
 
 // Per-step extras of the multi-step launch (risvec_step_fused_multi): where this step's trajectory
 // record goes (pointers already offset to the step's slice; nullptr = not recorded) and whether the
@@ -576,7 +627,7 @@ __device__ __forceinline__ StepPre step_pre(const Dims& d, const RisVecParams& P
 
 struct NoRing {};
 
-template <int VP, bool TRAJ = false, bool TM = false, class RIN = NoRing>
+template <int VP, bool TRAJ = false, bool TM = false, class RIN = NoRing, class ST = StepStores>
 __device__ __forceinline__ StepCarry step_tail(const Dims& d, const RisVecParams& P, const StepArgs& A,
                                                int e, int v, bool active, float gain, const StepIn& in,
                                                const StepPre& pre, const StepTraj* tj = nullptr, const RIN* rin = nullptr) {
@@ -656,24 +707,24 @@ __device__ __forceinline__ StepCarry step_tail(const Dims& d, const RisVecParams
     bool store_state = true;
     if constexpr (TRAJ) store_state = tj->store_state;
     if (active && store_state) {
-        A.data_buf[idx] = Bn;
-        st_out(A.rate + idx, rate);
-        st_out(A.data_t + idx, data_t);
-        st_out(A.data_p + idx, data_p);
-        st_out(A.reward + idx, rew);
-        st_out(A.over_power + idx, over_power);
+        st_to<ST::reread>(A.data_buf[idx]) = Bn;
+        st_out<ST::out>(A.rate + idx, rate);
+        st_out<ST::out>(A.data_t + idx, data_t);
+        st_out<ST::out>(A.data_p + idx, data_p);
+        st_out<ST::out>(A.reward + idx, rew);
+        st_out<ST::out>(A.over_power + idx, over_power);
         if (A.flags & RISVEC_STEP_OBS) {
             // marl_train_bcd.py:819-827 (element 3 = over_data/10 is always 0)
             float* o = A.obs + idx * 5;
-            st_out(o + 0, Bn * 0.1f); st_out(o + 1, data_t * 0.1f); st_out(o + 2, data_p * 0.1f); st_out(o + 3, 0.f);
-            st_out(o + 4, rate * 0.05f);
+            st_out<ST::obs>(o + 0, Bn * 0.1f); st_out<ST::obs>(o + 1, data_t * 0.1f); st_out<ST::obs>(o + 2, data_p * 0.1f);
+            st_out<ST::obs>(o + 3, 0.f); st_out<ST::obs>(o + 4, rate * 0.05f);
         }
         if (A.flags & RISVEC_STEP_POWER_W) {
             const float inv_tf = __builtin_amdgcn_rcpf(tf);
-            A.power_w[(long long)e * 2 * V + v] = E_tx * inv_tf;
-            A.power_w[(long long)e * 2 * V + V + v] = E_loc * inv_tf;
+            st_to<ST::out>(A.power_w[(long long)e * 2 * V + v]) = E_tx * inv_tf;
+            st_to<ST::out>(A.power_w[(long long)e * 2 * V + V + v]) = E_loc * inv_tf;
         }
-        if (v == 0) A.mec_q[e] = Q;
+        if (v == 0) st_to<ST::reread>(A.mec_q[e]) = Q;
         if constexpr (RING) ring_store<VP>(A, e, v, *rin, in, Bn, data_t, data_p, rate, rew);
     }
     if constexpr (TRAJ) {
@@ -719,7 +770,7 @@ __device__ __forceinline__ StepCarry step_tail(const Dims& d, const RisVecParams
                             ring_st(A.ring.reward_global_memory + row, val);
                         }
                     }
-                    if (store_state) A.metrics[(long long)e * RISVEC_METRICS + slot] = val;
+                    if (store_state) st_to<ST::out>(A.metrics[(long long)e * RISVEC_METRICS + slot]) = val;
                     if constexpr (TRAJ) {
                         if (tj->metrics) tj->metrics[(long long)e * RISVEC_METRICS + slot] = val;
                     }
@@ -756,7 +807,7 @@ __device__ __forceinline__ StepCarry step_tail(const Dims& d, const RisVecParams
             const float4 m3 = make_float4(s_de * inv_v, s_en * inv_v, 0.f, 0.f);
             if (store_state) {
                 float4* m = reinterpret_cast<float4*>(A.metrics + (long long)e * RISVEC_METRICS);
-                m[0] = m0; m[1] = m1; m[2] = m2; m[3] = m3;
+                st_to4<ST::out>(m[0]) = m0; st_to4<ST::out>(m[1]) = m1; st_to4<ST::out>(m[2]) = m2; st_to4<ST::out>(m[3]) = m3;
             }
             if constexpr (TRAJ) {
                 if (tj->metrics) {
@@ -766,7 +817,7 @@ __device__ __forceinline__ StepCarry step_tail(const Dims& d, const RisVecParams
             }
         }
     } else if (active && v == 0) {
-        if (store_state) A.metrics[(long long)e * RISVEC_METRICS] = rew_sum * inv_v;          // global_reward only
+        if (store_state) st_to<ST::out>(A.metrics[(long long)e * RISVEC_METRICS]) = rew_sum * inv_v;   // global_reward only
         if constexpr (TRAJ) {
             if (tj->metrics) tj->metrics[(long long)e * RISVEC_METRICS] = rew_sum * inv_v;
         }
@@ -774,12 +825,12 @@ __device__ __forceinline__ StepCarry step_tail(const Dims& d, const RisVecParams
     return StepCarry{Bn, Q};
 }
 
-template <int VP, bool TRAJ = false, bool TM = false, class RIN = NoRing>
+template <int VP, bool TRAJ = false, bool TM = false, class RIN = NoRing, class ST = StepStores>
 __device__ __forceinline__ StepCarry step_core(const Dims& d, const RisVecParams& P, const StepArgs& A,
                                                int e, int v, bool active, float gain, const StepIn& in,
                                                const StepTraj* tj = nullptr, const RIN* rin = nullptr) {
     const StepPre pre = step_pre<TRAJ>(d, P, A, e, v, active, in);
-    return step_tail<VP, TRAJ, TM, RIN>(d, P, A, e, v, active, gain, in, pre, tj, rin);
+    return step_tail<VP, TRAJ, TM, RIN, ST>(d, P, A, e, v, active, gain, in, pre, tj, rin);
 }
 
 inline StepArgs make_step_args(const RisVecState& s, const float* action, const int32_t* partner,
