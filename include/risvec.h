@@ -998,6 +998,48 @@ size_t risvec_marl_critic_wide_pack_workspace(int32_t state_dims, int32_t action
 int risvec_marl_critic_wide_pack(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3, int32_t n_nets,
                                  const RisVecMarlCriticPackNet *nets, void *workspace, size_t workspace_bytes,
                                  risvec_stream_t stream);
+/* The critic loss of the multi-agent (SAC) learner and its gradients (Global_SAC_Critic.global_learn,
+ * Simulation-MARL-BCD/global_sac_critic.py:355-363: q1, q2 = the online critics, loss = mse(q1, y) + mse(q2, y),
+ * loss.backward()) without an autograd graph, in TWO launches on `stream` for n_rows rows and n_nets in {1, 2} nets of one
+ * shape, per net c:
+ *     e = (2 / n_rows) (q_c - target)                         target [n_rows]: a constant, read in place
+ *     loss[0] = sum_c (1 / n_rows) sum_b (q_c[b] - target[b])^2
+ *     d3 = (e qw) [h3 > 0]   d2 = (W3^T d3) [h2 > 0]   d1 = (W2^T d2) [h1 > 0]              (relu backward: out > 0)
+ *     dqw = sum_b e h3   dqb = sum_b e   dWl = dl^T a(l-1) (a0 = [state | action])   dbl = sum_b dl
+ * The gradients are OVERWRITTEN, never accumulated (zero_grad(set_to_none=True) and one backward()), every byte of them.
+ * Launch 1 (grid: 32-row tiles x nets) walks the forward of risvec_marl_critic on the packed stream, leaves every
+ * activation in the workspace, back-propagates the deltas within the workgroup -- the transposed products read the float32
+ * W2 and W3 IN PLACE, scaled by the power of two that `scales` records and split on the fly -- and writes q1 / q2.  Launch
+ * 2 runs one wavefront per 32 x 32 tile of every dWl over the batch; a few more wavefronts sum dqw, dqb and the loss in
+ * float64.  Deltas are multiplied by an exact power of two (per tile in launch 1, per layer and net in launch 2) that
+ * brings their largest entry into [64, 128) before the float16 split and the accumulator is multiplied back, so the
+ * accuracy is the forward's at any size of the TD error.  No atomics: every output element has one writer that sums in a
+ * fixed order, and every call gives the same bits.  No synchronisation, no allocation.
+ *   nets[c].fwd    the net as risvec_marl_critic takes it: a stream that is current for W1, W2, W3;
+ *   nets[c].W2 / W3  the float32 Linear weights [fc2, fc1] / [fc3, fc2] behind that stream, float-aligned;
+ *   grads[c]       dW1 [fc1, state_dims + action_dims], db1 [fc1], dW2 [fc2, fc1], db2 [fc2], dW3 [fc3, fc2], db3 [fc3],
+ *                  dqw [fc3], dqb [1]: float-aligned, all distinct;
+ *   state, action  as for risvec_marl_critic; no row >= n_rows of state, action or target is read;
+ *   q1, q2 [n_rows]  receive q_c; q2 with n_nets == 2 only (and then required);
+ *   workspace      risvec_marl_critic_grad_workspace(n_rows, ...) bytes (0: n_rows < 1, a shape that is not built, or
+ *                  n_nets outside {1, 2}), 16-byte aligned, of any content.
+ * Built for the shapes of risvec_marl_critic (risvec_marl_critic_grad_supported, host only); other shapes return
+ * RISVEC_ERR_UNSUPPORTED.  A NULL or misaligned pointer, n_rows < 1, n_nets outside {1, 2}, a wrong wstream_bytes and too
+ * small a workspace return RISVEC_ERR_ARG; all are reported before anything is launched and without touching a device. */
+typedef struct RisVecMarlCriticGradNet {
+    RisVecMarlCriticNet fwd;
+    const float *W2, *W3;
+} RisVecMarlCriticGradNet;
+typedef struct RisVecMarlCriticGrads {
+    float *dW1, *db1, *dW2, *db2, *dW3, *db3, *dqw, *dqb;
+} RisVecMarlCriticGrads;
+int risvec_marl_critic_grad_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3);
+size_t risvec_marl_critic_grad_workspace(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                                         int32_t fc3, int32_t n_nets);
+int risvec_marl_critic_grad(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                            int32_t n_nets, const RisVecMarlCriticGradNet *nets, const RisVecMarlCriticGrads *grads,
+                            const float *state, const float *action, const float *target, float *q1, float *q2, float *loss,
+                            void *workspace, size_t workspace_bytes, risvec_stream_t stream);
 /* Every agent's local twin target critics and local TD target of the multi-agent (SAC) learner (Agent.local_learn,
  * Simulation-MARL-BCD/sac_agent.py:263-284, called once per agent by global_sac_critic.py:373-392) in ONE launch for n_rows
  * rows and n_agents agents; grid (ceil(n_rows / 32), n_agents).  Agent j has n_nets in {1, 2} CriticNetworks of one shape

@@ -53,6 +53,39 @@ def net_table(count: int, nets, packed):
     return table
 
 
+def grad_tables(count: int, nets, packed, grads):
+    """The `RisVecMarlCriticGradNet` and `RisVecMarlCriticGrads` arrays of a `risvec_marl_critic_grad` launch: `count` nets,
+    their (wstream, scales) and their 8 gradient tensors in `_Net._WEIGHTS` order."""
+    fwd = net_table(count, nets, packed)
+    table, out = (N.RisVecMarlCriticGradNet * count)(), (N.RisVecMarlCriticGrads * count)()
+    for k, (net, g) in enumerate(zip(nets, grads)):
+        table[k] = N.RisVecMarlCriticGradNet(fwd[k], net.W2.data_ptr(), net.W3.data_ptr())
+        out[k] = N.RisVecMarlCriticGrads(*(t.data_ptr() for t in g))
+    return table, out
+
+
+def check_grads(grads, nets, what: str, device) -> list:
+    """The caller's gradient tensors, nested like `BatchedAdam`'s groups: per net 8 contiguous float32 tensors shaped like
+    the weights in `state_dict()` order, written in place.  -> a list of lists."""
+    try:
+        nested = [list(g) for g in grads]
+    except TypeError:
+        raise ValueError("%s: grads is a nested sequence, 8 tensors per net" % what) from None
+    if len(nested) != len(nets) or any(len(g) != len(_Net._WEIGHTS) for g in nested):
+        raise ValueError("%s: grads holds %d lists of %d tensors" % (what, len(nets), len(_Net._WEIGHTS)))
+    names = {a: k for k, a in _Net._SD.items()}
+    for c, (net, g) in enumerate(zip(nets, nested)):
+        for a, t in zip(_Net._WEIGHTS, g):
+            shape = getattr(net, a).shape
+            if not is_f32(t, device, shape):
+                raise ValueError("%s: the gradient of %s of net %d must be a contiguous float32 tensor of shape %s on %s "
+                                 "(it is written in place)" % (what, names[a], c + 1, tuple(shape), device))
+    flat = [t.data_ptr() for g in nested for t in g]
+    if len(set(flat)) != len(flat):
+        raise ValueError("%s: two gradient tensors are the same" % what)
+    return nested
+
+
 def q_net(net: _Net, x: torch.Tensor) -> torch.Tensor:
     """NET:38-49 of one net on the ready input x = [state | action], with library kernels."""
     F = torch.nn.functional
@@ -123,6 +156,7 @@ class CriticNets:
         self.gemm = choose_mode("gemm", gemm, "fused" if fused_ok else "library", self.GEMM_MODES, fused_ok, self._shape(), rule,
                                 wide_ok)
         self.fused_min_rows = self.AUTO_MIN_ROWS if gemm is None else 1
+        self._gemm_auto = gemm is None                        # the mode was chosen by default: measured row rules apply
         self._fused_ok = fused_ok
         self._wide = self.gemm == "wide"                      # built as gemm="wide": the streams are packed under the wide rule
         self._pack = "host"                                   # see `pack`

@@ -1311,6 +1311,69 @@ int risvec_marl_critic_wide_pack(int32_t state_dims, int32_t action_dims, int32_
                                   action_dims, fc1, fc2, fc3, n_nets, nets, workspace, workspace_bytes, stream);
 }
 
+int risvec_marl_critic_grad_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
+    return risvec::marl_critic_grad_supported(state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;
+}
+
+size_t risvec_marl_critic_grad_workspace(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                                         int32_t fc3, int32_t n_nets) {
+    return risvec::marl_critic_grad_workspace(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets);
+}
+
+int risvec_marl_critic_grad(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3,
+                            int32_t n_nets, const RisVecMarlCriticGradNet* nets, const RisVecMarlCriticGrads* grads,
+                            const float* state, const float* action, const float* target, float* q1, float* q2, float* loss,
+                            void* workspace, size_t workspace_bytes, risvec_stream_t stream) {
+    const char* fn = "risvec_marl_critic_grad";
+    if (n_rows < 1) return fail(RISVEC_ERR_ARG, "%s: n_rows=%d must be >= 1", fn, n_rows);
+    if (n_nets < 1 || n_nets > 2) return fail(RISVEC_ERR_ARG, "%s: n_nets=%d must be 1 or 2", fn, n_nets);
+    if (!risvec::marl_critic_grad_supported(state_dims, action_dims, fc1, fc2, fc3))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (built for state_dims + "
+                    "action_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256; use library "
+                    "kernels elsewhere)", fn, state_dims, action_dims, fc1, fc2, fc3);
+    if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
+    if (!grads) return fail(RISVEC_ERR_ARG, "%s: grads is NULL", fn);
+    const long long bytes = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+    for (int c = 0; c < n_nets; ++c) {
+        const RisVecMarlCriticNet& n = nets[c].fwd;
+        const Indexed pre("nets", c);
+        if (int rc = check_wstream_bytes(fn, pre.s, n.wstream_bytes, bytes)) return rc;
+        REQ_PTR_IN(pre.s, n.wstream, "wstream"); REQ_PTR_IN(pre.s, n.scales, "scales"); REQ_PTR_IN(pre.s, n.b1, "b1");
+        REQ_PTR_IN(pre.s, n.b2, "b2"); REQ_PTR_IN(pre.s, n.b3, "b3"); REQ_PTR_IN(pre.s, n.qw, "qw");
+        if (!n.qb) return fail(RISVEC_ERR_ARG, "%s: %sqb is NULL", fn, pre.s);
+        REQ_F32_IN(pre.s, nets[c].W2, "W2"); REQ_F32_IN(pre.s, nets[c].W3, "W3");
+        const RisVecMarlCriticGrads& g = grads[c];
+        const Indexed gpre("grads", c);
+        REQ_F32_IN(gpre.s, g.dW1, "dW1"); REQ_F32_IN(gpre.s, g.db1, "db1"); REQ_F32_IN(gpre.s, g.dW2, "dW2");
+        REQ_F32_IN(gpre.s, g.db2, "db2"); REQ_F32_IN(gpre.s, g.dW3, "dW3"); REQ_F32_IN(gpre.s, g.db3, "db3");
+        REQ_F32_IN(gpre.s, g.dqw, "dqw"); REQ_F32_IN(gpre.s, g.dqb, "dqb");
+    }
+    {   // one writer per gradient tensor
+        const float* all[16];
+        int k = 0;
+        for (int c = 0; c < n_nets; ++c) {
+            const RisVecMarlCriticGrads& g = grads[c];
+            for (const float* p : {g.dW1, g.db1, g.dW2, g.db2, g.dW3, g.db3, g.dqw, g.dqb}) all[k++] = p;
+        }
+        for (int a = 0; a < k; ++a)
+            for (int b = a + 1; b < k; ++b)
+                if (all[a] == all[b]) return fail(RISVEC_ERR_ARG, "%s: two gradient tensors are the same buffer", fn);
+    }
+    if (!state || !action) return fail(RISVEC_ERR_ARG, "%s: state or action is NULL", fn);
+    OPT_F32_IN("", state, "state"); OPT_F32_IN("", action, "action");
+    REQ_F32_IN("", target, "target");
+    REQ_F32_IN("", q1, "q1");
+    if (n_nets == 2) REQ_F32_IN("", q2, "q2");
+    else if (q2) return fail(RISVEC_ERR_ARG, "%s: q2 needs n_nets == 2", fn);
+    if (n_nets == 2 && q1 == q2) return fail(RISVEC_ERR_ARG, "%s: q1 and q2 are the same buffer", fn);
+    REQ_F32_IN("", loss, "loss");
+    REQ_PTR(workspace, "workspace");
+    const size_t need = risvec::marl_critic_grad_workspace(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets);
+    if (int rc = check_workspace_bytes(fn, workspace_bytes, need, "call", "risvec_marl_critic_grad_workspace")) return rc;
+    return finish(fn, risvec::launch_marl_critic_grad(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, grads, state, action,
+                                                      target, q1, q2, loss, workspace, (hipStream_t)stream));
+}
+
 int risvec_local_critics_supported(int32_t n_agents, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
                                    int32_t fc3) {
     return risvec::local_critics_supported(n_agents, state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;

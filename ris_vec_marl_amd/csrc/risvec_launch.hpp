@@ -181,6 +181,15 @@ long long marl_critic_wide_pack_workspace(int S, int A, int F1, int F2, int F3, 
 hipError_t launch_marl_critic_wide_pack(int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticPackNet* nets,
                                         void* workspace, hipStream_t st);
 
+// The critic loss and its gradients in two launches (k_marl_critic_grad.hip), for the shapes of marl_critic_supported:
+// the row launch walks the forward, leaves activations and deltas in the workspace and writes q1 / q2; the weight launch
+// writes every gradient tensor and the loss.  marl_critic_grad_workspace(): bytes (0: no such shape, net count or n_rows).
+bool marl_critic_grad_supported(int S, int A, int F1, int F2, int F3);
+size_t marl_critic_grad_workspace(long long n_rows, int S, int A, int F1, int F2, int F3, int n_nets);
+hipError_t launch_marl_critic_grad(long long n_rows, int S, int A, int F1, int F2, int F3, int n_nets, const RisVecMarlCriticGradNet* nets,
+                                   const RisVecMarlCriticGrads* grads, const float* state, const float* action, const float* target,
+                                   float* q1, float* q2, float* loss, void* workspace, hipStream_t st);
+
 // Every agent's local twin critics and local TD target in one launch (k_local_critics.hip): n_agents x n_nets nets of the
 // shape of k_marl_critic at (S, A), nets[j n_nets + c] = agent j's net c, on agent j's columns of the batch.  Exactly one of
 // action / heads is given (heads with power and A == n_agents + 2); q1, q2 and y [n_agents, n_rows] are optional.

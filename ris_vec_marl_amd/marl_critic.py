@@ -12,8 +12,9 @@ ReLU MLP on `cat([state, action])` -- the minimum, the entropy term and the TD t
 which covers 16 vehicles); the log-probability sums arrive as
 tensors the learner already has.  `soft_update_from` is `update_global_network_parameters` (:394-400) for both nets in
 one launch; with pack="device" the next `td_target` rebuilds both weight streams in two launches in all
-(`risvec_marl_critic_pack`).  Nothing here differentiates: the gradient half of `global_learn` stays with the learner.  No CPU compute
-path.
+(`risvec_marl_critic_pack`).  For the ONLINE critics `loss_backward` is the loss of `global_learn` (:355-363) and its
+gradient with respect to every weight in two launches (`risvec_marl_critic_grad`), without an autograd graph; the actor
+side of `global_learn` and the local critics' gradients stay with the learner.  No CPU compute path.
 """
 from __future__ import annotations
 
@@ -23,7 +24,8 @@ from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _native as N
-from ._critic_nets import CriticNets, _Net, draw_net, entropy_args, minus_entropy, net_table, q_net, q_outs  # noqa: F401 (_Net)
+from ._critic_nets import (CriticNets, _Net, check_grads, draw_net, entropy_args, grad_tables, minus_entropy, net_table, q_net,
+                           q_outs)
 from ._weights import (is_f32, load_weight_sets, out_f32, pack_out, pack_workspace, polyak_pairs, polyak_tau, rows_of,
                        share_weight_sets, soft_update_tensors, td_args, td_select)
 from ._wstream import _WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags
@@ -64,6 +66,21 @@ def _supported_wide(state_dims: int, action_dims: int, fc1_dims: int, fc2_dims: 
     overlaps `_supported` on purpose."""
     return (state_dims >= 1 and action_dims >= 1 and state_dims + action_dims <= 512 and fc1_dims >= 32
             and fc1_dims % 32 == 0 and fc1_dims <= 1024 and fc2_dims in (128, 256, 512) and fc3_dims in (128, 256))
+
+
+def grad_workspace_bytes(n_rows: int, state_dims: int, action_dims: int, fc1_dims: int, fc2_dims: int, fc3_dims: int,
+                         n_nets: int) -> int:
+    """`risvec_marl_critic_grad_workspace`, restated (the library is the authority: tests compare the two).  float32, with
+    npad = n_rows rounded up to 32: the input [S + A rounded up to 32][npad] once; per net the three activations and the
+    three deltas feature-major [F][npad], e and q - target [npad], and the tiles' largest deltas [3][npad / 32] rounded
+    up to 4 floats.  0: n_rows < 1, n_nets outside {1, 2} or a shape `risvec_marl_critic_grad` is not built for (its rule
+    is `risvec_marl_critic`'s)."""
+    if n_rows < 1 or n_nets not in (1, 2) or not _supported(state_dims, action_dims, fc1_dims, fc2_dims, fc3_dims):
+        return 0
+    r32 = lambda v: (v + 31) // 32 * 32                       # noqa: E731
+    npad = r32(n_rows)
+    per_net = 2 * (fc1_dims + fc2_dims + fc3_dims) * npad + 2 * npad + (3 * (npad // 32) + 3) // 4 * 4
+    return 4 * (r32(state_dims + action_dims) * npad + n_nets * per_net)
 
 
 def pack_marl_critic_weights(W1, W2, W3, wide: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -324,6 +341,100 @@ class BatchedTwinCritic(CriticNets):
         d8 = done.view(torch.uint8) if done.dtype == torch.bool else done
         self._launch(n, state_, action_, reward, d8, gamma, coef, logp_power, logp_intent, qs, out)
         return out
+
+    # ------------------------------------------------------------------ loss and gradients
+    #: with gemm=None, `loss_backward` runs the two device launches for row counts in this closed range and the library
+    #: path elsewhere; gemm="fused" runs them at every row count.  Measured at 64 / 256 / 4 096 rows, (40, 80) and (20, 24)
+    #: inputs (profiles/marl_critic_grad.json): faster than autograd in every round at each -- 6.5x / 6.1x / 2.9x at
+    #: (40, 80) with both weight streams rebuilt first.  The device time grows with the rows and nothing beyond 4 096 was
+    #: measured, so the default ends there.
+    GRAD_AUTO_ROWS = (1, 4096)
+
+    def alloc_grads(self) -> list:
+        """Per net, 8 zeroed float32 tensors shaped like the weights, in `state_dict()` order (fc1.weight, fc1.bias, ..,
+        q.weight, q.bias): nested like `BatchedAdam`'s groups, so `optimizer.step(grads=grads)` takes them as they are."""
+        return [[torch.zeros_like(getattr(net, a)) for a in _Net._WEIGHTS] for net in self.nets]
+
+    def _grad_device(self, n: int) -> bool:
+        if self.gemm != "fused":
+            return False
+        return not getattr(self, "_gemm_auto", False) or self.GRAD_AUTO_ROWS[0] <= n <= self.GRAD_AUTO_ROWS[1]
+
+    def _loss_args(self, state, action, target, grads, q, loss, what: str):
+        n, dev = self._rows(state, action), self.device
+        if not (is_f32(target, dev, (n,)) or is_f32(target, dev, (n, 1))):
+            raise ValueError("%s: target must be a contiguous float32 tensor of shape (%d,) or (%d, 1) on %s (it is read in "
+                             "place)" % (what, n, n, dev))
+        if target.requires_grad:
+            raise ValueError("%s: target is a constant; detach it" % what)
+        grads = self.alloc_grads() if grads is None else check_grads(grads, self.nets, what, dev)
+        qs = self._q_outs(q, n, what + ": q")
+        if qs is None:
+            qs = tuple(torch.empty(n, 1, device=dev) for _ in range(self.n_nets))
+        return n, grads, qs, out_f32(loss, (1,), what + ": loss", dev)
+
+    def loss_backward(self, state: torch.Tensor, action: torch.Tensor, target: torch.Tensor, grads=None, q=None, loss=None,
+                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`global_sac_critic.py:355-363` for these (online) critics without an autograd graph: loss = sum_c
+        mse_loss(Q_c(state, action), target) and its gradient with respect to every weight, in two launches
+        (`risvec_marl_critic_grad`) after the stale weight streams were rebuilt.  -> loss [1] on the device, no
+        synchronisation.  `grads` (default: new tensors from `alloc_grads`, kept as `last_grads`) are
+        OVERWRITTEN, the state after `zero_grad(set_to_none=True)` and one `backward()`; `q`: caller-owned [n, 1]
+        tensors that receive Q_c; `loss`: a caller-owned [1] tensor; `workspace`: a uint8 tensor of at least
+        `risvec_marl_critic_grad_workspace` bytes (default: one cached on this object and grown on demand).  target [n] or
+        [n, 1] float32 is a constant.  Everything is read in place, and what would have to be copied is refused.
+        gemm="library", gemm="wide" and -- with gemm=None -- row counts outside `GRAD_AUTO_ROWS` run
+        `loss_backward_torch` into the same buffers."""
+        what = "loss_backward"
+        n, grads, qs, loss = self._loss_args(state, action, target, grads, q, loss, what)
+        if not self._grad_device(n):
+            return self._loss_backward_torch(n, state, action, target, grads, qs, loss)
+        lib, dev = N.load(), self.device
+        need = int(lib.risvec_marl_critic_grad_workspace(n, *self._dims, self.n_nets))
+        if workspace is None:
+            cached = getattr(self, "_grad_workspace", None)
+            if cached is None or cached.numel() < need:
+                cached = self._grad_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = cached
+        else:
+            workspace = pack_workspace(workspace, need, what, dev)
+        nets, outs = grad_tables(self.n_nets, self.nets, self._fused_weights(), grads)
+        N.check(lib.risvec_marl_critic_grad(
+            n, *self._dims, self.n_nets, C.cast(nets, C.c_void_p), C.cast(outs, C.c_void_p), state.data_ptr(), action.data_ptr(),
+            target.data_ptr(), qs[0].data_ptr(), qs[1].data_ptr() if self.n_nets == 2 else None, loss.data_ptr(),
+            workspace.data_ptr(), workspace.numel(), N.stream(dev)))
+        self.last_grads = grads
+        return loss
+
+    def loss_backward_torch(self, state: torch.Tensor, action: torch.Tensor, target: torch.Tensor, grads=None, q=None,
+                            loss=None) -> torch.Tensor:
+        """`loss_backward` through autograd and library kernels (torch.cat, linear, relu, mse_loss, backward): the fallback
+        and the comparator.  The same arguments, checks and outputs."""
+        n, grads, qs, loss = self._loss_args(state, action, target, grads, q, loss, "loss_backward_torch")
+        return self._loss_backward_torch(n, state, action, target, grads, qs, loss)
+
+    def _loss_backward_torch(self, n, state, action, target, grads, qs, loss) -> torch.Tensor:
+        F = torch.nn.functional
+        x = torch.cat([state.view(n, self.state_dims), action.view(n, self.action_dims)], dim=1)
+        y = target.view(n)
+        leaves, total = [], None
+        with torch.enable_grad():
+            for net, qo in zip(self.nets, qs):
+                w = [getattr(net, a).detach().requires_grad_(True) for a in _Net._WEIGHTS]       # the same storage
+                h = torch.relu(F.linear(x, w[0], w[1]))
+                h = torch.relu(F.linear(h, w[2], w[3]))
+                h = torch.relu(F.linear(h, w[4], w[5]))
+                qv = F.linear(h, w[6], w[7])
+                qo.copy_(qv.detach())
+                term = F.mse_loss(qv.view(n), y)
+                total = term if total is None else total + term
+                leaves += w
+            got = torch.autograd.grad(total, leaves)
+        for t, g in zip((t for gs in grads for t in gs), got):
+            t.copy_(g)
+        loss.copy_(total.detach().view(1))
+        self.last_grads = grads
+        return loss
 
     def q_torch(self, state: torch.Tensor, action: torch.Tensor) -> tuple:
         x = torch.cat([state, action], dim=1)
