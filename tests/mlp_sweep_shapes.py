@@ -32,8 +32,14 @@ MARL_CRITIC = (
          "NG = 32; s_h sized by fc1; 148 480 bytes of dynamic LDS (the > 64 KiB attribute path)"),
     Case((33, 46, 992, 512, 128), "k_marl_critic<4,1>",
          "NG = 31: wavefront 3 owns one group fewer; KS = 5: groups end inside a prefetch round of kAhead"),
+    Case((24, 40, 96, 256, 256), "k_marl_critic<2,2>",
+         "S + A = 64: KS = 4 = kAhead exactly, every fc1 prefetch slot filled once and none clamped before the last round; "
+         "NG = 3: wavefront 3 owns no fc1 group"),
 )
-#: (index into MARL_CRITIC, n_nets): every case as a twin, the smallest and the largest as one net too
+#: (index into MARL_CRITIC, n_nets): every case as a twin, the smallest and the largest as one net too.  The table holds five
+#: of the six instantiations; <4,2> is asserted at the driver's shape by test_marl_critic_hip.py.  (That file's SMALL shape
+#: selects <2,2> as well, but nothing there asserts which kernel ran.)  `BatchedTwinCritic.loss_backward` is swept over the
+#: same runs (tests/test_marl_critic_grad_sweep_hip.py; the edges only the backward has are named there).
 MARL_CRITIC_RUNS = tuple((i, 2) for i in range(len(MARL_CRITIC))) + ((0, 1), (4, 1))
 
 # ---------------------------------------------------------------------------------------------------------------------

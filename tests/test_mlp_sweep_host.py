@@ -75,16 +75,27 @@ def test_marl_table_names_the_instantiation_and_the_edges():
         assert case.kernel == "k_marl_critic<%d,%d>" % (g.mt2, g.mt3), case
         assert lib.risvec_marl_critic_stream_bytes(*case.dims) == g.rows * 1024
         seen.add((g.mt2, g.mt3))
-    # with <1,1> (the fixtures), <2,2> and <4,2> (test_marl_critic_hip.py: SMALL, DRIVER) all six are run
-    assert seen == {(1, 1), (4, 1), (1, 2), (2, 1)}
-    assert seen | {(1, 1), (2, 2), (4, 2)} == {(a, b) for a in (1, 2, 4) for b in (1, 2)}
+    # with <4,2> (test_marl_critic_hip.py: DRIVER) all six are run
+    assert seen == {(1, 1), (4, 1), (1, 2), (2, 1), (2, 2)}
+    assert seen | {(4, 2)} == {(a, b) for a in (1, 2, 4) for b in (1, 2)} and (4, 2) not in seen
     geom = [MC.marl_critic_geom(*c.dims) for c in SW.MARL_CRITIC]
-    assert [(g.ks, g.ng) for g in geom] == [(1, 1), (1, 1), (2, 2), (8, 5), (8, 32), (5, 31)]
-    assert [c.dims[0] + c.dims[1] for c in SW.MARL_CRITIC] == [2, 16, 17, 128, 128, 79]
+    assert [(g.ks, g.ng) for g in geom] == [(1, 1), (1, 1), (2, 2), (8, 5), (8, 32), (5, 31), (4, 3)]
+    assert [c.dims[0] + c.dims[1] for c in SW.MARL_CRITIC] == [2, 16, 17, 128, 128, 79, 64]
     lds = [(g.ks + max(2 * g.ng, 8 * g.mt2)) * 2048 + 2 * 4 * 32 * 4 for g in geom]
     assert lds[4] == 148480 and lds[5] > 64 * 1024 and all(v <= 160 * 1024 for v in lds)
     assert 2 * geom[1].ng < 8 * geom[1].mt2 and 2 * geom[4].ng > 8 * geom[4].mt2      # what sizes s_h
-    assert sorted(SW.MARL_CRITIC_RUNS) == sorted([(i, 2) for i in range(6)] + [(0, 1), (4, 1)])
+    assert sorted(SW.MARL_CRITIC_RUNS) == sorted([(i, 2) for i in range(7)] + [(0, 1), (4, 1)])
+    # what the backward adds at the same shapes (tests/test_marl_critic_grad_sweep_hip.py): s_h = max(2 NG, K3 + K4) k-steps, the LDS
+    # of the row launch, XF = S + A rounded up to 32 and the live columns of the last column tile of d fc1.weight
+    from tests.test_marl_critic_grad_sweep_hip import BACKWARD_EDGE
+    assert list(BACKWARD_EDGE) == [c.dims for c in SW.MARL_CRITIC]
+    glds = [(g.ks + max(2 * g.ng, 8 * g.mt2 + 8 * g.mt3)) * 2048 + 2 * 4 * 32 * 4 for g in geom]
+    assert glds[4] == 148480 and all(v <= 160 * 1024 for v in glds)
+    assert [2 * g.ng > 8 * g.mt2 + 8 * g.mt3 for g in geom] == [False, False, False, False, True, True, False]
+    xf = [(c.dims[0] + c.dims[1] + 31) // 32 * 32 for c in SW.MARL_CRITIC]
+    assert xf == [32, 32, 32, 128, 128, 96, 64]
+    assert [c.dims[0] + c.dims[1] - (x - 32) for c, x in zip(SW.MARL_CRITIC, xf)] == [2, 16, 17, 32, 32, 15, 32]
+    assert {(g.mt2, g.mt3) for g in geom} | {(4, 2)} == {(a, b) for a in (1, 2, 4) for b in (1, 2)}   # <4,2>: test_marl_critic_grad_hip.py
 
 
 def test_sarl_critic_table_names_the_instantiation_and_the_edges():
