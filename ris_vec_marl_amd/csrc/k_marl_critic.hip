@@ -20,9 +20,10 @@
 // and every wavefront reads them back as B operands with one ds_read_b128 per fragment.  The workgroup walks the nets
 // one after the other, keeps q_1 in its s_red slot and finishes with the epilogue.
 //
-// The net walk (the fc1 group walk, fc2, fc3, the q dot product, the s_red reduction) and the input-fragment store are
-// risvec_critic_walk.hpp's, instantiated here and by k_local_critics.hip.  k_marl_critic_wide, further down, is the same
-// launch for inputs of up to 512 floats: fc1 walks the input in chunks.
+// The input staging and the net walk (the fc1 group walk, fc2, fc3, the q dot product, the s_red reduction) are
+// risvec_critic_walk.hpp's; this file adds the arguments, the epilogue and the launchers.  k_marl_critic_wide, further
+// down, is the same launch for inputs of up to 512 floats: fc1 walks the input in chunks, its own way, between the same
+// staging, tail (marl_run_tail) and epilogue.
 //
 // Every barrier sits under wave-uniform control flow: all loop bounds and the net count come from kernel arguments,
 // template parameters and the wavefront index.  Rows at or beyond n_rows are computed on row 0's input and never stored.
@@ -52,115 +53,8 @@ struct MarlCriticArgs {
     float* y;                      // [n_rows] or NULL
 };
 
-template <int MT2, int MT3>
-__global__ void __launch_bounds__(kMcBlock)
-k_marl_critic(MarlCriticArgs A) {
-    constexpr int K3 = 8 * MT2;                               // fc3 k-steps = fc2 / 16
-    extern __shared__ uint4 s_mem[];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int KS = A.KS, NG = A.NG;
-    uint4* s_in = s_mem;                                      // [KS][2][64]
-    uint4* s_h = s_mem + KS * 2 * kWave;                      // [max(2 NG, K3)][2][64]
-    const int hsteps = max(2 * NG, K3);
-    float* s_red = reinterpret_cast<float*>(s_h + hsteps * 2 * kWave);   // [kRedSlots][4][32]
-    const MarlLayout L = marl_layout(KS, NG, MT2, MT3);
-    const long long e0 = (long long)blockIdx.x * 32;
-
-    // ---- the input as split B fragments: k-step s, lane (r, h) holds x[16 s + 8 h + j], j < 8; x = [state | action | 0 ..]
-    {
-        const int S = A.S, W = A.S + A.NA;
-        for (int idx = tid; idx < KS * kWave; idx += kMcBlock) {
-            const int s = idx >> 6, l = idx & 63, rr = l & 31, hh = l >> 5;
-            const long long row = e0 + rr < A.n_rows ? e0 + rr : 0;
-            const float* ps = A.state + row * S;
-            const float* pa = A.action + row * A.NA;
-            f32x8_t v;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = 16 * s + 8 * hh + j;
-                v[j] = k < S ? ps[k] : (k < W ? pa[k - S] : 0.0f);
-            }
-            put_input(s_in, s, l, v);
-        }
-    }
-    __syncthreads();
-
-    // the net walk of risvec_critic_walk.hpp; called under wave-uniform control flow, ends on a barrier
-    auto run_net = [&](const MarlNetPtrs& P, int slot) { marl_run_net<MT2, MT3>(P, slot, s_in, s_h, s_red, L, KS, NG, wave, lane); };
-    run_net(A.net[0], 0);
-    const bool twin = A.n_nets == 2;                          // a kernel argument: uniform over the grid
-    if (twin) run_net(A.net[1], 1);
-
-    if (wave == 0 && h == 0) {
-        const long long e = e0 + r;
-        if (e < A.n_rows) {
-            auto red = [&](int slot) { return marl_red(s_red, slot, r); };
-            const float qv1 = red(0) + A.net[0].qb[0];
-            float m = qv1;
-            if (A.q1) A.q1[e] = qv1;
-            if (twin) {
-                const float qv2 = red(1) + A.net[1].qb[0];
-                if (A.q2) A.q2[e] = qv2;
-                m = fminf(qv1, qv2);
-            }
-            if (A.y) {
-                const float rw = A.reward[e];
-                float t = m;
-                if (A.lp || A.li) {
-                    float ent = 0.0f;
-                    if (A.lp) ent = A.coef[0] * A.lp[e];
-                    if (A.li) ent = A.lp ? fmaf(A.coef[1], A.li[e], ent) : A.coef[1] * A.li[e];
-                    t = m - ent;
-                }
-                A.y[e] = A.done[e] ? rw : fmaf(A.gamma, t, rw);      // a select, as target[done] = rewards_g[done] is
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// k_marl_critic_wide: the same launch for inputs that do not fit in LDS beside the activations (16 vehicles: 80 + 288
-// inputs = 23 k-steps).  fc1 walks the input in CHUNKS of kWideChunk k-steps: s_in holds one chunk, and a wavefront keeps
-// the accumulators of ALL its fc1 groups (at most kWideGroups = 1024 / 32 / 4, 16 registers each) across the chunks.
-// Per net and chunk: stage the chunk (zero beyond S + A; rows at or beyond n_rows read row 0), barrier, every wavefront
-// runs its groups wave, wave + 4, .. over the chunk's k-steps, barrier before the next chunk overwrites s_in.  Within a
-// group the k-steps are added in ascending order into that group's one accumulator, as k_marl_critic adds them: on one
-// chunk, and wherever the weights beyond the first chunk are zero, the two kernels give the same bits.  After the last
-// chunk bias, ReLU and the split fragments of every group go to s_h; from there on the walk is marl_run_tail and the
-// epilogue.  Net 2 stages the input again (s_in held net 1's last chunk).
-//
-// The accumulators are indexed statically (an unrolled loop over kWideGroups slots under the wave-uniform guard gi <
-// ngw): a run-time index would send them to scratch.  The weight prefetch keeps kAhead fragments in flight and walks
-// (chunk, group, k-step) in the order the MFMAs do; so that a fragment's register slot is static too, both walk a
-// group's k-steps of a chunk in blocks of kAhead positions, and a position beyond the chunk's last k-step neither loads
-// nor multiplies.  The prefetch stays on the last position once it has reached it.
-//
-// The staging and the epilogue below RESTATE k_marl_critic's, and marl_run_tail (risvec_critic_walk.hpp) restates the
-// second half of marl_run_net: having k_marl_critic call them changes its register counts.  Keep them in step.
-constexpr int kWideChunk = 8;        // k-steps of the input that s_in holds
-constexpr int kWideGroups = 8;       // fc1 groups a wavefront owns at most: fc1 <= 1024
-
-// The split B fragments of k-steps [s0, s0 + ns) of the tile's input -> s_in[0 .. ns): k-step s, lane (r, h) holds
-// x[16 s + 8 h + j], j < 8; x = [state | action | 0 ..].  k_marl_critic's staging with a first k-step.
-__device__ __forceinline__ void marl_stage_input(const MarlCriticArgs& A, uint4* s_in, long long e0, int s0, int ns, int tid) {
-    const int S = A.S, W = A.S + A.NA;
-    for (int idx = tid; idx < ns * kWave; idx += kMcBlock) {
-        const int s = idx >> 6, l = idx & 63, rr = l & 31, hh = l >> 5;
-        const long long row = e0 + rr < A.n_rows ? e0 + rr : 0;
-        const float* ps = A.state + row * S;
-        const float* pa = A.action + row * A.NA;
-        f32x8_t v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int k = 16 * (s0 + s) + 8 * hh + j;
-            v[j] = k < S ? ps[k] : (k < W ? pa[k - S] : 0.0f);
-        }
-        put_input(s_in, s, l, v);
-    }
-}
-
 // The minimum, the entropy term and the target of the tile's rows, from the q partial sums in s_red (after the last net's
-// closing barrier): k_marl_critic's epilogue, statement for statement.
+// closing barrier)
 __device__ __forceinline__ void marl_epilogue(const MarlCriticArgs& A, const float* s_red, long long e0, bool twin, int wave, int lane) {
     const int r = lane & 31, h = lane >> 5;
     if (wave == 0 && h == 0) {
@@ -192,6 +86,50 @@ __device__ __forceinline__ void marl_epilogue(const MarlCriticArgs& A, const flo
 
 template <int MT2, int MT3>
 __global__ void __launch_bounds__(kMcBlock)
+k_marl_critic(MarlCriticArgs A) {
+    constexpr int K3 = 8 * MT2;                               // fc3 k-steps = fc2 / 16
+    extern __shared__ uint4 s_mem[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int KS = A.KS, NG = A.NG;
+    uint4* s_in = s_mem;                                      // [KS][2][64]
+    uint4* s_h = s_mem + KS * 2 * kWave;                      // [max(2 NG, K3)][2][64]
+    const int hsteps = max(2 * NG, K3);
+    float* s_red = reinterpret_cast<float*>(s_h + hsteps * 2 * kWave);   // [kRedSlots][4][32]
+    const MarlLayout L = marl_layout(KS, NG, MT2, MT3);
+    const long long e0 = (long long)blockIdx.x * 32;
+
+    marl_stage_input(A.state, A.action, A.S, A.NA, A.n_rows, s_in, e0, 0, KS, tid);
+    __syncthreads();
+
+    // the net walk of risvec_critic_walk.hpp; called under wave-uniform control flow, ends on a barrier
+    auto run_net = [&](const MarlNetPtrs& P, int slot) { marl_run_net<MT2, MT3>(P, slot, s_in, s_h, s_red, L, KS, NG, wave, lane); };
+    run_net(A.net[0], 0);
+    const bool twin = A.n_nets == 2;                          // a kernel argument: uniform over the grid
+    if (twin) run_net(A.net[1], 1);
+    marl_epilogue(A, s_red, e0, twin, wave, lane);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_marl_critic_wide: the same launch for inputs that do not fit in LDS beside the activations (16 vehicles: 80 + 288
+// inputs = 23 k-steps).  fc1 walks the input in CHUNKS of kWideChunk k-steps: s_in holds one chunk, and a wavefront keeps
+// the accumulators of ALL its fc1 groups (at most kWideGroups = 1024 / 32 / 4, 16 registers each) across the chunks.
+// Per net and chunk: stage the chunk (zero beyond S + A; rows at or beyond n_rows read row 0), barrier, every wavefront
+// runs its groups wave, wave + 4, .. over the chunk's k-steps, barrier before the next chunk overwrites s_in.  Within a
+// group the k-steps are added in ascending order into that group's one accumulator, as k_marl_critic adds them: on one
+// chunk, and wherever the weights beyond the first chunk are zero, the two kernels give the same bits.  After the last
+// chunk bias, ReLU and the split fragments of every group go to s_h; from there on the walk is marl_run_tail and the
+// epilogue.  Net 2 stages the input again (s_in held net 1's last chunk).
+//
+// The accumulators are indexed statically (an unrolled loop over kWideGroups slots under the wave-uniform guard gi <
+// ngw): a run-time index would send them to scratch.  The weight prefetch keeps kAhead fragments in flight and walks
+// (chunk, group, k-step) in the order the MFMAs do; so that a fragment's register slot is static too, both walk a
+// group's k-steps of a chunk in blocks of kAhead positions, and a position beyond the chunk's last k-step neither loads
+// nor multiplies.  The prefetch stays on the last position once it has reached it.
+constexpr int kWideChunk = 8;        // k-steps of the input that s_in holds
+constexpr int kWideGroups = 8;       // fc1 groups a wavefront owns at most: fc1 <= 1024
+
+template <int MT2, int MT3>
+__global__ void __launch_bounds__(kMcBlock)
 k_marl_critic_wide(MarlCriticArgs A) {
     constexpr int K3 = 8 * MT2;                               // fc3 k-steps = fc2 / 16
     extern __shared__ uint4 s_mem[];
@@ -204,7 +142,7 @@ k_marl_critic_wide(MarlCriticArgs A) {
     const MarlLayout L = marl_layout(KS, NG, MT2, MT3);
     const long long e0 = (long long)blockIdx.x * 32;
     const int nch = (KS + kWideChunk - 1) / kWideChunk;       // chunks: a kernel argument's, uniform over the grid
-    const int ngw = NG > wave ? (NG - wave + kMcWaves - 1) / kMcWaves : 0;      // this wavefront's fc1 groups, <= kWideGroups
+    const int ngw = NG > wave ? (NG - wave + kCriticWaves - 1) / kCriticWaves : 0;      // this wavefront's fc1 groups, <= kWideGroups
 
     // called under wave-uniform control flow; ends on a barrier
     auto run_net = [&](const MarlNetPtrs& P, int slot) {
@@ -215,7 +153,7 @@ k_marl_critic_wide(MarlCriticArgs A) {
         int fc = 0, fgi = 0, fs = 0, fcs = min(kWideChunk, KS);
         auto fetch = [&](int i) {
             if (fs < fcs) {
-                const uint4* p = w1 + (size_t)((wave + kMcWaves * fgi) * KS + kWideChunk * fc + fs) * (2 * kWave);
+                const uint4* p = w1 + (size_t)((wave + kCriticWaves * fgi) * KS + kWideChunk * fc + fs) * (2 * kWave);
                 ah[i] = ld_frag(p);
                 al[i] = ld_frag(p + kWave);
             }
@@ -236,7 +174,7 @@ k_marl_critic_wide(MarlCriticArgs A) {
         for (int c = 0; c < nch; ++c) {
             const int cs = min(kWideChunk, KS - kWideChunk * c);
             if (c > 0) __syncthreads();                       // every wavefront is past the last chunk's MFMAs: s_in is free
-            marl_stage_input(A, s_in, e0, kWideChunk * c, cs, tid);
+            marl_stage_input(A.state, A.action, A.S, A.NA, A.n_rows, s_in, e0, kWideChunk * c, cs, tid);
             __syncthreads();
             if (ngw > 0) {                                    // wave-uniform; no barrier inside
 #pragma unroll
@@ -262,7 +200,7 @@ k_marl_critic_wide(MarlCriticArgs A) {
 #pragma unroll
             for (int gi = 0; gi < kWideGroups; ++gi) {
                 if (gi < ngw) {
-                    const int g = wave + kMcWaves * gi;
+                    const int g = wave + kCriticWaves * gi;
                     put_tile(s_h, g, bias_relu(d[gi], u1, tile_of(P.b1, 32 * g, h)), lane);
                 }
             }
@@ -313,7 +251,7 @@ bool marl_critic_supported(int S, int A, int F1, int F2, int F3) {
 // Deliberately overlaps the rule above: on a shape both cover, the two kernels are compared bit for bit.  fc1 <= 1024
 // is kWideGroups groups per wavefront.
 bool marl_critic_wide_supported(int S, int A, int F1, int F2, int F3) {
-    static_assert(kWideGroups * kMcWaves * 32 == 1024, "a wavefront holds the accumulators of all its fc1 groups");
+    static_assert(kWideGroups * kCriticWaves * 32 == 1024, "a wavefront holds the accumulators of all its fc1 groups");
     return S >= 1 && A >= 1 && S <= 511 && A <= 511 && S + A <= 512 && fc_supported(F1, F2, F3);
 }
 

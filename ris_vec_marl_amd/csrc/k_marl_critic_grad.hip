@@ -9,9 +9,10 @@
 // The gradients are overwritten, never accumulated.  Orientation, precision and register order are those of
 // risvec_mfma.hpp (read its header); the forward is the walk of risvec_critic_walk.hpp on the packed weight stream.
 //
-// 1  k_marl_critic_grad_rows<MT2, MT3>: grid (32-row tiles, nets), four wavefronts per tile.  The forward walk is
-//    marl_run_net's, RESTATED here statement for statement because every activation tile also goes to the workspace as it
-//    is produced (keep the two in step).  Then, in the same workgroup:
+// 1  k_marl_critic_grad_rows<MT2, MT3>: grid (32-row tiles, nets), four wavefronts per tile.  The forward is the
+//    shared walk (marl_stage_input, critic_fc1_walk, critic_fc2) with callbacks that also send every activation tile to the
+//    workspace as it is produced; only the fc3 block is this kernel's own, because d3 is formed in its registers.  Then, in
+//    the same workgroup:
 //      d3 is formed in registers (the fc3 tiles are still there) and goes to LDS as B fragments, exactly as put_tile
 //         leaves a layer's output for the next MFMA: registers 8u .. 8u+7 = k-step 2 tile + u;
 //      d2 = W3^T d3: wavefront w owns the fc2 tiles it owned in the forward, so the lane that wrote h2[f][row] applies its
@@ -156,101 +157,38 @@ k_marl_critic_grad_rows(GradRowArgs A) {
     uint4* s_h = s_mem + KS * 2 * kWave;                      // [max(2 NG, K3 + K4)][2][64]
     const int hsteps = max(2 * NG, K3 + K4);
     float* s_red = reinterpret_cast<float*>(s_h + hsteps * 2 * kWave);   // [kRedSlots][4][32]
-    float* s_max = s_red + kMcWaves * 32;                     // slot 1 of s_red: [3][4] maxima
+    float* s_max = s_red + kCriticWaves * 32;                     // slot 1 of s_red: [3][4] maxima
     uint4* s_d3 = s_h + K3 * 2 * kWave;                       // the d3 fragments, beside h2's
     const MarlLayout L = marl_layout(KS, NG, MT2, MT3);
     const long long e0 = (long long)blockIdx.x * 32, npad = A.npad, col = e0 + r;
     const int ntiles = (int)(npad / 32);
 
-    // ---- the input as split B fragments (k_marl_critic's staging), and feature-major to the workspace
-    {
+    // ---- the input as split B fragments, and feature-major to the workspace
+    marl_stage_input(A.state, A.action, A.S, A.NA, A.n_rows, s_in, e0, 0, KS, tid);
+    if (netc == 0) {
         const int S = A.S, W = A.S + A.NA;
-        for (int idx = tid; idx < KS * kWave; idx += kMcBlock) {
-            const int s = idx >> 6, l = idx & 63, rr = l & 31, hh = l >> 5;
+        for (int idx = tid; idx < A.XF * 32; idx += kMcBlock) {
+            const int k = idx >> 5, rr = idx & 31;
             const long long row = e0 + rr < A.n_rows ? e0 + rr : 0;
-            const float* ps = A.state + row * S;
-            const float* pa = A.action + row * A.NA;
-            f32x8_t v;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = 16 * s + 8 * hh + j;
-                v[j] = k < S ? ps[k] : (k < W ? pa[k - S] : 0.0f);
-            }
-            put_input(s_in, s, l, v);
-        }
-        if (netc == 0) {
-            for (int idx = tid; idx < A.XF * 32; idx += kMcBlock) {
-                const int k = idx >> 5, rr = idx & 31;
-                const long long row = e0 + rr < A.n_rows ? e0 + rr : 0;
-                A.x[(size_t)k * npad + e0 + rr] = k < S ? A.state[row * S + k] : (k < W ? A.action[row * A.NA + (k - S)] : 0.0f);
-            }
+            A.x[(size_t)k * npad + e0 + rr] = k < S ? A.state[row * S + k] : (k < W ? A.action[row * A.NA + (k - S)] : 0.0f);
         }
     }
     __syncthreads();
 
     const float u1 = P.scales[0], u2 = P.scales[1], u3 = P.scales[2];
-    // ---- fc1 (marl_run_net's group walk): bias, ReLU, the split fragments to LDS and the tile to the workspace
-    const int ngw = NG > wave ? (NG - wave + kMcWaves - 1) / kMcWaves : 0;
-    if (ngw > 0) {                                            // wave-uniform; no barrier inside
-        const int nst = ngw * KS;
-        const uint4* w1 = P.ws + L.fc1 * kWave + lane;
-        half8_t ah[kAhead], al[kAhead];
-        int fg = wave, fs = 0;                                // (group, k-step) of the next fetch
-        auto fetch = [&](int i) {
-            const uint4* p = w1 + (size_t)(fg * KS + fs) * (2 * kWave);
-            ah[i] = ld_frag(p);
-            al[i] = ld_frag(p + kWave);
-            if (fs + 1 < KS) ++fs;
-            else if (fg + kMcWaves < NG) { fg += kMcWaves; fs = 0; }    // else: stay on the last fragment
-        };
-#pragma unroll
-        for (int i = 0; i < kAhead; ++i) fetch(i);
-        f32x16_t d;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) d[q] = 0.0f;
-        int g = wave, s = 0;
-        for (int i0 = 0; i0 < nst; i0 += kAhead) {
-#pragma unroll
-            for (int i = 0; i < kAhead; ++i) {
-                if (i0 + i < nst) {
-                    const half8_t bh = ld_frag(s_in + (2 * s) * kWave + lane), bl = ld_frag(s_in + (2 * s + 1) * kWave + lane);
-                    d = mfma3(ah[i], al[i], bh, bl, d);
-                    fetch(i);
-                    if (++s == KS) {
-                        const f32x16_t y = bias_relu(d, u1, tile_of(P.b1, 32 * g, h));
-                        put_tile(s_h, g, y, lane);
-                        store_tile(G.h1, 32 * g, y, npad, col, h);
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) d[q] = 0.0f;
-                        s = 0;
-                        g += kMcWaves;
-                    }
-                }
-            }
-        }
-    }
+    // ---- fc1: bias, ReLU, the split fragments to LDS and the tile to the workspace
+    critic_fc1_walk(P.ws + L.fc1 * kWave, s_in, KS, NG, wave, lane, [&](int g, const f32x16_t& d) {
+        const f32x16_t y = bias_relu(d, u1, tile_of(P.b1, 32 * g, h));
+        put_tile(s_h, g, y, lane);
+        store_tile(G.h1, 32 * g, y, npad, col, h);
+    });
     __syncthreads();
 
-    // ---- fc2: output tiles [wave MT2, (wave + 1) MT2) over all 2 NG k-steps
-    {
-        f32x16_t acc[MT2];
-#pragma unroll
-        for (int m = 0; m < MT2; ++m)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[m][q] = 0.0f;
-        gemm_tiles<MT2>(acc, P.ws + (L.fc2 + (long long)wave * (2 * NG) * MT2 * 2) * kWave, s_h, 2 * NG, lane);
-        __syncthreads();                                      // every wavefront is past its fc2 MFMAs: s_h is free
-#pragma unroll
-        for (int m = 0; m < MT2; ++m) {
-            const int t = wave * MT2 + m;
-            const f32x16_t y = bias_relu(acc[m], u2, tile_of(P.b2, 32 * t, h));
-            put_tile(s_h, t, y, lane);
-            store_tile(G.h2, 32 * t, y, npad, col, h);
-        }
-    }
-    __syncthreads();
+    // ---- fc2, each output tile also to the workspace
+    critic_fc2<MT2>(P, s_h, L, NG, wave, lane, u2, [&](int t, const f32x16_t& y) { store_tile(G.h2, 32 * t, y, npad, col, h); });
 
-    // ---- fc3 + ReLU, the q dot product, and d3 = e wq [h3 > 0] in the registers of the fc3 tiles
+    // ---- fc3 + ReLU, the q dot product, and d3 = e wq [h3 > 0] in the registers of the fc3 tiles: critic_fc3_q with the
+    // store of h3 and the mask of d3 in its loop, so it stays this kernel's own
     f32x16_t d3[MT3];
     {
         f32x16_t a3[MT3];
@@ -339,7 +277,7 @@ k_marl_critic_grad_rows(GradRowArgs A) {
         // ---- d1 = (W2^T d2) [h1 > 0]: fc1 groups wave, wave + 4, ..
         const float back1 = u2 * ldexpf(1.0f, -s2);
         mx = 0.0f;
-        for (int g = wave; g < NG; g += kMcWaves) {
+        for (int g = wave; g < NG; g += kCriticWaves) {
             f32x16_t a1[1];
 #pragma unroll
             for (int q = 0; q < 16; ++q) a1[0][q] = 0.0f;
@@ -551,7 +489,7 @@ hipError_t launch_marl_critic_grad(long long n_rows, int S, int A, int F1, int F
     }
     note_kernel("k_marl_critic_grad_rows<%d,%d>x%d -> k_marl_critic_grad_weights", MT2, MT3, n_nets);
     const size_t lds = (size_t)(r.KS + std::max(2 * r.NG, 8 * MT2 + 8 * MT3)) * 2 * kWave * sizeof(uint4) +
-                       (size_t)kRedSlots * kMcWaves * 32 * sizeof(float);
+                       (size_t)kRedSlots * kCriticWaves * 32 * sizeof(float);
     hipError_t err = dispatch_mt2_mt3(F2, F3, [&](auto mt2, auto mt3) {
         return launch_dynamic_lds(k_marl_critic_grad_rows<decltype(mt2)::value, decltype(mt3)::value>, dim3((unsigned)ntiles, (unsigned)n_nets),
                                   dim3(kMcBlock), lds, st, r);

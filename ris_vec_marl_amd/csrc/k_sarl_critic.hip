@@ -20,9 +20,14 @@
 // pass: the raw pre-activation waits in the 64 bytes of LDS that its own split fragments replace after the variance
 // is known (lane-private, same bytes).
 //
+// The fc1 group walk (critic_fc1_walk, with the LayerNorm-1 statistics as its per-group callback), the input-fragment
+// store (put_input) and the s_red reduction (marl_red) are risvec_critic_walk.hpp's, shared with the multi-agent critic
+// kernels.  LayerNorm, the action branch and the s_red slot count (kSarlRedSlots) are this kernel's own.
+//
 // Every barrier sits under wave-uniform control flow: all loop bounds come from kernel arguments, template parameters
 // and the wavefront index.  Rows at or beyond n_rows are computed on row 0's input and never stored.  No global
 // address depends on loaded data; every weight prefetch index is clamped to the last fragment of its block.
+#include "risvec_critic_walk.hpp"
 #include "risvec_launch.hpp"
 #include "risvec_mfma.hpp"
 #include "risvec_step.hpp"
@@ -48,14 +53,13 @@ struct CriticArgs {
     float* y;                      // [n_rows] or NULL
 };
 
-constexpr int kCrBlock = 256;        // 4 wavefronts = 1 per SIMD, all on the same 32 rows
-constexpr int kCrWaves = kCriticWaves;
-constexpr int kRedSlots = 6;
+constexpr int kCrBlock = kMcBlock;   // the walk's workgroup: 4 wavefronts = 1 per SIMD, all on the same 32 rows
+constexpr int kSarlRedSlots = 6;     // s_red slots: three LayerNorms (variance; mean, variance; mean, variance) and q
 
 template <int MT2, int MT3>
 __global__ void __launch_bounds__(kCrBlock)
 k_sarl_critic(CriticArgs A) {
-    constexpr int F2 = 32 * MT2 * kCrWaves, F3 = 32 * MT3 * kCrWaves;
+    constexpr int F2 = 32 * MT2 * kCriticWaves, F3 = 32 * MT3 * kCriticWaves;
     constexpr int K3 = F2 / 16;                                // fc3 k-steps
     extern __shared__ uint4 s_mem[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -63,7 +67,7 @@ k_sarl_critic(CriticArgs A) {
     uint4* s_in = s_mem;                                      // [KS][2][64]
     uint4* s_h = s_mem + KS * 2 * kWave;                      // [max(KSA, 2 NG, K3)][2][64]
     const int hsteps = max(max(KSA, 2 * NG), K3);
-    float* s_red = reinterpret_cast<float*>(s_h + hsteps * 2 * kWave);   // [kRedSlots][4][32]
+    float* s_red = reinterpret_cast<float*>(s_h + hsteps * 2 * kWave);   // [kSarlRedSlots][4][32]
     const CriticLayout L = critic_layout(KS, KSA, NG, MT2, MT3);
     const long long e0 = (long long)blockIdx.x * 32;
     const float u1 = A.scales[0], u2 = A.scales[1], uav = A.scales[2], u3 = A.scales[3];
@@ -80,10 +84,7 @@ k_sarl_critic(CriticArgs A) {
                 const int k = 16 * s + 8 * hh + j;
                 v[j] = k < W ? p[k] : (one && k == W ? 1.0f : 0.0f);
             }
-            half8_t hi, lo;
-            split16(v, hi, lo);
-            dst[(2 * s) * kWave + l] = __builtin_bit_cast(uint4, hi);
-            dst[(2 * s + 1) * kWave + l] = __builtin_bit_cast(uint4, lo);
+            put_input(dst, s, l, v);
         }
     };
     stage_in(A.x, A.IN, KS, true, s_in);
@@ -99,63 +100,25 @@ k_sarl_critic(CriticArgs A) {
     gemm_tiles<MT2>(av, A.ws + (L.av + (long long)wave * KSA * MT2 * 2) * kWave, s_h, KSA, lane);
     __syncthreads();                                          // the action fragments are dead: s_h takes fc1
 
-    // ---- fc1, groups wave, wave + 4, .. (the group walk is the twin of k_marl_critic.hip's; keep the two in step): the
-    // scaled, centred pre-activation goes to LDS raw (float32, in the 64 bytes
-    // per lane that its split fragments will occupy), its squares into the LayerNorm-1 variance
-    const int ngw = NG > wave ? (NG - wave + kCrWaves - 1) / kCrWaves : 0;
+    // ---- fc1 (the group walk of risvec_critic_walk.hpp): the scaled, centred pre-activation goes to LDS raw (float32, in the
+    // 64 bytes per lane that its split fragments will occupy), its squares into the LayerNorm-1 variance
     auto own_slot = [&](int g, int c) { return s_h + ((2 * g) * 2 + c) * kWave + lane; };   // c < 4: (u, t) = (c >> 1, c & 1)
     float ss = 0.0f;
-    if (ngw > 0) {                                            // wave-uniform; no barrier inside
-        const int nst = ngw * KS;
-        const uint4* w1 = A.ws + L.fc1 * kWave + lane;
-        half8_t ah[kAhead], al[kAhead];
-        int fg = wave, fs = 0;                                // (group, k-step) of the next fetch
-        auto fetch = [&](int i) {
-            const uint4* p = w1 + (size_t)(fg * KS + fs) * (2 * kWave);
-            ah[i] = ld_frag(p);
-            al[i] = ld_frag(p + kWave);
-            if (fs + 1 < KS) ++fs;
-            else if (fg + kCrWaves < NG) { fg += kCrWaves; fs = 0; }    // else: stay on the last fragment
-        };
+    critic_fc1_walk(A.ws + L.fc1 * kWave, s_in, KS, NG, wave, lane, [&](int g, const f32x16_t& d) {
+        ss += sum16(d * d);
 #pragma unroll
-        for (int i = 0; i < kAhead; ++i) fetch(i);
-        f32x16_t d;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) d[q] = 0.0f;
-        int g = wave, s = 0;
-        for (int i0 = 0; i0 < nst; i0 += kAhead) {
-#pragma unroll
-            for (int i = 0; i < kAhead; ++i) {
-                if (i0 + i < nst) {
-                    const half8_t bh = ld_frag(s_in + (2 * s) * kWave + lane), bl = ld_frag(s_in + (2 * s + 1) * kWave + lane);
-                    d = mfma3(ah[i], al[i], bh, bl, d);
-                    fetch(i);
-                    if (++s == KS) {
-                        ss += sum16(d * d);
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            float4 v = make_float4(d[4 * c], d[4 * c + 1], d[4 * c + 2], d[4 * c + 3]);
-                            *reinterpret_cast<float4*>(own_slot(g, c)) = v;
-                        }
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) d[q] = 0.0f;
-                        s = 0;
-                        g += kCrWaves;
-                    }
-                }
-            }
+        for (int c = 0; c < 4; ++c) {
+            float4 v = make_float4(d[4 * c], d[4 * c + 1], d[4 * c + 2], d[4 * c + 3]);
+            *reinterpret_cast<float4*>(own_slot(g, c)) = v;
         }
-    }
+    });
     ss += __shfl_xor(ss, 32, kWave);
-    if (h == 0) s_red[(0 * kCrWaves + wave) * 32 + r] = ss;
+    if (h == 0) s_red[(0 * kCriticWaves + wave) * 32 + r] = ss;
     __syncthreads();
-    auto red = [&](int slot) {
-        const float* p = s_red + slot * kCrWaves * 32 + r;
-        return ((p[0] + p[32]) + p[64]) + p[96];
-    };
+    auto red = [&](int slot) { return marl_red(s_red, slot, r); };
     {
         const float k1 = rsqrtf((red(0) * u1) * u1 / (float)(32 * NG) + kLnEps) * u1;   // rstd, the weight scaling undone
-        for (int g = wave; g < NG; g += kCrWaves) {
+        for (int g = wave; g < NG; g += kCriticWaves) {
             f32x16_t d;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -187,7 +150,7 @@ k_sarl_critic(CriticArgs A) {
         }
         float s = sum16(vs);
         s += __shfl_xor(s, 32, kWave);
-        if (h == 0) s_red[(1 * kCrWaves + wave) * 32 + r] = s;
+        if (h == 0) s_red[(1 * kCriticWaves + wave) * 32 + r] = s;
         __syncthreads();                                      // every wavefront is past its fc2 MFMAs: s_h is free
         const float mean = red(1) * (1.0f / (float)F2);
         f32x16_t v2;
@@ -198,7 +161,7 @@ k_sarl_critic(CriticArgs A) {
         }
         float s2 = sum16(v2);
         s2 += __shfl_xor(s2, 32, kWave);
-        if (h == 0) s_red[(2 * kCrWaves + wave) * 32 + r] = s2;
+        if (h == 0) s_red[(2 * kCriticWaves + wave) * 32 + r] = s2;
         __syncthreads();
         const float rs = rsqrtf(red(2) * (1.0f / (float)F2) + kLnEps);
 #pragma unroll
@@ -229,7 +192,7 @@ k_sarl_critic(CriticArgs A) {
         }
         float s = sum16(vs);
         s += __shfl_xor(s, 32, kWave);
-        if (h == 0) s_red[(3 * kCrWaves + wave) * 32 + r] = s;
+        if (h == 0) s_red[(3 * kCriticWaves + wave) * 32 + r] = s;
         __syncthreads();
         const float mean = red(3) * (1.0f / (float)F3);
         f32x16_t v2;
@@ -240,7 +203,7 @@ k_sarl_critic(CriticArgs A) {
         }
         float s2 = sum16(v2);
         s2 += __shfl_xor(s2, 32, kWave);
-        if (h == 0) s_red[(4 * kCrWaves + wave) * 32 + r] = s2;
+        if (h == 0) s_red[(4 * kCriticWaves + wave) * 32 + r] = s2;
         __syncthreads();
         const float rs = rsqrtf(red(4) * (1.0f / (float)F3) + kLnEps);
         f32x16_t qs;
@@ -255,7 +218,7 @@ k_sarl_critic(CriticArgs A) {
         }
         float qp = sum16(qs);
         qp += __shfl_xor(qp, 32, kWave);
-        if (h == 0) s_red[(5 * kCrWaves + wave) * 32 + r] = qp;
+        if (h == 0) s_red[(5 * kCriticWaves + wave) * 32 + r] = qp;
         __syncthreads();
     }
     if (wave == 0 && h == 0) {
@@ -274,7 +237,7 @@ k_sarl_critic(CriticArgs A) {
 template <int MT2, int MT3>
 hipError_t launch_critic(const CriticArgs& a, hipStream_t st) {
     const int hsteps = std::max(std::max(a.KSA, 2 * a.NG), 8 * MT2);
-    const size_t lds = (size_t)(a.KS + hsteps) * 2 * kWave * sizeof(uint4) + (size_t)kRedSlots * kCrWaves * 32 * sizeof(float);
+    const size_t lds = (size_t)(a.KS + hsteps) * 2 * kWave * sizeof(uint4) + (size_t)kSarlRedSlots * kCriticWaves * 32 * sizeof(float);
     return launch_dynamic_lds(k_sarl_critic<MT2, MT3>, dim3((unsigned)((a.n_rows + 31) / 32)), dim3(kCrBlock), lds, st, a);
 }
 
