@@ -50,9 +50,17 @@
 #define RISVEC_GEN_STORES kStNonTemporal
 #endif
 
+// The row-per-lane members make the Philox arrival draw while the lane's loads are in flight, not behind the chains where
+// vector issue is the bound (gen_row_lane_form; EXPERIMENTS.md 2026-10-21).  RISVEC_GEN_EARLY=0 builds the library that
+// leaves the draw in step_pre (Makefile: gen_ab, e0).
+#ifndef RISVEC_GEN_EARLY
+#define RISVEC_GEN_EARLY 1
+#endif
+
 namespace risvec {
 
 using GenStores = StorePolicy<RISVEC_GEN_STORES>;
+constexpr bool kGenEarlyDraw = RISVEC_GEN_EARLY != 0;
 
 template <int V, int M>
 struct GenShape : PipeShape<V, M> {
@@ -475,7 +483,21 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
         theta_table_fill(s_ph[wave], lane);
         __builtin_amdgcn_wave_barrier();
     }
+    // step()'s inputs, and with them -- one scalar round trip -- the arguments the arrival draw reads.  The draw needs
+    // nothing from memory: issued here, behind the last request and in front of the wait for the first, it runs while all four
+    // wavefronts of the SIMD have nothing else to issue, instead of behind the chains where vector issue is the bound.  The
+    // empty asm pins the count here: neither the scheduler nor machine sinking may carry the draw down to its use.
+    RISVEC_ARGS_IN_ONE_TRIP("s"(A.action), "s"(A.data_buf), "s"(A.partner), "s"(A.arrivals), "s"(A.n_groups), "s"(A.mec_q),
+                            "s"(A.pl), "s"(A.flags), "s"(d.V), "s"(d.env_offset), "s"(A.seed), "s"(A.counter),
+                            "s"(KA.P.poisson_cdf[0]), "s"(KA.P.poisson_cdf[1]), "s"(KA.P.poisson_cdf[2]),
+                            "s"(KA.P.poisson_cdf[3]), "s"(KA.P.poisson_cdf[4]), "s"(KA.P.poisson_cdf[5]),
+                            "s"(KA.P.poisson_cdf[6]), "s"(KA.P.poisson_cdf[7]));
     const In in = Core::load(d, A, e_mine, v_mine, active);
+    int arr = 0;
+    if constexpr (kGenEarlyDraw) {
+        arr = Core::draw(d, KA.P, A, e_mine, v_mine);
+        asm volatile("" : "+v"(arr));
+    }
     Core::hold(in);
 
     // the env's w0 / w1 of float4 p, cmul(theta, b) as the reading lane p forms them: Q per lane, shared through s_w
@@ -531,7 +553,7 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
     const float2 img = row_tree<G>(leaf);
 
     const GenArgs<Core>& L = late_args<Core>();
-    Core::template run<VP, GenStores>(L.d, L.P, L.A, e_mine, v_mine, active, img, in);
+    Core::template run<VP, GenStores, kGenEarlyDraw>(L.d, L.P, L.A, e_mine, v_mine, active, img, in, arr);
 }
 
 // The shapes whose one-group member is the row-per-lane form: those that keep four wavefronts per SIMD (128 VGPRs) with it.

@@ -86,16 +86,20 @@ struct MarlCore {
     static __device__ __forceinline__ void hold(const In& in) {
         asm volatile("" ::"v"(in.a0), "v"(in.a1), "v"(in.B), "v"(in.Q0), "v"(in.pl), "v"(in.part), "v"(in.G), "v"(in.arr_in));
     }
-    template <int VP, class ST = StepStores>
+    // the lane's arrival count as step_pre draws it without injected arrivals; run<.., ARR_DRAWN = true> takes it back
+    static __device__ __forceinline__ int draw(const Dims& d, const Params& P, const Args& A, int e, int v) {
+        return draw_arrivals(d, P, A, e, v);
+    }
+    template <int VP, class ST = StepStores, bool ARR_DRAWN = false>
     static __device__ __forceinline__ void run(const Dims& d, const Params& P, const Args& A, int e, int v,
-                                               bool active, float2 img, const In& in) {
+                                               bool active, float2 img, const In& in, int arr_drawn = 0) {
         float g = 0.f;
         if (active) {
             const long long idx = (long long)e * d.V + v;
             g = gain_from_img(img, in.pl, A.h_d, idx);
             st_to<ST::reread>(A.gain[idx]) = g;
         }
-        step_core<VP, false, false, NoRing, ST>(d, P, A, e, v, active, g, in);
+        step_core<VP, false, false, NoRing, ST, ARR_DRAWN>(d, P, A, e, v, active, g, in, nullptr, nullptr, arr_drawn);
     }
 };
 
@@ -161,9 +165,12 @@ struct MarlRingCore {
 #pragma unroll
         for (int k = 0; k < VPC / 4; ++k) asm volatile("" ::"v"(in.r.mk[k]));
     }
-    template <int VP, class ST = StepStores>
+    static __device__ __forceinline__ int draw(const Dims& d, const Params& P, const Args& A, int e, int v) {
+        return draw_arrivals(d, P, A, e, v);
+    }
+    template <int VP, class ST = StepStores, bool ARR_DRAWN = false>
     static __device__ __forceinline__ void run(const Dims& d, const Params& P, const Args& A, int e, int v,
-                                               bool active, float2 img, const In& in) {
+                                               bool active, float2 img, const In& in, int arr_drawn = 0) {
         static_assert(VP == VPC, "ring core instantiated for another V");
         float g = 0.f;
         if (active) {
@@ -171,7 +178,7 @@ struct MarlRingCore {
             g = gain_from_img(img, in.s.pl, A.h_d, idx);
             st_to<ST::reread>(A.gain[idx]) = g;
         }
-        step_core<VP, false, false, RingIn<VPC>, ST>(d, P, A, e, v, active, g, in.s, nullptr, &in.r);
+        step_core<VP, false, false, RingIn<VPC>, ST, ARR_DRAWN>(d, P, A, e, v, active, g, in.s, nullptr, &in.r, arr_drawn);
     }
 };
 

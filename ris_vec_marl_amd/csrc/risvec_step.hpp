@@ -559,9 +559,19 @@ struct StepPre {
 // ARR_LATE (the T-step loop): the arrival draw is left to step_tail, at the place step() has it.  There the injected
 // arrivals are loaded under `if (A.arrivals)`, whose join costs an `s_waitcnt vmcnt(0)`: late in the step that is free,
 // at the top of the step it would wait for the next step's action prefetch every step (measured: +14 % per step).
-template <bool ARR_LATE = false>
+// The Philox arrival count of (env, vehicle) as step_pre / step_tail draw it below: a function of kernel arguments and the
+// lane's place alone, nothing from memory.  (The two keep their own copy of these lines: called through here, the table's
+// compares come out in another order and every kernel that runs step() compiles differently.)
+__device__ __forceinline__ int draw_arrivals(const Dims& d, const RisVecParams& P, const StepArgs& A, int e, int v) {
+    const uint4 x = philox4x32_10((uint32_t)(d.env_offset + e), (uint32_t)v, A.counter, kSiteArrivals, A.seed);
+    return poisson_from_u(u01(x.x), P.poisson_cdf);
+}
+
+// ARR_DRAWN: the caller made draw_arrivals() itself, earlier -- the row-per-lane GEN members, while their loads are in
+// flight -- and hands the count in as `arr_drawn`; injected arrivals still win.
+template <bool ARR_LATE = false, bool ARR_DRAWN = false>
 __device__ __forceinline__ StepPre step_pre(const Dims& d, const RisVecParams& P, const StepArgs& A, int e, int v,
-                                            bool active, const StepIn& in) {
+                                            bool active, const StepIn& in, int arr_drawn = 0) {
 #pragma clang fp contract(off)     // see step_tail
     StepPre r;
     const float B = in.B;
@@ -611,7 +621,10 @@ __device__ __forceinline__ StepPre step_pre(const Dims& d, const RisVecParams& P
     // The Philox draw is the production path and must be the FALL-THROUGH: a null-pointer test is predicted "unlikely",
     // which put the draw out of line -- two taken branches (two instruction-fetch restarts) per step for a lone wavefront.
     int arr = 0;
-    if constexpr (!ARR_LATE) {
+    if constexpr (ARR_DRAWN) {
+        static_assert(!ARR_LATE, "a drawn count is used here");
+        arr = A.arrivals == nullptr ? arr_drawn : in.arr_in;
+    } else if constexpr (!ARR_LATE) {
         if (__builtin_expect(A.arrivals == nullptr, 1)) {
             const uint4 x = philox4x32_10((uint32_t)(d.env_offset + e), (uint32_t)v, A.counter, kSiteArrivals, A.seed);
             arr = poisson_from_u(u01(x.x), P.poisson_cdf);
@@ -825,11 +838,11 @@ __device__ __forceinline__ StepCarry step_tail(const Dims& d, const RisVecParams
     return StepCarry{Bn, Q};
 }
 
-template <int VP, bool TRAJ = false, bool TM = false, class RIN = NoRing, class ST = StepStores>
+template <int VP, bool TRAJ = false, bool TM = false, class RIN = NoRing, class ST = StepStores, bool ARR_DRAWN = false>
 __device__ __forceinline__ StepCarry step_core(const Dims& d, const RisVecParams& P, const StepArgs& A,
                                                int e, int v, bool active, float gain, const StepIn& in,
-                                               const StepTraj* tj = nullptr, const RIN* rin = nullptr) {
-    const StepPre pre = step_pre<TRAJ>(d, P, A, e, v, active, in);
+                                               const StepTraj* tj = nullptr, const RIN* rin = nullptr, int arr_drawn = 0) {
+    const StepPre pre = step_pre<TRAJ, ARR_DRAWN>(d, P, A, e, v, active, in, arr_drawn);
     return step_tail<VP, TRAJ, TM, RIN, ST>(d, P, A, e, v, active, gain, in, pre, tj, rin);
 }
 
