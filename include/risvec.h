@@ -1040,6 +1040,42 @@ int risvec_marl_critic_grad(int32_t n_rows, int32_t state_dims, int32_t action_d
                             int32_t n_nets, const RisVecMarlCriticGradNet *nets, const RisVecMarlCriticGrads *grads,
                             const float *state, const float *action, const float *target, float *q1, float *q2, float *loss,
                             void *workspace, size_t workspace_bytes, risvec_stream_t stream);
+/* The critic side of the multi-agent (SAC) learner's actor update (Global_SAC_Critic.centralized_actor_update,
+ * Simulation-MARL-BCD/global_sac_critic.py:174-176 and the backward() at :246): d min(q1, q2) / d action for n_rows rows and
+ * n_nets in {1, 2} nets of one shape, without an autograd graph and without forming any weight gradient, in TWO launches on
+ * `stream`, per row b and net c:
+ *     d3 = qw [h3 > 0]   d2 = (W3^T d3) [h2 > 0]   d1 = (W2^T d2) [h1 > 0]   g_c[b, :] = (W1^T d1)[state_dims : state_dims + action_dims]
+ *     w_1, w_2 = (1, 0) if q_1 < q_2, (0, 1) if q_1 > q_2, (0.5, 0.5) if q_1 == q_2  (torch.min's backward; n_nets == 1: w_1 = 1)
+ *     out[b, :] = scale (w_1 g_1[b, :] + w_2 g_2[b, :])            q_min[b] = min(q_1[b], q_2[b])
+ * Launch 1 (grid: 32-row tiles x nets) walks the forward of risvec_marl_critic on the packed stream (q_c has its bits), keeps
+ * the ReLU masks as bits in registers, back-propagates the deltas within the workgroup -- the transposed products read the
+ * float32 W1, W2 and W3 IN PLACE, scaled by the power of two that `scales` records and split on the fly; a tile's deltas are
+ * multiplied by the exact power of two that brings its largest entry into [64, 128) and the accumulator is multiplied back --
+ * and leaves g_c and q_c in the workspace.  No W1 column at or beyond state_dims + action_dims is read.  Launch 2 (one thread
+ * per element of out) selects.  No atomics: every call gives the same bits.  No synchronisation, no allocation.
+ *   nets[c].fwd    the net as risvec_marl_critic takes it: a stream that is current for W1, W2, W3;
+ *   nets[c].W1 / W2 / W3  the float32 Linear weights [fc1, state_dims + action_dims] / [fc2, fc1] / [fc3, fc2] behind that
+ *                  stream, float-aligned;
+ *   state, action  as for risvec_marl_critic; no row >= n_rows is read;
+ *   scale          multiplies out (the actor loss's -1 / n_rows, say);
+ *   q1, q2 [n_rows]  optional: receive q_c; q2 with n_nets == 2 only;
+ *   q_min [n_rows] optional;   out [n_rows, action_dims] required; rows >= n_rows of neither are written;
+ *   workspace      risvec_marl_critic_action_grad_workspace(n_rows, ...) bytes (0: n_rows < 1, a shape that is not built, or
+ *                  n_nets outside {1, 2}), 16-byte aligned, of any content.
+ * Built for the shapes of risvec_marl_critic (risvec_marl_critic_action_grad_supported, host only); other shapes return
+ * RISVEC_ERR_UNSUPPORTED.  A NULL or misaligned pointer, n_rows < 1, n_nets outside {1, 2}, a wrong wstream_bytes and too
+ * small a workspace return RISVEC_ERR_ARG; all are reported before anything is launched and without touching a device. */
+typedef struct RisVecMarlCriticActionGradNet {
+    RisVecMarlCriticNet fwd;
+    const float *W1, *W2, *W3;
+} RisVecMarlCriticActionGradNet;
+int risvec_marl_critic_action_grad_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3);
+size_t risvec_marl_critic_action_grad_workspace(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1,
+                                                int32_t fc2, int32_t fc3, int32_t n_nets);
+int risvec_marl_critic_action_grad(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                                   int32_t fc3, int32_t n_nets, const RisVecMarlCriticActionGradNet *nets, const float *state,
+                                   const float *action, float scale, float *q1, float *q2, float *q_min, float *out,
+                                   void *workspace, size_t workspace_bytes, risvec_stream_t stream);
 /* Every agent's local twin target critics and local TD target of the multi-agent (SAC) learner (Agent.local_learn,
  * Simulation-MARL-BCD/sac_agent.py:263-284, called once per agent by global_sac_critic.py:373-392) in ONE launch for n_rows
  * rows and n_agents agents; grid (ceil(n_rows / 32), n_agents).  Agent j has n_nets in {1, 2} CriticNetworks of one shape

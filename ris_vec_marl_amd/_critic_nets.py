@@ -64,6 +64,16 @@ def grad_tables(count: int, nets, packed, grads):
     return table, out
 
 
+def action_grad_table(count: int, nets, packed):
+    """The `RisVecMarlCriticActionGradNet` array of a `risvec_marl_critic_action_grad` launch: `count` nets and their
+    (wstream, scales)."""
+    fwd = net_table(count, nets, packed)
+    table = (N.RisVecMarlCriticActionGradNet * count)()
+    for k, net in enumerate(nets):
+        table[k] = N.RisVecMarlCriticActionGradNet(fwd[k], net.W1.data_ptr(), net.W2.data_ptr(), net.W3.data_ptr())
+    return table
+
+
 def check_grads(grads, nets, what: str, device) -> list:
     """The caller's gradient tensors, nested like `BatchedAdam`'s groups: per net 8 contiguous float32 tensors shaped like
     the weights in `state_dict()` order, written in place.  -> a list of lists."""

@@ -170,6 +170,10 @@ class RisVecMarlCriticGradNet(C.Structure):
     _fields_ = [("fwd", RisVecMarlCriticNet), ("W2", _FP), ("W3", _FP)]
 
 
+class RisVecMarlCriticActionGradNet(C.Structure):
+    _fields_ = [("fwd", RisVecMarlCriticNet), ("W1", _FP), ("W2", _FP), ("W3", _FP)]
+
+
 class RisVecMarlCriticGrads(C.Structure):
     _fields_ = [("dW1", _FP), ("db1", _FP), ("dW2", _FP), ("db2", _FP), ("dW3", _FP), ("db3", _FP), ("dqw", _FP), ("dqb", _FP)]
 
@@ -291,6 +295,9 @@ _PROTOS = {
     "risvec_marl_critic_grad_supported": (C.c_int, [C.c_int32] * 5),
     "risvec_marl_critic_grad_workspace": (C.c_size_t, [C.c_int32] * 7),
     "risvec_marl_critic_grad": (C.c_int, [C.c_int32] * 7 + [_FP] * 9 + [C.c_size_t, _FP]),
+    "risvec_marl_critic_action_grad_supported": (C.c_int, [C.c_int32] * 5),
+    "risvec_marl_critic_action_grad_workspace": (C.c_size_t, [C.c_int32] * 7),
+    "risvec_marl_critic_action_grad": (C.c_int, [C.c_int32] * 7 + [_FP] * 3 + [C.c_float] + [_FP] * 5 + [C.c_size_t, _FP]),
     "risvec_local_critics_supported": (C.c_int, [C.c_int32] * 6),
     "risvec_local_critics": (C.c_int, [C.c_int32] * 8 + [_FP] * 7 + [C.c_float] + [_FP] * 7),
     "risvec_soft_update": (C.c_int, [C.c_int32, _FP, _FP, _FP, C.c_float, C.c_float, _FP]),

@@ -1374,6 +1374,51 @@ int risvec_marl_critic_grad(int32_t n_rows, int32_t state_dims, int32_t action_d
                                                       target, q1, q2, loss, workspace, (hipStream_t)stream));
 }
 
+int risvec_marl_critic_action_grad_supported(int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2, int32_t fc3) {
+    return risvec::marl_critic_action_grad_supported(state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;
+}
+
+size_t risvec_marl_critic_action_grad_workspace(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1,
+                                                int32_t fc2, int32_t fc3, int32_t n_nets) {
+    return risvec::marl_critic_action_grad_workspace(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets);
+}
+
+int risvec_marl_critic_action_grad(int32_t n_rows, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
+                                   int32_t fc3, int32_t n_nets, const RisVecMarlCriticActionGradNet* nets, const float* state,
+                                   const float* action, float scale, float* q1, float* q2, float* q_min, float* out,
+                                   void* workspace, size_t workspace_bytes, risvec_stream_t stream) {
+    const char* fn = "risvec_marl_critic_action_grad";
+    if (n_rows < 1) return fail(RISVEC_ERR_ARG, "%s: n_rows=%d must be >= 1", fn, n_rows);
+    if (n_nets < 1 || n_nets > 2) return fail(RISVEC_ERR_ARG, "%s: n_nets=%d must be 1 or 2", fn, n_nets);
+    if (!risvec::marl_critic_action_grad_supported(state_dims, action_dims, fc1, fc2, fc3))
+        return fail(RISVEC_ERR_UNSUPPORTED, "%s: state_dims=%d action_dims=%d fc1=%d fc2=%d fc3=%d (built for state_dims + "
+                    "action_dims <= 128, fc1 a multiple of 32 and <= 1024, fc2 = 128, 256 or 512, fc3 = 128 or 256; use library "
+                    "kernels elsewhere)", fn, state_dims, action_dims, fc1, fc2, fc3);
+    if (!nets) return fail(RISVEC_ERR_ARG, "%s: nets is NULL", fn);
+    const long long bytes = risvec::marl_critic_stream_bytes(state_dims, action_dims, fc1, fc2, fc3);
+    for (int c = 0; c < n_nets; ++c) {
+        const RisVecMarlCriticNet& n = nets[c].fwd;
+        const Indexed pre("nets", c);
+        if (int rc = check_wstream_bytes(fn, pre.s, n.wstream_bytes, bytes)) return rc;
+        REQ_PTR_IN(pre.s, n.wstream, "wstream"); REQ_PTR_IN(pre.s, n.scales, "scales"); REQ_PTR_IN(pre.s, n.b1, "b1");
+        REQ_PTR_IN(pre.s, n.b2, "b2"); REQ_PTR_IN(pre.s, n.b3, "b3"); REQ_PTR_IN(pre.s, n.qw, "qw");
+        if (!n.qb) return fail(RISVEC_ERR_ARG, "%s: %sqb is NULL", fn, pre.s);
+        REQ_F32_IN(pre.s, nets[c].W1, "W1"); REQ_F32_IN(pre.s, nets[c].W2, "W2"); REQ_F32_IN(pre.s, nets[c].W3, "W3");
+    }
+    if (!state || !action) return fail(RISVEC_ERR_ARG, "%s: state or action is NULL", fn);
+    OPT_F32_IN("", state, "state"); OPT_F32_IN("", action, "action");
+    if (!std::isfinite(scale)) return fail(RISVEC_ERR_ARG, "%s: scale must be finite", fn);
+    OPT_F32_IN("", q1, "q1"); OPT_F32_IN("", q2, "q2"); OPT_F32_IN("", q_min, "q_min");
+    if (n_nets == 1 && q2) return fail(RISVEC_ERR_ARG, "%s: q2 needs n_nets == 2", fn);
+    if (q1 && q1 == q2) return fail(RISVEC_ERR_ARG, "%s: q1 and q2 are the same buffer", fn);
+    REQ_F32_IN("", out, "out");
+    REQ_PTR(workspace, "workspace");
+    const size_t need = risvec::marl_critic_action_grad_workspace(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets);
+    if (int rc = check_workspace_bytes(fn, workspace_bytes, need, "call", "risvec_marl_critic_action_grad_workspace")) return rc;
+    return finish(fn, risvec::launch_marl_critic_action_grad(n_rows, state_dims, action_dims, fc1, fc2, fc3, n_nets, nets, state, action,
+                                                             scale, q1, q2, q_min, out, workspace, (hipStream_t)stream));
+}
+
 int risvec_local_critics_supported(int32_t n_agents, int32_t state_dims, int32_t action_dims, int32_t fc1, int32_t fc2,
                                    int32_t fc3) {
     return risvec::local_critics_supported(n_agents, state_dims, action_dims, fc1, fc2, fc3) ? 1 : 0;

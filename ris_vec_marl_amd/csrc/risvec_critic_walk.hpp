@@ -1,7 +1,8 @@
 // The critic walk: how a workgroup of four wavefronts takes one tile of 32 rows through a critic MLP, as
 // k_marl_critic.hip's header describes it.  This is the one place where its pieces exist; every critic kernel
 // instantiates them from here and adds only what it does differently:
-//   marl_stage_input  [state | action | 0 ..] -> split B fragments      k_marl_critic, k_marl_critic_wide, ..._grad_rows
+//   marl_stage_input  [state | action | 0 ..] -> split B fragments      k_marl_critic, k_marl_critic_wide, ..._grad_rows,
+//                                                                       ..._action_grad_rows (as every ..._grad_rows line below)
 //   critic_fc1_walk   the fc1 group walk, a callback per finished group k_sarl_critic, ..._grad_rows, marl_run_net
 //   critic_fc2        fc2 -> bias, ReLU -> s_h, a tap per output tile   ..._grad_rows, marl_run_tail
 //   critic_fc3_q      fc3, ReLU, the q dot product -> s_red[slot]       marl_run_tail

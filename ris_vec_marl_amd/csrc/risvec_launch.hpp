@@ -190,6 +190,16 @@ hipError_t launch_marl_critic_grad(long long n_rows, int S, int A, int F1, int F
                                    const RisVecMarlCriticGrads* grads, const float* state, const float* action, const float* target,
                                    float* q1, float* q2, float* loss, void* workspace, hipStream_t st);
 
+// d min(q1, q2) / d action in two launches (k_marl_critic_action_grad.hip), for the shapes of marl_critic_supported: the row
+// launch walks the forward and the deltas back to the action columns of W1^T and leaves g_c and q_c in the workspace (q_c in
+// q1 / q2 too where given); the select launch writes out and q_min (optional).  marl_critic_action_grad_workspace(): bytes
+// (0: no such shape, net count or n_rows).
+bool marl_critic_action_grad_supported(int S, int A, int F1, int F2, int F3);
+size_t marl_critic_action_grad_workspace(long long n_rows, int S, int A, int F1, int F2, int F3, int n_nets);
+hipError_t launch_marl_critic_action_grad(long long n_rows, int S, int A, int F1, int F2, int F3, int n_nets,
+                                          const RisVecMarlCriticActionGradNet* nets, const float* state, const float* action, float scale,
+                                          float* q1, float* q2, float* q_min, float* out, void* workspace, hipStream_t st);
+
 // Every agent's local twin critics and local TD target in one launch (k_local_critics.hip): n_agents x n_nets nets of the
 // shape of k_marl_critic at (S, A), nets[j n_nets + c] = agent j's net c, on agent j's columns of the batch.  Exactly one of
 // action / heads is given (heads with power and A == n_agents + 2); q1, q2 and y [n_agents, n_rows] are optional.

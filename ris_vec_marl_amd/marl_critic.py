@@ -13,8 +13,10 @@ which covers 16 vehicles); the log-probability sums arrive as
 tensors the learner already has.  `soft_update_from` is `update_global_network_parameters` (:394-400) for both nets in
 one launch; with pack="device" the next `td_target` rebuilds both weight streams in two launches in all
 (`risvec_marl_critic_pack`).  For the ONLINE critics `loss_backward` is the loss of `global_learn` (:355-363) and its
-gradient with respect to every weight in two launches (`risvec_marl_critic_grad`), without an autograd graph; the actor
-side of `global_learn` and the local critics' gradients stay with the learner.  No CPU compute path.
+gradient with respect to every weight in two launches (`risvec_marl_critic_grad`), without an autograd graph, and
+`action_grad` the critic side of `centralized_actor_update` (:174-176 and the `backward()` at :246): d min(q_1, q_2) / d action
+in two launches (`risvec_marl_critic_action_grad`), no weight gradient formed.  The policies' own backward and the local
+critics' gradients stay with the learner.  No CPU compute path.
 """
 from __future__ import annotations
 
@@ -24,8 +26,8 @@ from typing import Mapping, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _native as N
-from ._critic_nets import (CriticNets, _Net, check_grads, draw_net, entropy_args, grad_tables, minus_entropy, net_table, q_net,
-                           q_outs)
+from ._critic_nets import (CriticNets, _Net, action_grad_table, check_grads, draw_net, entropy_args, grad_tables, minus_entropy,
+                           net_table, q_net, q_outs)
 from ._weights import (is_f32, load_weight_sets, out_f32, pack_out, pack_workspace, polyak_pairs, polyak_tau, rows_of,
                        share_weight_sets, soft_update_tensors, td_args, td_select)
 from ._wstream import _WAVES, _by_wave, _frags, _from_wave, _split_scaled, _unfrags
@@ -435,6 +437,101 @@ class BatchedTwinCritic(CriticNets):
         loss.copy_(total.detach().view(1))
         self.last_grads = grads
         return loss
+
+    # ------------------------------------------------------------------ d min(q1, q2) / d action
+    #: with gemm=None, `action_grad` runs the two device launches for row counts in this closed range and
+    #: `action_grad_torch` elsewhere; gemm="fused" runs them at every row count.  The range is the measured row counts (64 /
+    #: 256 / 4 096; (40, 80) and (20, 24) inputs; profiles/marl_action_grad.json) at which the device form beat
+    #: `action_grad_torch` in every round at both shapes by more than the spread between rounds -- all three, 3.4x to 4.1x
+    #: with both weight streams rebuilt first; nothing below 64 or beyond 4 096 rows was measured, so the range ends there.
+    #: (): the device path is opt-in.
+    ACTION_GRAD_AUTO_ROWS = (64, 4096)
+
+    def _action_grad_device(self, n: int) -> bool:
+        if self.gemm != "fused":
+            return False
+        if not getattr(self, "_gemm_auto", False):
+            return True
+        rng = self.ACTION_GRAD_AUTO_ROWS
+        return len(rng) == 2 and rng[0] <= n <= rng[1]
+
+    def _action_grad_args(self, state, action, out, q_min, q, scale, what: str):
+        n, dev = self._rows(state, action), self.device
+        if action.requires_grad or state.requires_grad:
+            raise ValueError("%s: state and action are read as constants and the result is returned, not recorded; detach it"
+                             % what)
+        scale = float(scale)
+        if not scale == scale or scale in (float("inf"), float("-inf")):
+            raise ValueError("%s: scale must be finite" % what)
+        out = out_f32(out, (n, self.action_dims), what + ": out", dev)
+        if q_min is not None and not (is_f32(q_min, dev, (n,)) or is_f32(q_min, dev, (n, 1))):
+            raise ValueError("%s: q_min must be a contiguous float32 tensor of shape (%d,) or (%d, 1) on %s (it is written in "
+                             "place)" % (what, n, n, dev))
+        return n, out, self._q_outs(q, n, what + ": q"), scale
+
+    def action_grad(self, state: torch.Tensor, action: torch.Tensor, out: Optional[torch.Tensor] = None,
+                    q_min: Optional[torch.Tensor] = None, q=None, scale: float = 1.0,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The critic side of `centralized_actor_update` (`global_sac_critic.py:174-176` and the `backward()` at :246) for
+        these (online) critics without an autograd graph: out [n, action_dims] = scale * d min(Q_1, Q_2)(state, action) / d
+        action, row by row, in two launches (`risvec_marl_critic_action_grad`) after the stale weight streams were rebuilt;
+        where Q_1 == Q_2 each net counts half, as `torch.min`'s backward has it; n_nets == 1: scale * dQ / d action.  No
+        weight gradient is formed.  No synchronisation.  `out`: a caller-owned [n, action_dims] tensor; `q_min`: a
+        caller-owned [n] or [n, 1] tensor that receives min(Q_1, Q_2); `q`: caller-owned [n, 1] tensors (a pair; one when
+        n_nets == 1) that receive Q_c, with the bits of `forward`; `workspace`: a uint8 tensor of at least
+        `risvec_marl_critic_action_grad_workspace` bytes (default: one cached on this object and grown on demand).
+        Everything is read in place, and what would have to be copied is refused; an action that requires grad is refused
+        too -- detach it, and hand `out` to `torch.autograd.backward([actions_pi], [out])`.  gemm="library", gemm="wide" and
+        -- with gemm=None -- row counts outside `ACTION_GRAD_AUTO_ROWS` run `action_grad_torch` into the same buffers."""
+        what = "action_grad"
+        n, out, qs, scale = self._action_grad_args(state, action, out, q_min, q, scale, what)
+        if not self._action_grad_device(n):
+            return self._action_grad_torch(n, state, action, out, q_min, qs, scale)
+        lib, dev = N.load(), self.device
+        need = int(lib.risvec_marl_critic_action_grad_workspace(n, *self._dims, self.n_nets))
+        if workspace is None:
+            cached = getattr(self, "_action_grad_workspace", None)
+            if cached is None or cached.numel() < need:
+                cached = self._action_grad_workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = cached
+        else:
+            workspace = pack_workspace(workspace, need, what, dev)
+        nets = action_grad_table(self.n_nets, self.nets, self._fused_weights())
+        N.check(lib.risvec_marl_critic_action_grad(
+            n, *self._dims, self.n_nets, C.cast(nets, C.c_void_p), state.data_ptr(), action.data_ptr(), scale,
+            N.ptr(qs[0]) if qs is not None else None, N.ptr(qs[1]) if qs is not None and self.n_nets == 2 else None,
+            N.ptr(q_min), out.data_ptr(), workspace.data_ptr(), workspace.numel(), N.stream(dev)))
+        return out
+
+    def action_grad_torch(self, state: torch.Tensor, action: torch.Tensor, out: Optional[torch.Tensor] = None,
+                          q_min: Optional[torch.Tensor] = None, q=None, scale: float = 1.0) -> torch.Tensor:
+        """`action_grad` through autograd and library kernels (torch.cat, linear, relu, torch.min, autograd.grad with respect
+        to the action only, the weights detached): the fallback and the comparator.  The same arguments, checks and
+        outputs."""
+        n, out, qs, scale = self._action_grad_args(state, action, out, q_min, q, scale, "action_grad_torch")
+        return self._action_grad_torch(n, state, action, out, q_min, qs, scale)
+
+    def _action_grad_torch(self, n, state, action, out, q_min, qs, scale) -> torch.Tensor:
+        F = torch.nn.functional
+        with torch.enable_grad():
+            a = action.detach().view(n, self.action_dims).requires_grad_(True)
+            x = torch.cat([state.detach().view(n, self.state_dims), a], dim=1)
+            qv = []
+            for net in self.nets:
+                w = [getattr(net, k).detach() for k in _Net._WEIGHTS]
+                h = torch.relu(F.linear(x, w[0], w[1]))
+                h = torch.relu(F.linear(h, w[2], w[3]))
+                h = torch.relu(F.linear(h, w[4], w[5]))
+                qv.append(F.linear(h, w[6], w[7]))
+            m = torch.min(qv[0], qv[1]) if self.n_nets == 2 else qv[0]
+            g, = torch.autograd.grad(m.sum(), a)
+        if qs is not None:
+            for t, v in zip(qs, qv):
+                t.copy_(v.detach())
+        if q_min is not None:
+            q_min.copy_(m.detach().view(q_min.shape))
+        torch.mul(g, scale, out=out)
+        return out
 
     def q_torch(self, state: torch.Tensor, action: torch.Tensor) -> tuple:
         x = torch.cat([state, action], dim=1)
