@@ -57,10 +57,88 @@
 #define RISVEC_GEN_EARLY 1
 #endif
 
+// Wave priority by progress in the row-per-lane members (gen_row_lane_form, gen_prio_level below; EXPERIMENTS.md
+// 2026-10-21 (c)): schedule 1 ships, in the members gen_prio_of() names.  RISVEC_GEN_PRIO=0 builds the library that issues no s_setprio (the code before), 2
+// and 3 the schedules measured beside it (Makefile: gen_ab, q0 .. q3).
+#ifndef RISVEC_GEN_PRIO
+#define RISVEC_GEN_PRIO 1
+#endif
+
+// Diagnostic build only (Makefile: gen_ab, stamps / stamps_q1..q3; tools/gen_wave_timeline.py): the row-per-lane members
+// stamp s_memtime per wavefront into a buffer handed over through risvec_gen_stamps_buffer(), an entry point only that
+// library has.  The shipped kernel executes no stamp.
+#ifndef RISVEC_GEN_STAMPS
+#define RISVEC_GEN_STAMPS 0
+#endif
+
 namespace risvec {
 
 using GenStores = StorePolicy<RISVEC_GEN_STORES>;
 constexpr bool kGenEarlyDraw = RISVEC_GEN_EARLY != 0;
+constexpr int kGenPrio = RISVEC_GEN_PRIO;
+constexpr bool kGenStamps = RISVEC_GEN_STAMPS != 0;
+static_assert(kGenPrio >= 0 && kGenPrio <= 3, "RISVEC_GEN_PRIO: 0 (none) or schedule 1, 2, 3");
+
+// The priority of a row-lane wavefront once `done` of its NL leaves (the blocks of row_tree that run chains) are behind
+// it.  Vector issue among the wavefronts of a SIMD goes by priority, then age, so with every wavefront at one level the
+// oldest runs ahead and the youngest ends alone; keyed to progress, the one furthest behind is first in line.
+//   1: min(3, NL) at entry, one level down per leaf, 0 from the third leaf on and through step()
+//   2: as 1, but 3 again from the last leaf's fence (row_tree's folds and step(): latency-bound, little issue) to the end
+//   3: two levels: 1 until half the leaves are done, then 0
+constexpr int gen_prio_level(int schedule, int NL, int done) {
+    if (schedule == 3) return done < (NL + 1) / 2 ? 1 : 0;
+    if (schedule == 2 && done == NL) return 3;
+    const int top = NL < 3 ? NL : 3;
+    return schedule == 0 || done >= top ? 0 : top - done;
+}
+
+// The level to set once `done` leaves are behind, or -1 where the schedule has no change there.
+constexpr int gen_prio_change(int schedule, int NL, int done) {
+    if (schedule == 0) return -1;
+    const int now = gen_prio_level(schedule, NL, done);
+    return done == 0 || now != gen_prio_level(schedule, NL, done - 1) ? now : -1;
+}
+
+// The members that run the schedule: the ones it was measured to pay in -- the plain MARL core at 8 x 64, the headline.
+// With the ring core (bench.py --replay: a long tail of stores behind the chains) the same schedule LOSES 11 %: there the
+// wavefronts' stagger is what puts one wavefront's stores under the others' chains.  The other shapes are unmeasured.
+template <int V, int M, class Core>
+constexpr int gen_prio_of() {
+    return std::is_same<Core, MarlCore>::value && V == 8 && M == 64 ? kGenPrio : 0;
+}
+
+// row_tree_block() runs its leaves depth first, the far half of every fold behind the near one: leaf J is the
+// bit-reversed-J-th of the G/8 blocks.  Its rank among the leaves that run chains (8 J < NP):
+constexpr int gen_leaf_rank(int G, int NP, int J) {
+    auto rev = [](int G_, int j) {
+        int r = 0;
+        for (int b = 1; b < G_ / 8; b <<= 1) r = (r << 1) | ((j & b) ? 1 : 0);
+        return r;
+    };
+    int rank = 0;
+    for (int j = 0; j < G / 8; ++j)
+        if (8 * j < NP && rev(G, j) < rev(G, J)) ++rank;
+    return rank;
+}
+constexpr int gen_leaf_count(int G, int NP) { return (NP < G ? NP : G) / 8; }
+
+#if RISVEC_GEN_STAMPS
+// per wavefront kGenStampSlots uint64: the stamps in order, then [12], [13] s_memrealtime at entry and end, [14]
+// HW_REG_XCC_ID, [15] HW_REG_HW_ID | number of stamps << 32
+constexpr int kGenStampSlots = 16, kGenStampMax = 12;
+__device__ unsigned long long* g_gen_stamps = nullptr;
+__device__ long long g_gen_stamps_waves = 0;
+struct GenStamps {
+    unsigned long long t[kGenStampMax];
+    unsigned long long rt0;
+    int n = 0;
+    __device__ __forceinline__ void mark() { t[n++] = __builtin_amdgcn_s_memtime(); }
+};
+#else
+struct GenStamps {
+    __device__ __forceinline__ void mark() {}
+};
+#endif
 
 template <int V, int M>
 struct GenShape : PipeShape<V, M> {
@@ -443,14 +521,35 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
     const double* __restrict__ steer = KA.steer;
     const int n_groups_total = KA.n_groups_total;
 
+    constexpr int NL = gen_leaf_count(G, NP);                  // leaves that run chains
+    constexpr int PRIO = gen_prio_of<V, M, Core>();
+    [[maybe_unused]] GenStamps ts;
+    if constexpr (kGenStamps) {
+#if RISVEC_GEN_STAMPS
+        ts.rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+        ts.mark();                                             // entry
+    }
+
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / kWave) + wave);
-    if constexpr (TK) {
-        RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
-                                "s"(n_groups_total), "s"(d.E));
-    } else {
-        RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E));
+    // The arguments of the first requests in one scalar round trip (RISVEC_ARGS_IN_ONE_TRIP).  The entry level of a
+    // priority schedule (RISVEC_GEN_PRIO) is this statement's text, in front of the first request to memory, for the
+    // reason given at the leaf's fence below.
+    constexpr int level0 = gen_prio_change(PRIO, NL, 0);
+#define RISVEC_GEN_ENTRY(text, ...)                                                                                        \
+    if constexpr (TK) {                                                                                                    \
+        asm volatile(text ::"s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b), "s"(n_groups_total), \
+                     "s"(d.E)__VA_ARGS__);                                                                                 \
+    } else {                                                                                                               \
+        asm volatile(text ::"s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E)__VA_ARGS__);    \
     }
+    if constexpr (level0 >= 0) {
+        RISVEC_GEN_ENTRY("s_setprio %[level]", , [level] "n"(level0))
+    } else {
+        RISVEC_GEN_ENTRY("", )
+    }
+#undef RISVEC_GEN_ENTRY
     const int grp = wid;
     if (grp >= n_groups_total) return;                         // whole wave
 
@@ -499,6 +598,11 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
         asm volatile("" : "+v"(arr));
     }
     Core::hold(in);
+    if constexpr (kGenStamps) {                                // what the first vmcnt wait is for: the lane's theta and b
+        if constexpr (TK) asm volatile("" : "+v"(kq.w[0]), "+v"(bq[0].x));
+        else asm volatile("" : "+v"(tq[0].x), "+v"(bq[0].x));
+        ts.mark();
+    }
 
     // the env's w0 / w1 of float4 p, cmul(theta, b) as the reading lane p forms them: Q per lane, shared through s_w
     float4* __restrict__ wrow = s_w[wave] + i_env * WS;
@@ -542,18 +646,61 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
                 // (32 float4 in registers at M = 64) and the fourth wavefront per SIMD is lost.  The partials pass through
                 // an empty asm that clobbers memory: the next chunk's LDS reads cannot rise above it, nor this chunk's
                 // arithmetic sink below it.
-                asm volatile("" : "+v"(acc[0].x), "+v"(acc[0].y), "+v"(acc[1].x), "+v"(acc[1].y), "+v"(acc[2].x), "+v"(acc[2].y),
-                                  "+v"(acc[3].x), "+v"(acc[3].y), "+v"(acc[4].x), "+v"(acc[4].y), "+v"(acc[5].x), "+v"(acc[5].y),
-                                  "+v"(acc[6].x), "+v"(acc[6].y), "+v"(acc[7].x), "+v"(acc[7].y)
-                             :
-                             : "memory");
+                //
+                // A change of wave priority (RISVEC_GEN_PRIO) is the TEXT of the leaf's last fence, not an instruction of
+                // its own: the compiler sees the same statement with the same operands wherever the text is empty or not,
+                // so nothing else moves.  (__builtin_amdgcn_s_setprio ends a scheduling region: with it the M = 64 members
+                // need 115 ... 146 registers instead of 93 ... 122 and the ring core loses its fourth wavefront.)
+#define RISVEC_GEN_FENCE(text, ...)                                                                                            \
+    asm volatile(text : "+v"(acc[0].x), "+v"(acc[0].y), "+v"(acc[1].x), "+v"(acc[1].y), "+v"(acc[2].x), "+v"(acc[2].y),       \
+                        "+v"(acc[3].x), "+v"(acc[3].y), "+v"(acc[4].x), "+v"(acc[4].y), "+v"(acc[5].x), "+v"(acc[5].y),       \
+                        "+v"(acc[6].x), "+v"(acc[6].y), "+v"(acc[7].x), "+v"(acc[7].y)                                        \
+                 : __VA_ARGS__                                                                                                \
+                 : "memory")
+                constexpr int level = gen_prio_change(PRIO, NL, gen_leaf_rank(G, NP, J) + 1);
+                if constexpr (level >= 0) {
+                    if (it + 1 == NIT) RISVEC_GEN_FENCE("s_setprio %[level]", [level] "n"(level));
+                    else RISVEC_GEN_FENCE("", );
+                } else {
+                    RISVEC_GEN_FENCE("", );
+                }
+#undef RISVEC_GEN_FENCE
             }
+            if constexpr (kGenStamps) ts.mark();               // behind the leaf's last fence
         }
     };
-    const float2 img = row_tree<G>(leaf);
+    float2 img = row_tree<G>(leaf);
+    if constexpr (kGenStamps) {
+        asm volatile("" : "+v"(img.x), "+v"(img.y));
+        ts.mark();                                             // row_tree
+    }
 
     const GenArgs<Core>& L = late_args<Core>();
+#if RISVEC_GEN_STAMPS
+    {
+        int e_late = L.d.E;                                    // one field of the segment back: the wait for late_args()
+        asm volatile("" : "+s"(e_late));
+        ts.mark();
+    }
+#endif
     Core::template run<VP, GenStores, kGenEarlyDraw>(L.d, L.P, L.A, e_mine, v_mine, active, img, in, arr);
+#if RISVEC_GEN_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the last store has left
+    ts.mark();
+    const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
+    static_assert(NL + 5 <= kGenStampMax, "entry, first wait, NL leaves, tree, late, end");
+    unsigned long long* __restrict__ out = g_gen_stamps;
+    if (out != nullptr && wid < g_gen_stamps_waves && lane == 0) {
+        out += (long long)wid * kGenStampSlots;
+#pragma unroll
+        for (int i = 0; i < NL + 5; ++i) out[i] = ts.t[i];
+        out[12] = ts.rt0;
+        out[13] = rt1;
+        out[14] = __builtin_amdgcn_s_getreg(20 | (31 << 11));                                  // HW_REG_XCC_ID
+        out[15] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11))      // HW_REG_HW_ID
+                  | ((unsigned long long)(NL + 5) << 32);
+    }
+#endif
 }
 
 // The shapes whose one-group member is the row-per-lane form: those that keep four wavefronts per SIMD (128 VGPRs) with it.
@@ -614,6 +761,20 @@ static hipError_t launch_gen(const RisVecState& s, const typename Core::Params& 
 }
 
 int last_gen_launch_groups_per_wave() { return g_gen_per_wave; }
+
+#if RISVEC_GEN_STAMPS
+// The stamp buffer of the row-per-lane members: n_waves x kGenStampSlots uint64 of device memory, or nullptr to stop.
+// Synchronous; the caller keeps the buffer alive until it has handed over nullptr.
+extern "C" int risvec_gen_stamps_buffer(void* buf, long long n_waves) {
+    unsigned long long* p = static_cast<unsigned long long*>(buf);
+    if (buf == nullptr) n_waves = 0;
+    hipError_t err = hipDeviceSynchronize();
+    if (err == hipSuccess) err = hipMemcpyToSymbol(HIP_SYMBOL(g_gen_stamps_waves), &n_waves, sizeof(n_waves));
+    if (err == hipSuccess) err = hipMemcpyToSymbol(HIP_SYMBOL(g_gen_stamps), &p, sizeof(p));
+    if (err == hipSuccess) err = hipDeviceSynchronize();
+    return (int)err;
+}
+#endif
 
 // the shapes whose rows are whole chunks have GEN members; the others keep reading
 template <int V, int M, bool WHOLE = (M % kGeoChunk == 0)>
