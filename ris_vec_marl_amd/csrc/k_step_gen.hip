@@ -71,13 +71,28 @@
 #define RISVEC_GEN_STAMPS 0
 #endif
 
+// The HD row-per-lane members request a chunk's head one leaf ahead of the leaf that starts from it, not all NCH at entry, and
+// step()'s inputs at the top of the second leaf (gen_row_lane_form, gen_head_rank below; EXPERIMENTS.md 2026-10-21 (d)), in
+// the members gen_heads_ahead_of() / gen_late_in_of() name.  RISVEC_GEN_HEADS_AHEAD=0 builds the library that requests every
+// head at entry, 2 the one that requests two leaves ahead; RISVEC_GEN_LATE_IN=0 the library that requests step()'s inputs
+// at entry.  Both 0 is the code before (Makefile: gen_ab, h0, h1, h2, h1s, h2s).
+#ifndef RISVEC_GEN_HEADS_AHEAD
+#define RISVEC_GEN_HEADS_AHEAD 1
+#endif
+#ifndef RISVEC_GEN_LATE_IN
+#define RISVEC_GEN_LATE_IN 1
+#endif
+
 namespace risvec {
 
 using GenStores = StorePolicy<RISVEC_GEN_STORES>;
 constexpr bool kGenEarlyDraw = RISVEC_GEN_EARLY != 0;
 constexpr int kGenPrio = RISVEC_GEN_PRIO;
 constexpr bool kGenStamps = RISVEC_GEN_STAMPS != 0;
+constexpr int kGenHeadsAhead = RISVEC_GEN_HEADS_AHEAD;
+constexpr bool kGenLateIn = RISVEC_GEN_LATE_IN != 0;
 static_assert(kGenPrio >= 0 && kGenPrio <= 3, "RISVEC_GEN_PRIO: 0 (none) or schedule 1, 2, 3");
+static_assert(kGenHeadsAhead >= 0 && kGenHeadsAhead <= 2, "RISVEC_GEN_HEADS_AHEAD: 0 (all at entry), 1 or 2 leaves ahead");
 
 // The priority of a row-lane wavefront once `done` of its NL leaves (the blocks of row_tree that run chains) are behind
 // it.  Vector issue among the wavefronts of a SIMD goes by priority, then age, so with every wavefront at one level the
@@ -121,6 +136,47 @@ constexpr int gen_leaf_rank(int G, int NP, int J) {
     return rank;
 }
 constexpr int gen_leaf_count(int G, int NP) { return (NP < G ? NP : G) / 8; }
+
+// Heads D leaves ahead.  Chunk c is read by leaf c % (G/8) (a leaf at NIT = 2 owns chunks J and J + G/8).  The rank at
+// whose top -- behind the fence of the leaf before, in front of its first chain instruction -- the head of chunk c is
+// requested, or -1: with the entry batch.  D = 0 is the code before: every head at entry.  Otherwise the chunks of the
+// first D leaves in execution order travel at entry and the others D leaves ahead of their own, so the entry burst of
+// the launch (every wavefront of the grid within the same microsecond) carries D / NL of the heads' bytes.
+constexpr int gen_head_rank(int G, int NP, int D, int c) {
+    const int own = gen_leaf_rank(G, NP, c % (G / 8));
+    return D == 0 || own < D ? -1 : own - D;
+}
+// every chunk requested exactly once, at a rank below its own leaf's, and at entry exactly the first D leaves' chunks
+constexpr bool gen_head_schedule_ok(int G, int NP, int D) {
+    const int NL = gen_leaf_count(G, NP);
+    for (int c = 0; c < NP / 8; ++c) {
+        const int own = gen_leaf_rank(G, NP, c % (G / 8));
+        int n = 0;
+        for (int r = -1; r < NL; ++r)
+            if (gen_head_rank(G, NP, D, c) == r) {
+                ++n;
+                if (r >= own) return false;
+                if (D > 0 && (r == -1) != (own < D)) return false;
+            }
+        if (n != 1) return false;
+    }
+    return true;
+}
+
+// The members that request ahead: the ones it was measured to pay in -- the plain MARL core at 8 x 64, the headline -- and
+// only HD members have heads.  The ring core (bench.py --replay) and the other shapes keep the code before.
+template <int V, int M, class Core, bool HD>
+constexpr bool gen_ahead_member() {
+    return HD && std::is_same<Core, MarlCore>::value && V == 8 && M == 64;
+}
+template <int V, int M, class Core, bool HD>
+constexpr int gen_heads_ahead_of() {
+    return gen_ahead_member<V, M, Core, HD>() ? kGenHeadsAhead : 0;
+}
+template <int V, int M, class Core, bool HD>
+constexpr bool gen_late_in_of() {
+    return gen_ahead_member<V, M, Core, HD>() && kGenLateIn;
+}
 
 #if RISVEC_GEN_STAMPS
 // per wavefront kGenStampSlots uint64: the stamps in order, then [12], [13] s_memrealtime at entry and end, [14]
@@ -523,6 +579,11 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
 
     constexpr int NL = gen_leaf_count(G, NP);                  // leaves that run chains
     constexpr int PRIO = gen_prio_of<V, M, Core>();
+    constexpr int D = gen_heads_ahead_of<V, M, Core, HD>();    // heads requested D leaves ahead (0: all at entry)
+    constexpr bool LATE = gen_late_in_of<V, M, Core, HD>();    // step()'s inputs at the top of the leaf of rank IN_RANK
+    constexpr int IN_RANK = NL < 2 ? NL - 1 : 1;
+    static_assert(gen_head_schedule_ok(G, NP, 0) && gen_head_schedule_ok(G, NP, 1) && gen_head_schedule_ok(G, NP, 2),
+                  "every chunk's head is requested once, below its own leaf's rank");
     [[maybe_unused]] GenStamps ts;
     if constexpr (kGenStamps) {
 #if RISVEC_GEN_STAMPS
@@ -560,12 +621,15 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
     const int e_ld = active ? e_mine : d.E - 1;
     const int row = e_ld * V + v_mine;
     double2 head[HD ? NCH : 1];
-    if constexpr (HD) {
+    // the heads gen_head_rank() puts at rank R (-1: this batch), through the same clamped row wherever they are requested
+    auto request_heads = [&](auto rc) {
+        constexpr int R = decltype(rc)::value;
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) head[c] = reinterpret_cast<const double2*>(steer)[(long long)row * NCH + c];
-    } else {
-        head[0].x = steer[row];
-    }
+        for (int c = 0; c < NCH; ++c)
+            if (gen_head_rank(G, NP, D, c) == R) head[c] = reinterpret_cast<const double2*>(steer)[(long long)row * NCH + c];
+    };
+    if constexpr (HD) request_heads(std::integral_constant<int, -1>{});
+    else head[0].x = steer[row];
     const double2 z = reinterpret_cast<const double2*>(KA.z_r)[row];
     GenIdx<Q> kq;
     float4 tq[TK ? 1 : Q], bq[Q];
@@ -591,13 +655,15 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
                             "s"(KA.P.poisson_cdf[0]), "s"(KA.P.poisson_cdf[1]), "s"(KA.P.poisson_cdf[2]),
                             "s"(KA.P.poisson_cdf[3]), "s"(KA.P.poisson_cdf[4]), "s"(KA.P.poisson_cdf[5]),
                             "s"(KA.P.poisson_cdf[6]), "s"(KA.P.poisson_cdf[7]));
-    const In in = Core::load(d, A, e_mine, v_mine, active);
+    // (LATE: the draw and its arguments keep this place; the inputs are requested, and held, at the top of leaf IN_RANK)
+    In in;
+    if constexpr (!LATE) in = Core::load(d, A, e_mine, v_mine, active);
     int arr = 0;
     if constexpr (kGenEarlyDraw) {
         arr = Core::draw(d, KA.P, A, e_mine, v_mine);
         asm volatile("" : "+v"(arr));
     }
-    Core::hold(in);
+    if constexpr (!LATE) Core::hold(in);
     if constexpr (kGenStamps) {                                // what the first vmcnt wait is for: the lane's theta and b
         if constexpr (TK) asm volatile("" : "+v"(kq.w[0]), "+v"(bq[0].x));
         else asm volatile("" : "+v"(tq[0].x), "+v"(bq[0].x));
@@ -626,6 +692,23 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
     // block J of the partials: float4 gl = 8 J + k of the row, i.e. chunk J (then chunk J + G/8), against w of the same index
     auto leaf = [&](auto jc, float2 (&acc)[8]) {
         constexpr int J = decltype(jc)::value;
+        if constexpr (8 * J < NP && ((D > 0 && NL > 1) || LATE)) {
+            // Behind the fence of the leaf before (its memory clobber: no request rises above it) and in front of this
+            // leaf's chains: step()'s inputs where they are due, then the heads of the leaf D ranks on.  The inputs are
+            // held one leaf later, behind that leaf's own requests.  (load_step_in's requests stand under `if (active)`,
+            // which the compiler joins with a wait for zero: in fact they are waited for here, with this leaf's head.)
+            constexpr int R = gen_leaf_rank(G, NP, J);
+            if constexpr (LATE && R == IN_RANK) in = Core::load(d, A, e_mine, v_mine, active);
+            if constexpr (D > 0) request_heads(std::integral_constant<int, R>{});
+            // Left alone the scheduler sinks the request a hundred instructions into the leaf, behind the wait for this
+            // leaf's own head, which is then a wait for zero.  The statement's memory clobber keeps the requests above
+            // it, and it reads this leaf's heads, so the wait for them stands behind the requests and counts down to them.
+            if constexpr (HD) {
+                if constexpr (NIT == 1) asm volatile("" ::"v"(head[J].x), "v"(head[J].y) : "memory");
+                else asm volatile("" ::"v"(head[J].x), "v"(head[J].y), "v"(head[J + G / 8].x), "v"(head[J + G / 8].y) : "memory");
+            }
+            if constexpr (LATE && R == IN_RANK + 1) Core::hold(in);
+        }
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = make_float2(0.f, 0.f);
         if constexpr (8 * J < NP) {
@@ -670,6 +753,7 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
         }
     };
     float2 img = row_tree<G>(leaf);
+    if constexpr (LATE && IN_RANK + 1 >= NL) Core::hold(in);
     if constexpr (kGenStamps) {
         asm volatile("" : "+v"(img.x), "+v"(img.y));
         ts.mark();                                             // row_tree
