@@ -37,89 +37,44 @@
 //   * HD (RISVEC_STEP_STEER_HEADS_CURRENT): the sincospi at the head of a chunk is a function of the angle alone, so
 //     risvec_steer_heads() evaluates it once per geometry and the feed reads the float64 pair (steer_head() /
 //     steer_chunk_from_head(), risvec_dev.hpp): 48 vector instructions per pass less, 16 bytes per lane and pass more.
+//
+// Every GEN member writes step()'s outputs non-temporal (GenStores).  The row-per-lane members draw the arrivals while
+// their loads are in flight, and the headline among them runs a schedule of its own (GenRowSchedule).  Each of these was
+// measured against its alternatives, which are no longer built: EXPERIMENTS.md has the figures and the commit they can
+// be rebuilt from.  One build switch is left, the diagnostic RISVEC_GEN_STAMPS.
 #include <cstddef>
 
 #include "risvec_pipe.hpp"
+
+// Diagnostic build only (Makefile: gen_stamps; tools/gen_wave_timeline.py): the row-per-lane members stamp s_memtime per
+// wavefront into a buffer handed over through risvec_gen_stamps_buffer(), an entry point only that library has.  The
+// shipped kernel executes no stamp.
+#ifndef RISVEC_GEN_STAMPS
+#define RISVEC_GEN_STAMPS 0
+#endif
+
+namespace risvec {
 
 // How the GEN members write step()'s outputs (StorePolicy, risvec_step.hpp): every output with the non-temporal hint,
 // row-lane and stage form, both cores.  A launch leaves 48 V + 68 bytes per env behind (14.8 MB at 32 768 x 8) and
 // nothing on the device reads them before the launch ends; plain stores left them all dirty in L2 for the end of the
 // launch to write back.  Measured against plain, write-through and write-through with the re-read tensors or obs left
-// plain (EXPERIMENTS.md 2026-10-20 (d)); RISVEC_GEN_STORES builds the others (Makefile: gen_ab).
-#ifndef RISVEC_GEN_STORES
-#define RISVEC_GEN_STORES kStNonTemporal
-#endif
+// plain (EXPERIMENTS.md 2026-10-20 (d)).
+using GenStores = StorePolicy<kStNonTemporal>;
 
-// The row-per-lane members make the Philox arrival draw while the lane's loads are in flight, not behind the chains where
-// vector issue is the bound (gen_row_lane_form; EXPERIMENTS.md 2026-10-21).  RISVEC_GEN_EARLY=0 builds the library that
-// leaves the draw in step_pre (Makefile: gen_ab, e0).
-#ifndef RISVEC_GEN_EARLY
-#define RISVEC_GEN_EARLY 1
-#endif
-
-// Wave priority by progress in the row-per-lane members (gen_row_lane_form, gen_prio_level below; EXPERIMENTS.md
-// 2026-10-21 (c)): schedule 1 ships, in the members gen_prio_of() names.  RISVEC_GEN_PRIO=0 builds the library that issues no s_setprio (the code before), 2
-// and 3 the schedules measured beside it (Makefile: gen_ab, q0 .. q3).
-#ifndef RISVEC_GEN_PRIO
-#define RISVEC_GEN_PRIO 1
-#endif
-
-// Diagnostic build only (Makefile: gen_ab, stamps / stamps_q1..q3; tools/gen_wave_timeline.py): the row-per-lane members
-// stamp s_memtime per wavefront into a buffer handed over through risvec_gen_stamps_buffer(), an entry point only that
-// library has.  The shipped kernel executes no stamp.
-#ifndef RISVEC_GEN_STAMPS
-#define RISVEC_GEN_STAMPS 0
-#endif
-
-// The HD row-per-lane members request a chunk's head one leaf ahead of the leaf that starts from it, not all NCH at entry, and
-// step()'s inputs at the top of the second leaf (gen_row_lane_form, gen_head_rank below; EXPERIMENTS.md 2026-10-21 (d)), in
-// the members gen_heads_ahead_of() / gen_late_in_of() name.  RISVEC_GEN_HEADS_AHEAD=0 builds the library that requests every
-// head at entry, 2 the one that requests two leaves ahead; RISVEC_GEN_LATE_IN=0 the library that requests step()'s inputs
-// at entry.  Both 0 is the code before (Makefile: gen_ab, h0, h1, h2, h1s, h2s).
-#ifndef RISVEC_GEN_HEADS_AHEAD
-#define RISVEC_GEN_HEADS_AHEAD 1
-#endif
-#ifndef RISVEC_GEN_LATE_IN
-#define RISVEC_GEN_LATE_IN 1
-#endif
-
-namespace risvec {
-
-using GenStores = StorePolicy<RISVEC_GEN_STORES>;
-constexpr bool kGenEarlyDraw = RISVEC_GEN_EARLY != 0;
-constexpr int kGenPrio = RISVEC_GEN_PRIO;
-constexpr bool kGenStamps = RISVEC_GEN_STAMPS != 0;
-constexpr int kGenHeadsAhead = RISVEC_GEN_HEADS_AHEAD;
-constexpr bool kGenLateIn = RISVEC_GEN_LATE_IN != 0;
-static_assert(kGenPrio >= 0 && kGenPrio <= 3, "RISVEC_GEN_PRIO: 0 (none) or schedule 1, 2, 3");
-static_assert(kGenHeadsAhead >= 0 && kGenHeadsAhead <= 2, "RISVEC_GEN_HEADS_AHEAD: 0 (all at entry), 1 or 2 leaves ahead");
-
-// The priority of a row-lane wavefront once `done` of its NL leaves (the blocks of row_tree that run chains) are behind
-// it.  Vector issue among the wavefronts of a SIMD goes by priority, then age, so with every wavefront at one level the
-// oldest runs ahead and the youngest ends alone; keyed to progress, the one furthest behind is first in line.
-//   1: min(3, NL) at entry, one level down per leaf, 0 from the third leaf on and through step()
-//   2: as 1, but 3 again from the last leaf's fence (row_tree's folds and step(): latency-bound, little issue) to the end
-//   3: two levels: 1 until half the leaves are done, then 0
-constexpr int gen_prio_level(int schedule, int NL, int done) {
-    if (schedule == 3) return done < (NL + 1) / 2 ? 1 : 0;
-    if (schedule == 2 && done == NL) return 3;
+// The priority of a row-lane wavefront that runs the priority schedule once `done` of its NL leaves (the blocks of
+// row_tree that run chains) are behind it: min(3, NL) at entry, one level down per leaf, 0 from the third leaf on and
+// through step().  Vector issue among the wavefronts of a SIMD goes by priority, then age, so with every wavefront at one
+// level the oldest runs ahead and the youngest ends alone; keyed to progress, the one furthest behind is first in line.
+constexpr int gen_prio_level(int NL, int done) {
     const int top = NL < 3 ? NL : 3;
-    return schedule == 0 || done >= top ? 0 : top - done;
+    return done >= top ? 0 : top - done;
 }
 
 // The level to set once `done` leaves are behind, or -1 where the schedule has no change there.
-constexpr int gen_prio_change(int schedule, int NL, int done) {
-    if (schedule == 0) return -1;
-    const int now = gen_prio_level(schedule, NL, done);
-    return done == 0 || now != gen_prio_level(schedule, NL, done - 1) ? now : -1;
-}
-
-// The members that run the schedule: the ones it was measured to pay in -- the plain MARL core at 8 x 64, the headline.
-// With the ring core (bench.py --replay: a long tail of stores behind the chains) the same schedule LOSES 11 %: there the
-// wavefronts' stagger is what puts one wavefront's stores under the others' chains.  The other shapes are unmeasured.
-template <int V, int M, class Core>
-constexpr int gen_prio_of() {
-    return std::is_same<Core, MarlCore>::value && V == 8 && M == 64 ? kGenPrio : 0;
+constexpr int gen_prio_change(int NL, int done) {
+    const int now = gen_prio_level(NL, done);
+    return done == 0 || now != gen_prio_level(NL, done - 1) ? now : -1;
 }
 
 // row_tree_block() runs its leaves depth first, the far half of every fold behind the near one: leaf J is the
@@ -139,9 +94,10 @@ constexpr int gen_leaf_count(int G, int NP) { return (NP < G ? NP : G) / 8; }
 
 // Heads D leaves ahead.  Chunk c is read by leaf c % (G/8) (a leaf at NIT = 2 owns chunks J and J + G/8).  The rank at
 // whose top -- behind the fence of the leaf before, in front of its first chain instruction -- the head of chunk c is
-// requested, or -1: with the entry batch.  D = 0 is the code before: every head at entry.  Otherwise the chunks of the
-// first D leaves in execution order travel at entry and the others D leaves ahead of their own, so the entry burst of
-// the launch (every wavefront of the grid within the same microsecond) carries D / NL of the heads' bytes.
+// requested, or -1: with the entry batch.  D = 0: every head at entry.  Otherwise the chunks of the first D leaves in
+// execution order travel at entry and the others D leaves ahead of their own, so the entry burst of the launch (every
+// wavefront of the grid within the same microsecond) carries D / NL of the heads' bytes.  The members use D = 0 and 1
+// (GenRowSchedule); tests/test_gen_heads_ahead_host.py restates the rule for general D.
 constexpr int gen_head_rank(int G, int NP, int D, int c) {
     const int own = gen_leaf_rank(G, NP, c % (G / 8));
     return D == 0 || own < D ? -1 : own - D;
@@ -163,36 +119,59 @@ constexpr bool gen_head_schedule_ok(int G, int NP, int D) {
     return true;
 }
 
-// The members that request ahead: the ones it was measured to pay in -- the plain MARL core at 8 x 64, the headline -- and
-// only HD members have heads.  The ring core (bench.py --replay) and the other shapes keep the code before.
-template <int V, int M, class Core, bool HD>
-constexpr bool gen_ahead_member() {
-    return HD && std::is_same<Core, MarlCore>::value && V == 8 && M == 64;
-}
-template <int V, int M, class Core, bool HD>
-constexpr int gen_heads_ahead_of() {
-    return gen_ahead_member<V, M, Core, HD>() ? kGenHeadsAhead : 0;
-}
-template <int V, int M, class Core, bool HD>
-constexpr bool gen_late_in_of() {
-    return gen_ahead_member<V, M, Core, HD>() && kGenLateIn;
-}
-
+// The stamps of a row-lane wavefront (RISVEC_GEN_STAMPS).  Per wavefront kGenStampSlots uint64: the stamps in order, then
+// [12], [13] s_memrealtime at entry and end, [14] HW_REG_XCC_ID, [15] HW_REG_HW_ID | number of stamps << 32.
+// mark_behind() first passes the registers a wait of interest is for through an empty asm, so that the wait stands in
+// front of the stamp.  Without the switch every body is empty: no stamp, no pin.
+constexpr int kGenStampMax = 12;
 #if RISVEC_GEN_STAMPS
-// per wavefront kGenStampSlots uint64: the stamps in order, then [12], [13] s_memrealtime at entry and end, [14]
-// HW_REG_XCC_ID, [15] HW_REG_HW_ID | number of stamps << 32
-constexpr int kGenStampSlots = 16, kGenStampMax = 12;
+constexpr int kGenStampSlots = 16;
 __device__ unsigned long long* g_gen_stamps = nullptr;
 __device__ long long g_gen_stamps_waves = 0;
 struct GenStamps {
     unsigned long long t[kGenStampMax];
     unsigned long long rt0;
     int n = 0;
+    __device__ __forceinline__ void begin() {
+        rt0 = __builtin_amdgcn_s_memrealtime();
+        mark();
+    }
     __device__ __forceinline__ void mark() { t[n++] = __builtin_amdgcn_s_memtime(); }
+    template <class T0, class T1>
+    __device__ __forceinline__ void mark_behind(T0& v0, T1& v1) {
+        asm volatile("" : "+v"(v0), "+v"(v1));
+        mark();
+    }
+    __device__ __forceinline__ void mark_behind_scalar(int s) {
+        asm volatile("" : "+s"(s));
+        mark();
+    }
+    // behind the wavefront's last store: the closing stamp, and lane 0 writes the wavefront's slots (n_all stamps)
+    __device__ __forceinline__ void finish(int wid, int lane, int n_all) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        mark();
+        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
+        unsigned long long* __restrict__ out = g_gen_stamps;
+        if (out != nullptr && wid < g_gen_stamps_waves && lane == 0) {
+            out += (long long)wid * kGenStampSlots;
+#pragma unroll
+            for (int i = 0; i < n_all; ++i) out[i] = t[i];
+            out[12] = rt0;
+            out[13] = rt1;
+            out[14] = __builtin_amdgcn_s_getreg(20 | (31 << 11));                                  // HW_REG_XCC_ID
+            out[15] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11))      // HW_REG_HW_ID
+                      | ((unsigned long long)n_all << 32);
+        }
+    }
 };
 #else
 struct GenStamps {
+    __device__ __forceinline__ void begin() {}
     __device__ __forceinline__ void mark() {}
+    template <class T0, class T1>
+    __device__ __forceinline__ void mark_behind(T0&, T1&) {}
+    __device__ __forceinline__ void mark_behind_scalar(int) {}
+    __device__ __forceinline__ void finish(int, int, int) {}
 };
 #endif
 
@@ -213,6 +192,36 @@ struct GenShape : PipeShape<V, M> {
     static constexpr int NO = NCH / SP;                        // outer iterations per group
     static_assert(SP * UPP % S::CHUNKS == 0 && NCH % SP == 0 && NO * EPO == S::EPW, "outer iterations must tile the group");
     static constexpr int STAGE = kWave * (kGeoChunk / 2 + 1);  // float4 per wavefront: 64 chunks of 8 (+1 pad)
+};
+
+// The headline member: the plain MARL core at 8 x 64 (bench.py's default workload).  It alone takes the schedule below,
+// because that is where each part of it was measured to pay (EXPERIMENTS.md 2026-10-21 (c), (d)).  The ring core
+// (bench.py --replay: a long tail of stores behind the chains) LOSES with each part -- 11 % with the priority levels,
+// whose stagger is what puts one wavefront's stores under the others' chains, 5 ... 7 % with the heads a leaf ahead, with
+// or without the late inputs -- and 4 x 16 and 16 x 64 run as one-group launches in no benchmark leg: unmeasured.
+template <int V, int M, class Core>
+constexpr bool gen_headline_member() {
+    return std::is_same<Core, MarlCore>::value && V == 8 && M == 64;
+}
+
+// When a row-lane member (gen_row_lane_form) asks for what and at which priority its wavefronts run.  Every other member
+// than the headline sets no priority and requests everything a lane reads in one batch at entry.
+template <int V, int M, class Core, bool HD>
+struct GenRowSchedule {
+    using S = GenShape<V, M>;
+    static constexpr int NL = gen_leaf_count(S::G, S::NP);     // leaves that run chains
+    // wave priority by progress (gen_prio_level), each level the text of a statement that stands there anyway
+    static constexpr bool prio = gen_headline_member<V, M, Core>();
+    // only HD members have heads: the head of a chunk requested heads_ahead leaves ahead of the leaf that starts from it
+    // (gen_head_rank), 0: all NCH at entry
+    static constexpr int heads_ahead = HD && gen_headline_member<V, M, Core>() ? 1 : 0;
+    // step()'s inputs requested at the top of the leaf of rank in_rank and held at the top of the leaf after it, not at entry
+    static constexpr bool late_in = HD && gen_headline_member<V, M, Core>();
+    static constexpr int in_rank = NL < 2 ? NL - 1 : 1;
+    // the level to set once `done` leaves are behind, or -1: none
+    static constexpr int prio_change(int done) { return prio ? gen_prio_change(NL, done) : -1; }
+    static_assert(gen_head_schedule_ok(S::G, S::NP, 0) && gen_head_schedule_ok(S::G, S::NP, 1),
+                  "every chunk's head is requested once, below its own leaf's rank");
 };
 
 // what one outer iteration reads from memory: per pass the lane's chunk -- its row's angle, or (HD) the chunk's head as
@@ -265,6 +274,30 @@ __device__ __forceinline__ const GenArgs<Core>& late_args() {
     asm volatile("" : "+s"(seg));
     return *(const GenArgs<Core>*)seg;
 }
+
+// The arguments of a member's first requests in one scalar round trip (RISVEC_ARGS_IN_ONE_TRIP), in the names both forms
+// give them (steer, KA, A, n_groups_total, d; TK picks theta's source).  A statement, not a function: `text` is what the
+// row-lane form's entry priority level is written into (RISVEC_GEN_FENCE has the reason), and further operands follow a
+// comma: RISVEC_GEN_FIRST_ARGS("", ) or RISVEC_GEN_FIRST_ARGS("...", , operand, ...).
+#define RISVEC_GEN_FIRST_ARGS(text, ...)                                                                                   \
+    if constexpr (TK) {                                                                                                    \
+        asm volatile(text ::"s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b), "s"(n_groups_total), \
+                     "s"(d.E)__VA_ARGS__);                                                                                 \
+    } else {                                                                                                               \
+        asm volatile(text ::"s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E)__VA_ARGS__);    \
+    }
+
+// The fence behind a chain of the row-lane form's leaf: its eight partials `acc` pass through an asm that clobbers memory.
+// A change of wave priority is the TEXT of the leaf's last fence, not an instruction of its own: the compiler sees the
+// same statement with the same operands wherever the text is empty or not, so nothing else moves.
+// (__builtin_amdgcn_s_setprio ends a scheduling region: with it the M = 64 members need 115 ... 146 registers instead of
+// 93 ... 122 and the ring core loses its fourth wavefront.)  Hence a macro: the text of an asm must be a literal.
+#define RISVEC_GEN_FENCE(acc, text, ...)                                                                                   \
+    asm volatile(text : "+v"(acc[0].x), "+v"(acc[0].y), "+v"(acc[1].x), "+v"(acc[1].y), "+v"(acc[2].x), "+v"(acc[2].y),    \
+                        "+v"(acc[3].x), "+v"(acc[3].y), "+v"(acc[4].x), "+v"(acc[4].y), "+v"(acc[5].x), "+v"(acc[5].y),    \
+                        "+v"(acc[6].x), "+v"(acc[6].y), "+v"(acc[7].x), "+v"(acc[7].y)                                     \
+                 : __VA_ARGS__                                                                                             \
+                 : "memory")
 
 // TK: theta by index, as in k_step_fused_pipe.  ONE: every wavefront owns one group (group `wid`; per_wave and rev are
 // not read).  HD (RISVEC_STEP_STEER_HEADS_CURRENT): the head of a chunk, exp(-j pi ang m0) in float64, is a function of
@@ -406,12 +439,7 @@ __device__ __forceinline__ void gen_stage_form(const GenArgs<Core>& KA) {
     const int v_mine = lane % VP;
 
     if constexpr (ONE) {
-        if constexpr (TK) {
-            RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
-                                    "s"(n_groups_total), "s"(d.E));
-        } else {
-            RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E));
-        }
+        RISVEC_GEN_FIRST_ARGS("", )
         const int grp = wid;
         if (grp >= n_groups_total) return;                     // whole wave: no cross-lane op is skipped
         Feed cur;
@@ -445,13 +473,7 @@ __device__ __forceinline__ void gen_stage_form(const GenArgs<Core>& KA) {
         int grp = per_wave > 0 ? wid * per_wave : wid;
         int grp_end = per_wave > 0 ? grp + per_wave : n_groups_total;
         grp_end = grp_end < n_groups_total ? grp_end : n_groups_total;
-        if constexpr (TK) {
-            RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b),
-                                    "s"(n_groups_total), "s"(per_wave), "s"(d.E));
-        } else {
-            RISVEC_ARGS_IN_ONE_TRIP("s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(per_wave),
-                                    "s"(d.E));
-        }
+        RISVEC_GEN_FIRST_ARGS("", , "s"(per_wave))
         if (grp >= grp_end) return;                            // whole wave: no cross-lane op is skipped
         const int grp_first = grp;
         if (KA.rev) {                                          // a few scalar adds: a wavefront owns a handful of groups
@@ -577,40 +599,23 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
     const double* __restrict__ steer = KA.steer;
     const int n_groups_total = KA.n_groups_total;
 
-    constexpr int NL = gen_leaf_count(G, NP);                  // leaves that run chains
-    constexpr int PRIO = gen_prio_of<V, M, Core>();
-    constexpr int D = gen_heads_ahead_of<V, M, Core, HD>();    // heads requested D leaves ahead (0: all at entry)
-    constexpr bool LATE = gen_late_in_of<V, M, Core, HD>();    // step()'s inputs at the top of the leaf of rank IN_RANK
-    constexpr int IN_RANK = NL < 2 ? NL - 1 : 1;
-    static_assert(gen_head_schedule_ok(G, NP, 0) && gen_head_schedule_ok(G, NP, 1) && gen_head_schedule_ok(G, NP, 2),
-                  "every chunk's head is requested once, below its own leaf's rank");
-    [[maybe_unused]] GenStamps ts;
-    if constexpr (kGenStamps) {
-#if RISVEC_GEN_STAMPS
-        ts.rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-        ts.mark();                                             // entry
-    }
+    using SCH = GenRowSchedule<V, M, Core, HD>;
+    constexpr int NL = SCH::NL;                                // leaves that run chains
+    constexpr int D = SCH::heads_ahead;                        // heads requested D leaves ahead (0: all at entry)
+    constexpr bool LATE = SCH::late_in;                        // step()'s inputs at the top of the leaf of rank IN_RANK
+    constexpr int IN_RANK = SCH::in_rank;
+    GenStamps ts;
+    ts.begin();                                                // entry
 
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     const int wid = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock / kWave) + wave);
-    // The arguments of the first requests in one scalar round trip (RISVEC_ARGS_IN_ONE_TRIP).  The entry level of a
-    // priority schedule (RISVEC_GEN_PRIO) is this statement's text, in front of the first request to memory, for the
-    // reason given at the leaf's fence below.
-    constexpr int level0 = gen_prio_change(PRIO, NL, 0);
-#define RISVEC_GEN_ENTRY(text, ...)                                                                                        \
-    if constexpr (TK) {                                                                                                    \
-        asm volatile(text ::"s"(steer), "s"(KA.z_r), "s"(A.theta_k), "s"(A.theta_k_stride), "s"(A.b), "s"(n_groups_total), \
-                     "s"(d.E)__VA_ARGS__);                                                                                 \
-    } else {                                                                                                               \
-        asm volatile(text ::"s"(steer), "s"(KA.z_r), "s"(A.theta), "s"(A.b), "s"(n_groups_total), "s"(d.E)__VA_ARGS__);    \
-    }
+    // The entry level of the priority schedule is the text of the argument batch, in front of the first request to memory.
+    constexpr int level0 = SCH::prio_change(0);
     if constexpr (level0 >= 0) {
-        RISVEC_GEN_ENTRY("s_setprio %[level]", , [level] "n"(level0))
+        RISVEC_GEN_FIRST_ARGS("s_setprio %[level]", , [level] "n"(level0))
     } else {
-        RISVEC_GEN_ENTRY("", )
+        RISVEC_GEN_FIRST_ARGS("", )
     }
-#undef RISVEC_GEN_ENTRY
     const int grp = wid;
     if (grp >= n_groups_total) return;                         // whole wave
 
@@ -658,17 +663,11 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
     // (LATE: the draw and its arguments keep this place; the inputs are requested, and held, at the top of leaf IN_RANK)
     In in;
     if constexpr (!LATE) in = Core::load(d, A, e_mine, v_mine, active);
-    int arr = 0;
-    if constexpr (kGenEarlyDraw) {
-        arr = Core::draw(d, KA.P, A, e_mine, v_mine);
-        asm volatile("" : "+v"(arr));
-    }
+    int arr = Core::draw(d, KA.P, A, e_mine, v_mine);
+    asm volatile("" : "+v"(arr));
     if constexpr (!LATE) Core::hold(in);
-    if constexpr (kGenStamps) {                                // what the first vmcnt wait is for: the lane's theta and b
-        if constexpr (TK) asm volatile("" : "+v"(kq.w[0]), "+v"(bq[0].x));
-        else asm volatile("" : "+v"(tq[0].x), "+v"(bq[0].x));
-        ts.mark();
-    }
+    if constexpr (TK) ts.mark_behind(kq.w[0], bq[0].x);        // what the first vmcnt wait is for: the lane's theta and b
+    else ts.mark_behind(tq[0].x, bq[0].x);
 
     // the env's w0 / w1 of float4 p, cmul(theta, b) as the reading lane p forms them: Q per lane, shared through s_w
     float4* __restrict__ wrow = s_w[wave] + i_env * WS;
@@ -728,63 +727,28 @@ __device__ __forceinline__ void gen_row_lane_form(const GenArgs<Core>& KA) {
                 // One chain and its 8 float4 of w at a time: left to itself the compiler asks for all of the row's w first
                 // (32 float4 in registers at M = 64) and the fourth wavefront per SIMD is lost.  The partials pass through
                 // an empty asm that clobbers memory: the next chunk's LDS reads cannot rise above it, nor this chunk's
-                // arithmetic sink below it.
-                //
-                // A change of wave priority (RISVEC_GEN_PRIO) is the TEXT of the leaf's last fence, not an instruction of
-                // its own: the compiler sees the same statement with the same operands wherever the text is empty or not,
-                // so nothing else moves.  (__builtin_amdgcn_s_setprio ends a scheduling region: with it the M = 64 members
-                // need 115 ... 146 registers instead of 93 ... 122 and the ring core loses its fourth wavefront.)
-#define RISVEC_GEN_FENCE(text, ...)                                                                                            \
-    asm volatile(text : "+v"(acc[0].x), "+v"(acc[0].y), "+v"(acc[1].x), "+v"(acc[1].y), "+v"(acc[2].x), "+v"(acc[2].y),       \
-                        "+v"(acc[3].x), "+v"(acc[3].y), "+v"(acc[4].x), "+v"(acc[4].y), "+v"(acc[5].x), "+v"(acc[5].y),       \
-                        "+v"(acc[6].x), "+v"(acc[6].y), "+v"(acc[7].x), "+v"(acc[7].y)                                        \
-                 : __VA_ARGS__                                                                                                \
-                 : "memory")
-                constexpr int level = gen_prio_change(PRIO, NL, gen_leaf_rank(G, NP, J) + 1);
+                // arithmetic sink below it.  The leaf's last fence carries the schedule's change of priority, if it has one
+                // there (RISVEC_GEN_FENCE).
+                constexpr int level = SCH::prio_change(gen_leaf_rank(G, NP, J) + 1);
                 if constexpr (level >= 0) {
-                    if (it + 1 == NIT) RISVEC_GEN_FENCE("s_setprio %[level]", [level] "n"(level));
-                    else RISVEC_GEN_FENCE("", );
+                    if (it + 1 == NIT) RISVEC_GEN_FENCE(acc, "s_setprio %[level]", [level] "n"(level));
+                    else RISVEC_GEN_FENCE(acc, "", );
                 } else {
-                    RISVEC_GEN_FENCE("", );
+                    RISVEC_GEN_FENCE(acc, "", );
                 }
-#undef RISVEC_GEN_FENCE
             }
-            if constexpr (kGenStamps) ts.mark();               // behind the leaf's last fence
+            ts.mark();                                         // behind the leaf's last fence
         }
     };
     float2 img = row_tree<G>(leaf);
     if constexpr (LATE && IN_RANK + 1 >= NL) Core::hold(in);
-    if constexpr (kGenStamps) {
-        asm volatile("" : "+v"(img.x), "+v"(img.y));
-        ts.mark();                                             // row_tree
-    }
+    ts.mark_behind(img.x, img.y);                              // row_tree
 
     const GenArgs<Core>& L = late_args<Core>();
-#if RISVEC_GEN_STAMPS
-    {
-        int e_late = L.d.E;                                    // one field of the segment back: the wait for late_args()
-        asm volatile("" : "+s"(e_late));
-        ts.mark();
-    }
-#endif
-    Core::template run<VP, GenStores, kGenEarlyDraw>(L.d, L.P, L.A, e_mine, v_mine, active, img, in, arr);
-#if RISVEC_GEN_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the last store has left
-    ts.mark();
-    const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
+    ts.mark_behind_scalar(L.d.E);                              // one field of the segment back: the wait for late_args()
+    Core::template run<VP, GenStores, true>(L.d, L.P, L.A, e_mine, v_mine, active, img, in, arr);
     static_assert(NL + 5 <= kGenStampMax, "entry, first wait, NL leaves, tree, late, end");
-    unsigned long long* __restrict__ out = g_gen_stamps;
-    if (out != nullptr && wid < g_gen_stamps_waves && lane == 0) {
-        out += (long long)wid * kGenStampSlots;
-#pragma unroll
-        for (int i = 0; i < NL + 5; ++i) out[i] = ts.t[i];
-        out[12] = ts.rt0;
-        out[13] = rt1;
-        out[14] = __builtin_amdgcn_s_getreg(20 | (31 << 11));                                  // HW_REG_XCC_ID
-        out[15] = (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11))      // HW_REG_HW_ID
-                  | ((unsigned long long)(NL + 5) << 32);
-    }
-#endif
+    ts.finish(wid, lane, NL + 5);                              // the last store has left
 }
 
 // The shapes whose one-group member is the row-per-lane form: those that keep four wavefronts per SIMD (128 VGPRs) with it.

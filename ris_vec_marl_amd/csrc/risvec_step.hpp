@@ -358,8 +358,7 @@ inline int pick_group(int M, int vec, int VP) {
 // Three classes of output take a kind each: `out` (rate, data_t, data_p, reward, over_power, power_w, metrics: nobody on
 // the device reads them before the next kernel), `reread` (data_buf, mec_q, gain: the next launch or the cached step
 // reads them back) and `obs` (five 4-byte stores 20 bytes apart per lane).  StepStores is what a kernel gets when it
-// names no policy: plain everywhere -- with it a kernel compiles to what it was before the policy existed -- unless the
-// whole library is built with another kind (RISVEC_STEP_STORES: the A/B library of the Makefile's `stores_ab`).  The GEN
+// names no policy: plain everywhere -- with it a kernel compiles to what it was before the policy existed.  The GEN
 // members name their own (GenStores, k_step_gen.hip).  The replay ring's stores are not the policy's: they are
 // non-temporal always (ring_st*).
 enum : int { kStPlain = 0, kStThrough = 1, kStNonTemporal = 2 };
@@ -367,10 +366,7 @@ template <int OUT, int REREAD = OUT, int OBS = OUT>
 struct StorePolicy {
     static constexpr int out = OUT, reread = REREAD, obs = OBS;
 };
-#ifndef RISVEC_STEP_STORES
-#define RISVEC_STEP_STORES kStPlain
-#endif
-using StepStores = StorePolicy<RISVEC_STEP_STORES>;
+using StepStores = StorePolicy<kStPlain>;
 
 template <int KIND, class T>
 __device__ __forceinline__ void st_out(T* p, T v) {

@@ -1,24 +1,17 @@
 """GPU tests of when the HD row-per-lane GEN members (k_step_fused_gen<..., ONE, HD>, gen_row_lane_form) request the chunk
-heads of their rows: the heads of the first leaves with the entry batch, the others at the top of an earlier leaf
-(RISVEC_GEN_HEADS_AHEAD, gen_head_rank() in k_step_gen.hip), and -- in the A/B libraries that have it -- step()'s inputs at
-the top of the second leaf (RISVEC_GEN_LATE_IN).  Where a value is requested changes no value: GEN as the rule deals it
-(risvec_last_gen_groups_per_wave() == 1, heads read) must leave the bits of the reading form (h_r touched through torch:
-k_step_fused_pipe reads the rows) in every tensor a step writes, after each of three steps with data_buf / mec_q carried.
-No tolerance anywhere.
+heads of their rows and step()'s inputs (GenRowSchedule, gen_head_rank() in k_step_gen.hip).  The headline member (plain
+MARL core, 8 x 64) requests the head of the first leaf with the entry batch, every other head at the top of the leaf before
+its own, and step()'s inputs at the top of the second leaf; the ring core and the other shapes request everything in the
+entry batch.  Where a value is requested changes no value: GEN as the rule deals it (risvec_last_gen_groups_per_wave() ==
+1, heads read) must leave the bits of the reading form (h_r touched through torch: k_step_fused_pipe reads the rows) in
+every tensor a step writes, after each of three steps with data_buf / mec_q carried.  No tolerance anywhere.
 
   * shapes 8 x 64 and 16 x 64 (four leaves) and 4 x 16 (NCH = 1: nothing can be deferred, it must simply still be equal);
   * E in {1, EPW - 1, EPW + 1, 3 EPW + 1}: a deferred request on an inactive lane goes through the clamped row, and every
     output has a guard row behind E prefilled with a NaN pattern, which must stay unwritten;
   * MARL core and ring core; theta by index, and theta by tensor at EPW + 1;
   * renew_positions() + compute_parms() between steps two and three: the heads are rewritten there and the third step's
-    requests, entry and deferred, must read the new ones.
-
-Where the A/B libraries are built (make -C ris_vec_marl_amd/csrc gen_ab: librisvec_gen_h0 / h1 / h2 / h1s / h2s.so), a child
-process per library (a library is chosen once per process, RISVEC_LIB) runs every case above on it."""
-import os
-import subprocess
-import sys
-
+    requests, entry and deferred, must read the new ones."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -29,9 +22,6 @@ from tests.test_gen_row_lane_hip import ROW_LANE_SHAPES, SIZES, _hard_theta  # n
 from tests.test_hip_parity import make_vec  # noqa: E402
 from tests.test_theta_index_step_hip import DEV, STEP_KEYS, _N, _inputs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ris_vec_marl_amd", "csrc")
-AB_LIBS = ["h0", "h1", "h2", "h1s", "h2s"]
 STEPS = 3
 SEED = 9
 CORES = ["marl", "ring"]
@@ -130,29 +120,3 @@ def test_theta_by_tensor_same_bits_as_the_reading_form(V, M, size, core):
 @pytest.mark.parametrize("V,M,size,core", RENEW_CASES)
 def test_new_geometry_before_the_third_step_is_what_the_requests_read(V, M, size, core):
     _case(V, M, size, core, "index", renew=True)
-
-
-def _child():
-    """(an A/B library is loaded: RISVEC_LIB) every case of this module"""
-    for c in INDEX_CASES:
-        _case(*c, "index")
-    for c in TENSOR_CASES:
-        _case(*c, "tensor")
-    for c in RENEW_CASES:
-        _case(*c, "index", renew=True)
-    print("OK %d cases on %s" % (len(INDEX_CASES) + len(TENSOR_CASES) + len(RENEW_CASES), os.environ["RISVEC_LIB"]))
-
-
-@pytest.mark.parametrize("name", AB_LIBS)
-def test_ab_library_same_bits_as_its_reading_form(name):
-    lib = os.path.join(CSRC, "librisvec_gen_%s.so" % name)
-    if not os.path.isfile(lib):
-        pytest.skip("librisvec_gen_%s.so is not built (make -C ris_vec_marl_amd/csrc gen_ab)" % name)
-    env = dict(os.environ, RISVEC_LIB=lib, PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)], cwd=ROOT, env=env, timeout=300,
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0 and "OK " in r.stdout, r.stdout[-4000:]
-
-
-if __name__ == "__main__":
-    _child()

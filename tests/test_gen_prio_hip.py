@@ -1,6 +1,6 @@
-"""GPU tests of the row-per-lane GEN members (k_step_fused_gen<..., ONE>, gen_row_lane_form) as the library ships them -- with
-whatever wave-priority schedule RISVEC_GEN_PRIO left in them -- and of the DIAGNOSTIC build that stamps them
-(librisvec_gen_stamps.so, make -C ris_vec_marl_amd/csrc gen_ab; tools/gen_wave_timeline.py).
+"""GPU tests of the row-per-lane GEN members (k_step_fused_gen<..., ONE>, gen_row_lane_form) as the library ships them -- the
+headline member with its wave-priority schedule (GenRowSchedule, k_step_gen.hip) -- and of the DIAGNOSTIC build that stamps
+them (librisvec_gen_stamps.so, make -C ris_vec_marl_amd/csrc gen_stamps; tools/gen_wave_timeline.py).
 
 A priority level changes when a wavefront issues, never what: GEN as the rule deals it (risvec_last_gen_groups_per_wave()
 == 1) must leave the bits of the reading form (h_r touched through torch: k_step_fused_pipe reads the rows) in every tensor
@@ -96,7 +96,7 @@ def _child(path):
 @pytest.fixture(scope="module")
 def stamped(tmp_path_factory):
     if not os.path.isfile(STAMPS_LIB):
-        pytest.skip("librisvec_gen_stamps.so is not built (make -C ris_vec_marl_amd/csrc gen_ab)")
+        pytest.skip("librisvec_gen_stamps.so is not built (make -C ris_vec_marl_amd/csrc gen_stamps)")
     path = str(tmp_path_factory.mktemp("gen_stamps") / "out.npz")
     env = dict(os.environ, RISVEC_LIB=STAMPS_LIB, PYTHONPATH=ROOT)
     subprocess.run([sys.executable, os.path.abspath(__file__), path], cwd=ROOT, env=env, check=True, timeout=300)

@@ -2,8 +2,8 @@
 """Diagnostic: how the four wavefronts of a SIMD get through the row-per-lane GEN member of the headline shape
 (32 768 x 8 x 64, k_step_fused_gen<8,64,MarlCore,TK,ONE,HD>).
 
-Runs bench.py's default workload on a STAMPS build of the library (make -C ris_vec_marl_amd/csrc gen_ab ->
-librisvec_gen_stamps.so, or librisvec_gen_stamps_q<N>.so for a priority schedule): there gen_row_lane_form writes, per
+Runs bench.py's default workload on the STAMPS build of the library (make -C ris_vec_marl_amd/csrc gen_stamps ->
+librisvec_gen_stamps.so: the shipped kernel's schedule, with -DRISVEC_GEN_STAMPS=1): there gen_row_lane_form writes, per
 wavefront, s_memtime at entry / behind the first vmcnt wait / behind each leaf in execution order / behind row_tree /
 behind the wait for late_args() / behind the last store, and its hardware id.  The shipped kernel executes no stamp.
 
@@ -119,7 +119,7 @@ def summarize(launches: list, ticks_per_us) -> dict:
 
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--lib", required=True, help="a STAMPS build of the library")
+    ap.add_argument("--lib", required=True, help="the STAMPS build of the library: librisvec_gen_stamps.so (make gen_stamps)")
     ap.add_argument("--tag", required=True, help="profiles/<tag>_gen_timeline.json")
     ap.add_argument("--launches", type=int, default=32, help="launches reduced (each the last of a back-to-back burst)")
     ap.add_argument("--burst", type=int, default=4)
