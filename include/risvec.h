@@ -329,7 +329,9 @@ int risvec_reset(const RisVecState *s, const RisVecParams *p, const int32_t *spa
 
 /* renew_positions (ENV:412-542).  u_turn [E,V,8] float32 uniform draws consumed left
  * to right, one per detected lane crossing; NULL -> Philox.  n_used [E,V] int32
- * (optional) receives the number of draws consumed. */
+ * (optional) receives the number of draws consumed.  A move may need 2 * n_lanes draws (one per lane of the two
+ * lists a direction looks at); a u_turn row and the two Philox sites hold 8, so p->n_lanes > 4 is refused with
+ * RISVEC_ERR_UNSUPPORTED. */
 int risvec_mobility(const RisVecState *s, const RisVecParams *p, const float *u_turn,
                     int32_t *n_used, uint64_t seed, uint32_t counter, risvec_stream_t stream);
 

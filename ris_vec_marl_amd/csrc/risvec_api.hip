@@ -407,6 +407,10 @@ int risvec_mobility(const RisVecState* s, const RisVecParams* p, const float* u_
     if (int rc = check_common(fn, s, p)) return rc;
     REQ_PTR(s->pos, "state.pos"); REQ_PTR(s->dir, "state.dir"); REQ_PTR(s->vel, "state.vel");
     OPT_PTR(u_turn, "u_turn"); OPT_PTR(n_used, "n_used");
+    if (p->n_lanes > 4)     // a move may draw 2 * n_lanes numbers; a u_turn row and the two Philox sites hold 8
+        return fail(RISVEC_ERR_UNSUPPORTED,
+                    "%s: n_lanes=%d: a move may need 2*n_lanes turn draws and u_turn rows hold 8 (at most 4 lanes per direction)",
+                    fn, p->n_lanes);
     return finish(fn, risvec::launch_mobility(*s, *p, u_turn, n_used, seed, counter, (hipStream_t)stream));
 }
 

@@ -294,7 +294,9 @@ class VecEnviron(ParamAttrs, Currency):
         self._obs_stale = True         # DataBuf changed under the observation the last step wrote
 
     def renew_positions(self, u_turn=None, return_n_used: bool = False):
-        """Environment.py:412-542.  u_turn [E,V,8] float32 injected uniform draws."""
+        """Environment.py:412-542.  u_turn [E,V,8] float32 injected uniform draws, consumed left to right, one per
+        detected lane crossing.  A move may need 2 * n_lanes of them and a row holds 8: with more than four lanes per
+        direction the move is refused (RisVecError, RISVEC_ERR_UNSUPPORTED)."""
         self._ensure_device()
         E, V = self.n_envs, self.n_veh
         u = self._arg(u_turn, torch.float32, (E, V, 8), "u_turn")

@@ -1,7 +1,7 @@
 """The text of `risvec_last_error()` for the argument checks that the learner-side entry points share (the per-net table of
 `risvec_marl_critic` / `risvec_local_critics` and their output checks, the stream and workspace sizes and the float
 pointers of the three `*_pack` entry points, `risvec_soft_update`, `risvec_adam_step`'s pointers, the state pointers of
-`risvec_sarl_step` / `risvec_sarl_rollout`, the n_envs / n_veh range of the marshalling entry points): the code AND the
+`risvec_sarl_step` / `risvec_sarl_rollout`, the n_envs / n_veh range of the marshalling entry points, the lane limit of `risvec_mobility`): the code AND the
 message, byte for byte, one fault per call.  The pointers are aligned host addresses that are only checked, never
 dereferenced: nothing here touches a device."""
 import ctypes as C
@@ -259,3 +259,26 @@ def test_marshalling_dims_messages():
     says(calls["risvec_policy_sample"](4, 8, p + 4), N.ERR_ARG, "risvec_policy_sample: power_raw is not 16-byte aligned")
     says(calls["risvec_episode_clear"](4, 8, None), N.ERR_ARG, "risvec_episode_clear: acc is NULL")
     says(calls["risvec_episode_clear"](1 << 27, 64), N.ERR_SHAPE, "risvec_episode_clear: n_envs*(17+n_veh) must stay below 2^31")
+
+
+def test_mobility_refuses_more_than_four_lanes():
+    """A move may draw 2 * n_lanes numbers and a u_turn row (and the two Philox sites) hold 8: with more than four lanes per
+    direction `risvec_mobility` refuses, as `risvec_reset` does, before anything is launched.  1...4 lanes pass the check
+    (the next fault, a missing state pointer, is named instead)."""
+    lib, fn = N.load(), "risvec_mobility"
+    s = N.RisVecState()
+    s.abi_version, s.struct_bytes = N.ABI_VERSION, C.sizeof(N.RisVecState)
+    s.n_envs, s.n_veh, s.n_ris, s.control_bit = 4, 8, 40, 3
+    s.pos, s.dir, s.vel = FAKE, FAKE, FAKE
+
+    def call(n, u=FAKE, nu=FAKE):
+        lanes = {k: [100.0 + i for i in range(n)] for k in ("up_lanes", "down_lanes", "left_lanes", "right_lanes")}
+        return lib.risvec_mobility(C.byref(s), C.byref(rv.EnvParams().to_c(lanes, 400, 400)), u, nu, 0, 1, None)
+    for n in (5, 6, 7, 8):
+        for u in (FAKE, None):                                # injected and Philox draws alike
+            says(call(n, u=u), N.ERR_UNSUPPORTED,
+                 "%s: n_lanes=%d: a move may need 2*n_lanes turn draws and u_turn rows hold 8 (at most 4 lanes per direction)" % (fn, n))
+    s.vel = None
+    for n in (1, 2, 3, 4):
+        says(call(n), N.ERR_ARG, "%s: state.vel is NULL" % fn)
+    says(call(5), N.ERR_ARG, "%s: state.vel is NULL" % fn)    # in the order of the checks: the state's pointers first

@@ -1005,11 +1005,13 @@ def test_sarl_facade_and_philox():
 
 # ---------------------------------------------------------------------------- edge shapes
 @pytest.mark.parametrize("E,V,M,b", [(1, 1, 1, 0), (1, 1, 2, 1), (3, 2, 2, 2), (65, 64, 2, 3), (2, 7, 3, 3),
-                                     (129, 8, 64, 3), (31, 16, 256, 3), (5, 4, 16, 6)])
+                                     (129, 8, 64, 3), (31, 16, 256, 3), (5, 4, 16, 6),
+                                     (3, 64, 2048, 3), (2, 17, 1000, 3), (5, 1, 257, 2), (4, 33, 258, 3)])
 def test_edge_shapes_full_protocol(E, V, M, b):
     """Smallest / largest / ragged shapes through every kernel: reset, mobility, geometry, random phase,
     BCD, gains (fused and not), step - against the oracle on the device's own float32 tensors.
-    E is deliberately not a multiple of the envs a wave owns."""
+    E is deliberately not a multiple of the envs a wave owns.  The last four rows lie beyond M = 256 and V = 16, up to
+    the largest accepted shape (64 x 2048): the generic members of every family (no kernel sizes anything by M)."""
     rng = np.random.default_rng(E * 1000 + V * 10 + M)
     p = orc.OracleParams.yaml_effective()
     env = make_vec(E, V, M, b=b, seed=9, yaml=True)
